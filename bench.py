@@ -6,15 +6,21 @@ decode x5 + NMS), ResNet50FPN, 800x1280, batch 8 per GPU, bf16 autocast, channel
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --mode train ...            # BASELINE config 3: RN50FPN fp32 training, 2 images per GPU
+    python bench.py --full ...                  # + every figure below, the other configurations and the detail file
+    python bench.py --dump-outputs DIR ...      # + DIR/<name>.npy: what the last timed step returned (float32)
 
 One process per GPU.  Inference is embarrassingly parallel over images, so N>1 runs N
 replicas with NO data-path collective (weak scaling); the only collectives are the barrier and the
 MAX-reduction of the timed region.  A "step" is one call of the drop-in `Model.forward` (eval) on one
 device-resident synthetic batch -- since round 2 that call IS the BN-folded engine + the HIP
-post-processing (odtk/model.py); `--no-fuse` times the eager nn.Module graph instead, and the default run
+post-processing (odtk/model.py); `--no-fuse` times the eager nn.Module graph instead, and `--full`
 reports that number too (`eager`).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times `--steps` steps and prints the headline (`metric`, `value`, `unit`,
+`ms_per_step`, ...); nothing else runs on the GPU.  Inputs are seeded: the same arguments give the same
+images and weights.  Everything else is measured only with `--full`.
+
+Extra objects on the line with --full:
   roofline     -- the dominant kernel of the hand-written path (prefilter_scan_kernel, HBM-bound):
                   algorithmic bytes per launch (sizeof(dtype) x every score of the batch)
                   divided by its average launch duration measured with hipEvents on the launch stream
@@ -161,19 +167,22 @@ def run_train(args, rank, local_rank, world, dev):
         step()
     sync()
     elapsed, _ = parallel.timed_steps(step, args.steps, sync, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, cls_loss=losses[-1][0], box_loss=losses[-1][1])
     both = T.reduce_losses(losses[-1][0], losses[-1][1], world)
-    # the hand-written training-side kernels, timed on a few extra steps outside the timed region.  EVERY rank runs the
-    # steps (each one all-reduces gradients under DDP); only rank 0 records
+    # the hand-written training-side kernels, timed on a few extra steps outside the timed region (--full).  EVERY rank runs
+    # the steps (each one all-reduces gradients under DDP); only rank 0 records
     hip_kernels = None
-    if on_gpu:
+    profile = on_gpu and args.full
+    if profile:
         from odtk import _C
-    if rank == 0 and on_gpu:
+    if rank == 0 and profile:
         _C.profile_enable(True, ('retina_loss_kernel', 'loss_reduce_kernel', 'snap_to_anchors_kernel'))
         _C.profile_collect()
-    for _ in range(5 if on_gpu else 0):
+    for _ in range(5 if profile else 0):
         step()
     sync()
-    if rank == 0 and on_gpu:
+    if rank == 0 and profile:
         _C.profile_enable(False)
         prof = _C.profile_collect()
         hip_kernels = {k: {'us_per_step': round(v[0] / 5 * 1e3, 1), 'launches_per_step': v[1] // 5} for k, v in prof.items() if v[1]}
@@ -189,7 +198,7 @@ def run_train(args, rank, local_rank, world, dev):
             hip_kernels['retina_loss_kernel'].update({'alg_bytes_per_step': alg, 'achieved_GBps': round(alg / t / 1e9, 1),
                                                       'frac_of_hbm_peak': round(alg / t / 1e9 / HBM_PEAK_GBS, 4)})
     exposed = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same step on the bare module: identical compute, no gradient all-reduce (replicas drift apart from here on,
         # which no longer matters: nothing is timed with DDP after this)
         def quiet_step():
@@ -239,6 +248,15 @@ def kernel_src_hash():
         h.update(os.path.basename(f).encode())
         h.update(open(f, 'rb').read())
     return h.hexdigest()[:16]
+
+
+def plan_path(args):
+    """The committed engine plan of this workload (routes, convolution-library instances, hipBLASLt solutions: odtk/fused.py
+    plan_state), or None.  The plan pass picks all three by stopwatch, and near ties flip from run to run with other bits."""
+    name = '%s%s_%s_bs%d_%dx%d.json' % (short_name(args.backbone).lower(), '_rotated' if args.rotated_bbox else '', args.dtype,
+                                        args.batch, args.height, args.width)
+    path = os.path.join(ROOT, 'plans', name)
+    return path if os.path.isfile(path) else None
 
 
 def default_workload(args):
@@ -298,9 +316,22 @@ def build_parser():
                          'no roofline) -- never a measurement')
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'], help='default: nccl (= RCCL) on cuda, gloo on cpu')
     ap.add_argument('--tiny', action='store_true', help='ResNet18FPN on one 128x128 image per rank: the size the CPU tests run')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline and per-kernel figures, the eager A/B, the CPU baseline and parity check, '
+                         "BASELINE.json's other configurations and the detail file (a plain run times the steps only)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's scores / boxes / classes, or the "
+                         'training losses) as DIR/<name>.npy in float32')
     ap.add_argument('--detail-out', default=os.path.join(ROOT, 'gpurun_out', 'bench_detail_latest.json'),
                     help='where the full record (every leg, every sub-object) is written; the stdout line is the compact headline')
     return ap
+
+
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (a few KB: B x detections boxes, or two loss scalars)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def sanitize(obj):
@@ -339,7 +370,7 @@ def headline(full):
     h = {k: full.get(k) for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
                                   'scaling', 'vs_baseline', 'dtype', 'data')}
     cfg = full.get('config') or {}
-    h['config'] = pick(cfg, 'workload', 'global_batch', 'parallelism', 'entry', 'postproc', 'device', 'backend')
+    h['config'] = pick(cfg, 'workload', 'global_batch', 'parallelism', 'entry', 'postproc', 'device', 'backend', 'plan')
     if full.get('roofline'):
         h['roofline'] = pick(full['roofline'], 'kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic',
                              'alg_bytes_per_launch', 'avg_us', 'launches')
@@ -490,22 +521,23 @@ def main(argv=None):
         # the headline is safe from here on: printed FIRST to stderr (a leg that kills the process cannot take it down),
         # then the legs, then the one stdout line
         log('[bench] headline %.1f s: %s' % (time.perf_counter() - t_start, headline_line(line)))
-        # BASELINE.json's other configurations behind the headline (1 GPU, default invocation only): RN101FPN bs 16 (config 4),
+        # BASELINE.json's other configurations behind the headline (--full, 1 GPU, default invocation only): RN101FPN bs 16 (config 4),
         # --rotated-bbox bs 8 (config 5), the per-GPU share of config 3 (fp32 training, 2 images) and the batch-1 latency the
         # reference publishes for its TensorRT engines (README.md:26-34; timing loop extras/cppapi/infer.cpp:69-77)
-        if world == 1 and default_run and args.mode == 'infer' and not args.no_other_configs:
+        if world == 1 and default_run and args.mode == 'infer' and args.full and not args.no_other_configs:
             try:
                 line['other_configs'] = other_configs(args, rank, local_rank, world, dev)
             except Exception as e:                           # noqa: BLE001 -- never the headline's problem
                 line['other_configs'] = [{'key': 'legs', 'error': '%s: %s' % (type(e).__name__, e)}]
         line['wall_s'] = round(time.perf_counter() - t_start, 1)
-        try:
-            os.makedirs(os.path.dirname(args.detail_out), exist_ok=True)
-            with open(args.detail_out, 'w') as f:
-                f.write(json.dumps(sanitize(line), allow_nan=False, indent=1))
-            line['detail'] = os.path.relpath(args.detail_out, ROOT)
-        except OSError as e:
-            line['detail'] = 'not written: %s' % e
+        if args.full:
+            try:
+                os.makedirs(os.path.dirname(args.detail_out), exist_ok=True)
+                with open(args.detail_out, 'w') as f:
+                    f.write(json.dumps(sanitize(line), allow_nan=False, indent=1))
+                line['detail'] = os.path.relpath(args.detail_out, ROOT)
+            except OSError as e:
+                line['detail'] = 'not written: %s' % e
         real_stdout.write(headline_line(line) + '\n')
         real_stdout.flush()
     if world > 1:
@@ -515,6 +547,7 @@ def main(argv=None):
 def leg_args(args, **over):
     leg = copy.copy(args)
     leg.steps, leg.warmup, leg.cpu_seconds, leg.no_eager_leg = args.other_steps, min(args.warmup, 5), 0.0, True
+    leg.dump_outputs = None                                   # the headline's outputs only
     for k, v in over.items():
         setattr(leg, k, v)
     return leg
@@ -635,6 +668,8 @@ def run_infer_cpu_plumbing(args, rank, world, dev, model, amp_dtype):
     elapsed, out = parallel.timed_steps(step, args.steps, None, dev)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, scores=out[0], boxes=out[1], classes=out[2])
     return {'metric': 'images/sec end-to-end (incl. decode+NMS), %s %dpx bs=%d' % (short_name(args.backbone), args.height, args.batch),
             'value': round(args.batch * world * args.steps / elapsed, 2), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
@@ -672,15 +707,21 @@ def run_infer(args, rank, world, dev):
 
     g = torch.Generator(device='cpu').manual_seed(rank)
     x = torch.randn(args.batch, 3, args.height, args.width, generator=g).to(dev).contiguous(memory_format=torch.channels_last)
-    flops_img = conv_flops_per_image(model, x[:1])
+    flops_img = conv_flops_per_image(model, x[:1]) if args.full else None
 
     def autocast():
         return torch.autocast('cuda', dtype=amp_dtype, enabled=amp_dtype is not None)
+
+    plan_file = plan_path(args) if fuse_graph else None
+    plan = json.load(open(plan_file)) if plan_file else None
+    plan_taken = []                                          # (gemm, conv) library lines each load_plan took, in order
 
     def engine():
         e = model.inference_engine(amp_dtype or torch.float32)
         e.level_streams = not args.no_level_streams
         e.tower_plan = args.tower_plan
+        if plan is not None and e.libraries_taken is None:   # every engine of the run (calibration included) on the same plan
+            plan_taken.append(e.load_plan(plan))
         return e
 
     def timed_heads(inp):
@@ -703,22 +744,77 @@ def run_infer(args, rank, world, dev):
         out = step()
     torch.cuda.synchronize()
     n_det = int((out[0] > 0).sum().item())
+    # a plan pins only what this build still offers: a line the libraries did not take, or a hipBLASLt pin they no longer have,
+    # is timed as usual -- the run then loses the plan's routes and its outputs may differ from run to run
+    plan_record = None
+    if plan is not None:
+        kinds = [line.split(' ', 1)[0] for line in plan['libraries']]
+        plan_record = {'file': os.path.relpath(plan_file, ROOT), 'library_lines': [kinds.count('gemm'), kinds.count('conv')],
+                       'taken': list(plan_taken[0]), 'gemm_pin_misses': _C.gemm_plan_pin_misses()}
+        if rank == 0 and (plan_record['taken'] != plan_record['library_lines'] or plan_record['gemm_pin_misses']):
+            log('[bench] WARNING: %s does not fit this build (%s): the libraries timed what it does not pin, so the outputs may '
+                'differ from run to run' % (plan_record['file'], strict_json(plan_record)))
 
     # time only the three post-processing launches inside the timed region (6 event records per step);
     # the ~110 epilogue launches per step are timed in a separate, untimed pass below
     post = ('prefilter_scan_kernel', 'select_decode_kernel', 'nms_kernel',
             'nms_first_round_kernel', 'rotated_sup_matrix_kernel')   # (the last two: rotated boxes only, five launches)
     post = tuple(k for k in post if k in _C.KERNEL_NAMES)
-    _C.profile_enable(True, post)
-    _C.profile_collect()
+    if args.full:
+        _C.profile_enable(True, post)
+        _C.profile_collect()
     # EXACTLY `steps` steps between barrier + device-sync brackets, MAX over ranks (tested on CPU with
     # gloo, world_size 2: tests/test_parallel_gloo.py)
     elapsed, out = parallel.timed_steps(step, args.steps, torch.cuda.synchronize, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, scores=out[0], boxes=out[1], classes=out[2])
+    images = args.batch * world * args.steps
+    value = images / elapsed
+    line = None
+    if rank == 0:
+        line = {
+            'metric': 'images/sec end-to-end (incl. decode+NMS), %s%s %dpx bs=%d' % (
+                short_name(args.backbone), ' --rotated-bbox' if args.rotated_bbox else '', args.height, args.batch),
+            'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
+            'data': 'synthetic randn images, random-init weights; last cls conv rescaled so that %.4f %% of the scores '
+                    'are >= %.2f (SURVEY 8d sparse-realistic; logit sigma %.4f -> %.4f); %d detections in the last batch'
+                    % (100 * args.fraction, model.threshold, sigma0, sigma1, n_det),
+            'config': {'workload': '%s %s inference%s, bs=%d per GPU at %dx%d, HIP decode x5 + NMS'
+                                   % (args.backbone, args.dtype, (' --rotated-bbox' + (' (unit (sin, cos) head bias)' if args.unit_rotation else ''))
+                                      if args.rotated_bbox else '',
+                                      args.batch, args.height, args.width),
+                       'global_batch': args.batch * world, 'image': [args.height, args.width],
+                       'parallelism': 'replicas x%d (no data-path collective)' % world,
+                       'memory_format': 'channels_last', 'miopen_find': miopen_find, 'postproc': args.postproc,
+                       'entry': 'Model.forward (eval)',
+                       'graph': 'BN folded into conv weights + HIP bias/skip/ReLU epilogue + 1x1 convs as fused GEMMs' if fuse_graph
+                                else 'eager nn.Module under autocast',
+                       'plan': plan_record},
+        }
+    if not args.full:
+        model.__dict__['_engine_cache'].clear()
+        return line
     _C.profile_enable(False)
     prof = _C.profile_collect()
     eager = None
     epilogue_roofline, marker_timed, quoted_epilogue_obj = None, None, None
-    conv_epilogue = conv_epilogue_record(engine()) if (fuse_graph and rank == 0) else None
+    conv_epilogue = None
+    if fuse_graph and rank == 0:
+        measured = engine()
+        if plan is not None:
+            # the step ran the committed plan, which measures nothing: the plan pass's per-layer A/B -- what a run without a plan
+            # routes -- is taken on a second engine with no plan loaded (same weights, same input; the library instances and
+            # hipBLASLt solutions stay the plan's, they are pinned for the process)
+            from odtk.fused import FusedRetinaNet
+            measured = FusedRetinaNet(model, amp_dtype or torch.float32)
+            with torch.no_grad():
+                measured.plan(x)
+        conv_epilogue = conv_epilogue_record(measured)
+        if conv_epilogue is not None and plan is not None:
+            conv_epilogue['step_plan'] = dict(plan_record, plan_hash=engine().plan_hash())
+        del measured
     if rank == 0:
         # The engine's own epilogue kernels.  Their algorithmic bytes (every element read once and written once, + the skip
         # input) are counted live over three untimed steps.  Their TIME cannot be taken live: an event pair handed to a launch
@@ -793,9 +889,6 @@ def run_infer(args, rank, world, dev):
                      'ms_per_step': round(t_eager / n_eager * 1e3, 3), 'steps': n_eager,
                      'graph': 'eager nn.Module under autocast (Model.fused_graph = False), same post-processing'}
             model.fused_graph = True
-
-    images = args.batch * world * args.steps
-    value = images / elapsed
 
     # ---- roofline of the dominant hand-written kernel ----
     with torch.no_grad():
@@ -972,27 +1065,8 @@ def run_infer(args, rank, world, dev):
                                      {k: round(v, 2) for k, v in pipeline_trials.items()}),
                         'postproc': postproc}
 
-    line = None
     if rank == 0:
-        line = {
-            'metric': 'images/sec end-to-end (incl. decode+NMS), %s%s %dpx bs=%d' % (
-                short_name(args.backbone), ' --rotated-bbox' if args.rotated_bbox else '', args.height, args.batch),
-            'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
-            'data': 'synthetic randn images, random-init weights; last cls conv rescaled so that %.4f %% of the scores '
-                    'are >= %.2f (SURVEY 8d sparse-realistic; logit sigma %.4f -> %.4f); %d detections in the last batch'
-                    % (100 * args.fraction, model.threshold, sigma0, sigma1, n_det),
-            'config': {'workload': '%s %s inference%s, bs=%d per GPU at %dx%d, HIP decode x5 + NMS'
-                                   % (args.backbone, args.dtype, (' --rotated-bbox' + (' (unit (sin, cos) head bias)' if args.unit_rotation else ''))
-                                      if args.rotated_bbox else '',
-                                      args.batch, args.height, args.width),
-                       'global_batch': args.batch * world, 'image': [args.height, args.width],
-                       'parallelism': 'replicas x%d (no data-path collective)' % world,
-                       'memory_format': 'channels_last', 'miopen_find': miopen_find, 'postproc': args.postproc,
-                       'entry': 'Model.forward (eval)',
-                       'graph': 'BN folded into conv weights + HIP bias/skip/ReLU epilogue + 1x1 convs as fused GEMMs' if fuse_graph
-                                else 'eager nn.Module under autocast'},
+        line.update({
             'roofline': roofline, 'latency_bound': latency_bound, 'conv_roofline': conv_roofline, 'kernels': kernels,
             'postproc_us_per_step': round(sum(kernels[k]['avg_us'] * kernels[k]['launches'] for k in post if k in kernels) / max(n, 1), 2),
             'quoted': quoted, 'parity': parity, 'kernel_src_sha16': src_hash,
@@ -1001,7 +1075,7 @@ def run_infer(args, rank, world, dev):
             'spec_candidates_per_image_per_level': SPEC_CANDIDATES if (args.height, args.width) == (800, 1280) and not args.rotated_bbox else None,
             'eager': eager,
             'cpu_baseline': cpu_baseline,
-        }
+        })
     model.__dict__['_engine_cache'].clear()
     return line
 

@@ -4,6 +4,8 @@ import argparse
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -104,16 +106,59 @@ def test_sanitize_handles_tensors_and_numpy():
     assert out == {'a': None, 'b': 2.5, 'c': [1, None], '4': 3}
 
 
-def _run_bench(tmp_path, *flags):
+def _run_bench(tmp_path, *flags, full=True):
     detail = str(tmp_path / 'detail.json')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['OMP_NUM_THREADS'] = '2'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--device', 'cpu', '--tiny', '--steps', '2', '--warmup', '1',
-                        '--detail-out', detail] + list(flags), env=env, capture_output=True, text=True, timeout=900)
+                        '--detail-out', detail] + (['--full'] if full else []) + list(flags),
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout                          # ONE stdout line, whatever the ranks and legs did
-    return _strict_loads(lines[0]), json.load(open(detail))
+    return _strict_loads(lines[0]), (json.load(open(detail)) if full else None)
+
+
+def _dumps(folder):
+    import numpy as np
+    return {n: np.load(str(folder / (n + '.npy'))) for n in ('scores', 'boxes', 'classes')}
+
+
+def test_plain_run_dumps_the_last_step_and_writes_no_detail(tmp_path):
+    """A run without --full times the steps and prints the line, nothing more; --dump-outputs writes what the last timed step
+    returned, as float32 .npy files -- the same bits in a second run with the same arguments."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d, _ = _run_bench(tmp_path, '--dump-outputs', str(tmp_path / ('outputs%d' % i)), full=False)
+        assert d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['unit'] == 'images/s' and d['dtype'] == 'fp32'
+        assert not (tmp_path / 'detail.json').exists() and d.get('detail') is None
+        runs.append(_dumps(tmp_path / ('outputs%d' % i)))
+    arrays = runs[0]
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert arrays['scores'].shape == arrays['classes'].shape == arrays['boxes'].shape[:2] and arrays['boxes'].shape[2] == 4
+    assert all(np.array_equal(arrays[n].view(np.uint32), runs[1][n].view(np.uint32)) for n in arrays)
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_is_lean_and_reproducible(tmp_path):
+    """The default workload on the GPU without --full: the committed plan is loaded and fits this build (every library line
+    taken, no hipBLASLt pin missed), none of the --full figures is measured, and two runs write the same bits."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / ('outputs%d' % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                            '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _strict_loads(r.stdout.strip().splitlines()[-1])
+        assert d['steps'] == 2 and d['roofline'] is None and d['cpu_baseline'] is None and d['detail'] is None
+        assert not ({'latency_bound', 'conv_roofline', 'kernels_avg_us', 'eager', 'conv_epilogue', 'other_configs', 'parity'} & set(d))
+        plan = d['config']['plan']
+        assert plan['file'] == 'plans/rn50fpn_bf16_bs8_800x1280.json'
+        assert plan['taken'] == plan['library_lines'] and plan['gemm_pin_misses'] == 0 and 'WARNING' not in r.stderr
+        runs.append(_dumps(out))
+    assert all(np.array_equal(runs[0][n].view(np.uint32), runs[1][n].view(np.uint32)) for n in runs[0])
 
 
 def test_bare_gpus_2_spawns_its_own_ranks_infer(tmp_path):
@@ -149,3 +194,29 @@ def test_committed_pmc_traffic_is_for_these_kernel_sources():
     key = pmc['bf16_logits_channels_last']
     assert key['scores_per_launch'] == 122860800                     # 15 357 600 scores per image x 8
     assert 1.0 <= key['traffic_bytes'] / float(key['algorithmic_bytes']) <= 1.05
+
+
+def test_default_workload_runs_on_a_committed_plan():
+    """Same arguments, same outputs: the default workload's engine plan (routes, convolution-library instances, hipBLASLt
+    solutions -- picked by stopwatch when no plan is loaded) is committed, names only layers of its engine and leaves no k x k
+    convolution to MIOpen, whose find mode may pick kernels that do not reproduce their own bits."""
+    import torch
+    from odtk import fused
+    from odtk.model import Model
+    args = bench.build_parser().parse_args([])
+    args.batch, args.dtype = 8, 'bf16'
+    path = bench.plan_path(args)
+    assert path is not None and bench.default_workload(args)
+    plan = json.load(open(path))
+    assert plan['format'] == 'odtk-conv-plan-1' and plan['dtype'] == 'bfloat16' and plan['geometries'] == [[8, 3, 800, 1280]]
+    torch.manual_seed(0)
+    model = Model(backbones='ResNet50FPN', classes=80)
+    model.initialize(None)
+    convs = {n: m for n, m in fused.FusedRetinaNet(model.eval(), torch.bfloat16).named_modules() if isinstance(m, fused._Conv)}
+    assert set(plan['layers']) <= set(convs)
+    for name, routes in plan['layers'].items():
+        for key, library in routes.items():
+            assert library or convs[name].pointwise, (name, key)          # route 0 only for copy + GEMM
+    assert plan['stem'] and all(plan['stem'].values())
+    args.batch = 16
+    assert bench.plan_path(args) is None

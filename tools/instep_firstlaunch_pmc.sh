@@ -17,7 +17,7 @@ run() {   # tag counters... -- command
   python tools/pmc_read.py $(find $O/$tag -name '*_results.db' | head -1) --match odtk --skip 4 2>&1 | grep "prefilter_scan\|select_decode\|nms_kernel" | awk '{print $1, $2, $6, $NF}' | sed 's/_ZN4odtk[0-9]*//; s/INS_.*kd//; s/ILi.*kd//' > $O/$tag.txt
   cat $O/$tag.txt
 }
-STEP="python bench.py --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
+STEP="python bench.py --full --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
 B2B="python tools/postproc_bench.py --kind sparse --dtype bf16 --logits --channels-last --bias --batch 8 --iters 12"
 echo "== in step: tlb";      run step_tlb GRBM_UTCL2_BUSY GRBM_GUI_ACTIVE TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_STALL_MULTI_MISS_sum -- $STEP
 echo "== back to back: tlb"; run b2b_tlb  GRBM_UTCL2_BUSY GRBM_GUI_ACTIVE TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_STALL_MULTI_MISS_sum -- $B2B

@@ -17,7 +17,7 @@ run() {   # tag counters... -- command
   python tools/pmc_read.py $(find $O/$tag -name '*_results.db' | head -1) --match prefilter_scan --skip 4 > $O/$tag.txt 2>&1
   cat $O/$tag.txt
 }
-STEP="python bench.py --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
+STEP="python bench.py --full --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
 B2B="python tools/postproc_bench.py --kind sparse --dtype bf16 --logits --channels-last --bias --batch 8 --iters 12"
 run step_tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum -- $STEP
 run b2b_tcc  TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum -- $B2B

@@ -7,7 +7,10 @@
 #   (2) rocprofv3 --pmc (own passes, --kernel-trace only): UTCL1 translation misses and L2-TLB busy cycles of prefilter_scan_kernel
 O=gpurun_out/prefilter_tlb; mkdir -p $O
 export TMPDIR=/tmp ODTK_CONV_ROUTE=library
-BENCH="python3 bench.py --gpus 1 --steps 40 --warmup 8 --no-other-configs --no-eager-leg --cpu-seconds 0"
+# (bench.py now loads the default workload's committed plan, plans/rn50fpn_bf16_bs8_800x1280.json, whose routes take precedence
+#  over ODTK_CONV_ROUTE: the bench arms run that plan -- every k x k layer, the heads' last convolutions included, on the library,
+#  as this experiment needs, but layers.3.0.down as copy + GEMM and the library instances pinned by the plan)
+BENCH="python3 bench.py --full --gpus 1 --steps 40 --warmup 8 --no-other-configs --no-eager-leg --cpu-seconds 0"
 for rep in 1 2 3; do
   for A in 0 1; do
     if [ $A = 1 ]; then export ODTK_CLS_ARENA=1; else unset ODTK_CLS_ARENA; fi
@@ -25,7 +28,7 @@ run() {   # tag -- command
   python tools/pmc_read.py $(find $O/$tag -name '*_results.db' | head -1) --match odtk --skip 4 2>&1 | grep "prefilter_scan\|select_decode\|nms_kernel" | awk '{print $1, $2, $6, $NF}' | sed 's/_ZN4odtk[0-9]*//; s/INS_.*kd//; s/ILi.*kd//' > $O/$tag.txt
   cat $O/$tag.txt
 }
-STEP="python bench.py --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
+STEP="python bench.py --full --steps 12 --warmup 6 --cpu-seconds 0 --no-eager-leg --no-other-configs"
 unset ODTK_CLS_ARENA;    echo "== no arena: tlb counters"; run step_tlb_arena0 -- $STEP
 export ODTK_CLS_ARENA=1; echo "== arena: tlb counters";    run step_tlb_arena1 -- $STEP
 find $O -name "*.db" -size +8M -delete

@@ -12,7 +12,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 STEPS=${STEPS:-50}
 
-rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench -- python bench.py --steps $STEPS --warmup 10 --cpu-seconds 0 --no-eager-leg --no-other-configs \
+rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench -- python bench.py --full --steps $STEPS --warmup 10 --cpu-seconds 0 --no-eager-leg --no-other-configs \
     > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 DB=$(find $OUT/bench -name "*_results.db" | head -1)
 python tools/rocpd_stats.py "$DB" --steady prefilter_scan:$STEPS --csv $OUT/${R}_bench_steady_kernel_stats.csv --top 25 > $OUT/${R}_bench_steady_kernel_stats.txt 2>&1
@@ -31,10 +31,10 @@ pmc bf16_fused_sparse bf16_logits_channels_last 2 --kind sparse --dtype bf16 --l
 pmc fp32_sparse fp32_scores_nchw 4 --kind sparse
 
 # 3. MFMA utilisation of the convolution kernels (SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE, one pass, short run)
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT/pmc_mfma -o pmc -- python bench.py --steps 6 --warmup 4 \
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT/pmc_mfma -o pmc -- python bench.py --full --steps 6 --warmup 4 \
     --cpu-seconds 0 --no-eager-leg --no-other-configs > $OUT/pmc_mfma.log 2>&1
 python tools/pmc_mfma.py "$(find $OUT/pmc_mfma -name '*_results.db' | head -1)" --steps 3 --csv $OUT/${R}_pmc_mfma_bench.csv > $OUT/${R}_pmc_mfma_bench.txt 2>&1
-# (the other BASELINE configurations are legs of the default bench.py run since round 3: `other_configs` on its line)
+# (the other BASELINE configurations are legs of `bench.py --full`: `other_configs` on its line)
 rm -rf $OUT/bench/*/*.db.tmp 2>/dev/null
 # the raw rocpd databases are large: keep only the summaries
 find $OUT -name "*.db" -size +8M -delete
