@@ -65,7 +65,8 @@ extern "C" {
 
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
- * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t; -1 for any other value.  A binding compiled (or
+ * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t; -1 for any other value (4 stays
+ * unassigned: tests/test_abi_host.py probes it as the first unknown id).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -253,6 +254,39 @@ int odtk_upsample_nearest2x(const void *x, void *out, int batch_size, int height
  */
 int odtk_stem_pack(const void *x, void *out, int batch_size, int height, int width, int in_dtype, int channels_last, int out_dtype,
                    void *stream);
+
+/*
+ * odtk_preprocess_images -- the network's input from decoded source images, one launch for the whole batch: bilinear resize,
+ * optional mirror, zero padding to height x width, normalisation, channels_last.  Replaces, on the device, what the reference's
+ * dataset workers do per image on the host (odtk/data.py:56-59 `im.resize(.., Image.BILINEAR)`, :88 the flip, :111-117 the
+ * normalisation, :166-176 the padding of the batch) and what its DALI loader did on the GPU (odtk/dali.py); bit-identical to
+ * the former: Pillow's 8-bit resampling is fixed-point integer arithmetic, and the weights arrive as tables computed on the
+ * host in double (odtk/data.py: resample_weights).
+ *   images      HOST odtk_image_t[batch_size] (copied by value into the kernel arguments, kernels of up to 64 images)
+ *   src         DEVICE uint8, src_bytes long: the source pixels, R G B interleaved, 3 bytes per pixel; image i starts at
+ *               src + src_offset, its rows are src_pitch bytes apart
+ *   tables      DEVICE int32[tables_len].  One table per axis and (source length, target length) pair, at index t:
+ *               tables[t + 2 o], tables[t + 2 o + 1] = first source index and number of taps n <= taps of output index o
+ *               (o < target length), then tables[t + 2 * target + o * taps + i] = weight i of output o in units of 2^-22.
+ *               pass(s)[o] = clamp((2^21 + sum_i s[first + i] * weight[i]) >> 22, 0, 255); the horizontal pass runs first and
+ *               is rounded to bytes.  x_table / y_table = -1: that pass is skipped (requires source length == target length).
+ *   norm_table  DEVICE [3][256] of `dtype`: the value of byte v in channel c
+ *   out         DEVICE [batch_size, height, width, 3] of `dtype` (ODTK_F32 / BF16 / F16) = [batch, 3, height, width] with
+ *               channels_last strides; out[b][y][x][c] = norm_table[c][resized_b[y][mirror ? out_width - 1 - x : x][c]] for
+ *               y < out_height and x < out_width, +0.0 elsewhere.  Every element is written.
+ * Everything is checked on the host before anything touches HIP, including that every image and every table lies inside
+ * src_bytes / tables_len.  No workspace, no synchronisation.
+ */
+typedef struct odtk_image {
+  uint64_t src_offset;                      /* bytes from src to the first pixel                        */
+  int32_t src_width, src_height, src_pitch; /* pixels, pixels, bytes (>= 3 * src_width)                 */
+  int32_t out_width, out_height;            /* size after the resize (<= width, height of the batch)    */
+  int32_t mirror;                           /* 1: flip left-right AFTER the resize                      */
+  int32_t x_table, y_table;                 /* index of the axis' table in `tables`, -1: pass skipped   */
+  int32_t x_taps, y_taps;                   /* taps per output index of that table                      */
+} odtk_image_t;
+int odtk_preprocess_images(int batch_size, const odtk_image_t *images, const void *src, size_t src_bytes, const int32_t *tables,
+                           size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *stream);
 
 /*
  * odtk_gemm_bias_act -- 1x1 (pointwise) convolution of a channels_last activation as ONE GEMM with

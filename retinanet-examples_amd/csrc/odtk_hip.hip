@@ -26,6 +26,7 @@
 #include "targets.hpp"
 #include "loss.hpp"
 #include "gemm_lt.hpp"
+#include "preprocess.hpp"
 
 namespace {
 
@@ -792,6 +793,7 @@ int odtk_abi_struct_size(int which) {
     case 1: return static_cast<int>(sizeof(odtk_snap_level_t));
     case 2: return static_cast<int>(sizeof(odtk_snap_rot_level_t));
     case 3: return static_cast<int>(sizeof(odtk_loss_level_t));
+    case 5: return static_cast<int>(sizeof(odtk_image_t));
     default: return -1;
   }
 }
@@ -1167,6 +1169,59 @@ int odtk_stem_pack(const void *x, void *out, int batch_size, int height, int wid
   if (in_dtype == ODTK_F32) return stem_pack_launch<odtk::F32>(x, out, batch_size, height, width, channels_last, out_dtype, s);
   if (in_dtype == ODTK_BF16) return stem_pack_launch<odtk::BF16>(x, out, batch_size, height, width, channels_last, out_dtype, s);
   return stem_pack_launch<odtk::F16>(x, out, batch_size, height, width, channels_last, out_dtype, s);
+}
+
+// One axis of one image: the table (or the skipped pass) is consistent with the sizes and lies inside `tables`.
+static bool preprocess_axis_ok(int32_t table, int32_t taps, int32_t in_size, int32_t out_size, size_t tables_len) {
+  if (table < 0) return table == -1 && in_size == out_size;
+  if (taps <= 0) return false;
+  const unsigned long long need = 1ull * static_cast<uint32_t>(out_size) * (2ull + static_cast<uint32_t>(taps));
+  return need < (1ull << 31) && static_cast<unsigned long long>(table) + need <= tables_len;
+}
+
+int odtk_preprocess_images(int batch_size, const odtk_image_t *images, const void *src, size_t src_bytes, const int32_t *tables,
+                           size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *stream) {
+  if (!images || !src || !norm_table || !out || batch_size <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned es = dtype == ODTK_F32 ? 4u : 2u;
+  if ((reinterpret_cast<uintptr_t>(norm_table) | reinterpret_cast<uintptr_t>(out)) & (es - 1u)) return ODTK_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(tables) & 3u) return ODTK_ERR_INVALID;
+  if (3ull * height * width >= (1ull << 31) || (height + odtk::kPreTileH - 1) / odtk::kPreTileH > 65535) return ODTK_ERR_INVALID;
+  for (int b = 0; b < batch_size; ++b) {
+    const odtk_image_t &im = images[b];
+    if (im.src_width <= 0 || im.src_height <= 0 || im.out_width <= 0 || im.out_height <= 0) return ODTK_ERR_INVALID;
+    if (im.out_width > width || im.out_height > height || (im.mirror != 0 && im.mirror != 1)) return ODTK_ERR_INVALID;
+    if (im.src_pitch <= 0 || 3ll * im.src_width > im.src_pitch) return ODTK_ERR_INVALID;
+    const unsigned long long extent = 1ull * (im.src_height - 1) * im.src_pitch + 3ull * im.src_width;   // 32-bit offsets inside one image
+    if (extent >= (1ull << 31) || im.src_offset > src_bytes || extent > src_bytes - im.src_offset) return ODTK_ERR_INVALID;
+    if ((im.x_table >= 0 || im.y_table >= 0) && !tables) return ODTK_ERR_INVALID;
+    if (!preprocess_axis_ok(im.x_table, im.x_taps, im.src_width, im.out_width, tables_len) ||
+        !preprocess_axis_ok(im.y_table, im.y_taps, im.src_height, im.out_height, tables_len))
+      return ODTK_ERR_INVALID;
+  }
+  static_assert(sizeof(odtk::PreArgs) <= 4096, "kernel arguments travel by value");
+  odtk::PreArgs args;
+  args.src = static_cast<const uint8_t *>(src);
+  args.tables = tables;
+  args.norm = norm_table;
+  args.out = out;
+  args.height = height;
+  args.width = width;
+  args.vector_rows = ((3ull * width * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
+  const dim3 tiles((width + odtk::kPreTileW - 1) / odtk::kPreTileW, (height + odtk::kPreTileH - 1) / odtk::kPreTileH);
+  for (int first = 0; first < batch_size; first += odtk::kPreMaxImages) {   // one launch for batches of up to 64 images
+    const int n = batch_size - first < odtk::kPreMaxImages ? batch_size - first : odtk::kPreMaxImages;
+    args.first = first;
+    std::memcpy(args.images, images + first, sizeof(odtk_image_t) * n);
+    if (n < odtk::kPreMaxImages) std::memset(args.images + n, 0, sizeof(odtk_image_t) * (odtk::kPreMaxImages - n));
+    const dim3 grid(tiles.x, tiles.y, static_cast<unsigned>(n));
+    if (es == 4)
+      hipLaunchKernelGGL(odtk::preprocess_images_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), args);
+    else
+      hipLaunchKernelGGL(odtk::preprocess_images_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), args);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
 }
 
 int odtk_gemm_init(const char *hipblaslt_path) { return odtk::lt::init(hipblaslt_path); }

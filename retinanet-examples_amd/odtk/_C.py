@@ -64,6 +64,14 @@ class Level(ctypes.Structure):
                 ('cls_bias', _vp), ('box_bias', _vp), ('cls_thresholds', _vp)]
 
 
+class Image(ctypes.Structure):
+    """odtk_image_t"""
+    _fields_ = [('src_offset', ctypes.c_uint64), ('src_width', ctypes.c_int32), ('src_height', ctypes.c_int32),
+                ('src_pitch', ctypes.c_int32), ('out_width', ctypes.c_int32), ('out_height', ctypes.c_int32),
+                ('mirror', ctypes.c_int32), ('x_table', ctypes.c_int32), ('y_table', ctypes.c_int32),
+                ('x_taps', ctypes.c_int32), ('y_taps', ctypes.c_int32)]
+
+
 _SIGNATURES = {
     'odtk_version': (ctypes.c_char_p, []),
     'odtk_abi_struct_size': (ctypes.c_int, [ctypes.c_int]),
@@ -113,6 +121,8 @@ _SIGNATURES = {
                                                ctypes.c_int, ctypes.c_void_p]),
     'odtk_stem_pack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'odtk_preprocess_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), _vp, _sz, _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, _vp]),
     'odtk_nms_sorted_runs': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_gemm_init': (ctypes.c_int, [ctypes.c_char_p]),
@@ -157,7 +167,7 @@ def library():
             fn.restype = res
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
-        for which, mirror in enumerate((Level, SnapLevel, SnapRotLevel, LossLevel)):
+        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -789,6 +799,31 @@ def stem_pack(x, dtype):
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
         _check(library().odtk_stem_pack(x.data_ptr(), out.data_ptr(), n, h, w, _DTYPES[x.dtype], cl, _DTYPES[dtype], stream), 'stem_pack')
+    return out
+
+
+def preprocess_images(src, images, tables, table, height, width):
+    """The network's input from decoded source images in one launch (include/odtk_hip.h: odtk_preprocess_images): Pillow-exact
+    bilinear resize, mirror, zero padding to height x width, normalisation, channels_last.
+    src: uint8 CUDA tensor holding the source pixels (R G B interleaved); images: a ctypes array (or sequence) of `Image`, HOST
+    memory; tables: int32 CUDA tensor of the resampling tables (odtk/data.py: resample_weights; may be empty when no image is
+    resized); table: [3, 256] CUDA tensor of float32 / bfloat16 / float16, whose dtype is the output's.
+    -> [len(images), 3, height, width] with channels_last strides."""
+    if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise RuntimeError('preprocess_images: src must be a contiguous uint8 CUDA tensor')
+    if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
+        raise RuntimeError('preprocess_images: tables must be a contiguous int32 tensor on the device of src')
+    if table.device != src.device or table.dtype not in _DTYPES or tuple(table.shape) != (3, 256) or not table.is_contiguous():
+        raise RuntimeError('preprocess_images: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src')
+    if not isinstance(images, ctypes.Array):
+        images = (Image * len(images))(*images)
+    batch = len(images)
+    out = torch.empty((batch, 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
+    with torch.cuda.device(src.device):
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        _check(library().odtk_preprocess_images(batch, images, src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None,
+                                                tables.numel(), table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype],
+                                                stream), 'preprocess_images')
     return out
 
 

@@ -17,10 +17,15 @@ split of the work between the host and the GPU:
   * the batch is born NHWC: `[B, H, W, 3]` viewed as `[B, 3, H, W]` IS a channels_last tensor, the layout
     the convolutions want (the reference builds NCHW and converts every batch, infer.py:75, train.py:96).
 
+With `device_resize=True` the resize moves to the device as well: workers hand over the decoded SOURCE pixels (uint8 RGB, 3
+bytes per pixel) with the tables of Pillow's fixed-point bilinear resampling (`resample_weights`), and one HIP launch per batch
+(`odtk_preprocess_images`) resizes, mirrors, pads and normalises -- bit-identical to the host path, see `SourceBatch`.
+
 `CocoIndex` is the part of `pycocotools.coco.COCO` (nvidia/cocoapi master, un-pinned and absent from this
 image) that the reference touches: `dataset`, `imgs`, `getCatIds`, `getAnnIds`, `loadAnns`, `loadImgs`,
 `loadRes`.
 """
+import functools
 import json
 import math
 import os
@@ -123,6 +128,158 @@ def _batch_buffer(shape):
     return proto.new(storage).resize_(*shape)
 
 
+# -- Pillow's 8-bit bilinear resampling, restated -----------------------------------------------------------------------------------
+# `Image.resize(size, Image.BILINEAR)` on an 8-bit image is fixed-point integer arithmetic over weights computed in double.  The
+# weights below are what the device path ships (include/odtk_hip.h: odtk_preprocess_images); applied with numpy they are the CPU
+# implementation of the same pipeline.
+
+RESAMPLE_BITS = 22                                                  # Pillow's PRECISION_BITS = 32 - 8 - 2
+
+
+@functools.lru_cache(maxsize=512)
+def resample_weights(in_size, out_size):
+    """One axis of `Image.resize(.., Image.BILINEAR)`, `in_size` -> `out_size` pixels (default box, no reducing_gap):
+    (bounds int32 [out_size, 2] = first source index and number of taps per output index, weights int32 [out_size, taps] in units
+    of 2^-22, zero beyond a row's taps).  Every step in IEEE double and in Pillow's operation order: the triangle filter is
+    stretched by max(in / out, 1), evaluated at `(i + first - center + 0.5) * (1 / stretch)` (a product with the reciprocal, not
+    a quotient), the weights are normalised by their sum taken in index order and rounded to fixed point half away from zero."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError('resample_weights: sizes must be positive, got %d -> %d' % (in_size, out_size))
+    scale = in_size / out_size
+    stretch = max(scale, 1.0)
+    support = 1.0 * stretch                                         # the triangle filter's own support is 1
+    taps = int(math.ceil(support)) * 2 + 1
+    inverse = 1.0 / stretch
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    first = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    count = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - first
+    tap = np.arange(taps, dtype=np.int64)[None, :]
+    t = np.abs(((tap + first[:, None]) - center[:, None] + 0.5) * inverse)
+    w = np.where(t < 1.0, 1.0 - t, 0.0)
+    w[tap >= count[:, None]] = 0.0
+    total = np.zeros(out_size, dtype=np.float64)
+    for i in range(taps):                                           # in index order, from 0.0 (x + 0.0 == x: the masked taps add nothing)
+        total = total + w[:, i]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        w = np.where(total[:, None] != 0.0, w / total[:, None], w)
+    weights = np.trunc(w * float(1 << RESAMPLE_BITS) + np.where(w < 0.0, -0.5, 0.5)).astype(np.int32)
+    bounds = np.stack([first, count], axis=1).astype(np.int32)
+    bounds.setflags(write=False)
+    weights.setflags(write=False)
+    return bounds, weights
+
+
+def _resample_pass(pixels, bounds, weights, axis):
+    """One pass along `axis` (0: vertical, 1: horizontal) of uint8 `[h, w, c]`: clamp((2^21 + sum src * weight) >> 22) per channel."""
+    pixels = np.moveaxis(pixels, axis, 0).astype(np.int32)
+    first, last = bounds[:, 0].astype(np.int64), pixels.shape[0] - 1
+    acc = np.full((bounds.shape[0],) + pixels.shape[1:], 1 << (RESAMPLE_BITS - 1), dtype=np.int32)
+    for i in range(weights.shape[1]):                               # weights beyond a row's taps are zero: the clamped index adds nothing
+        acc += pixels[np.minimum(first + i, last)] * weights[:, i].reshape((-1,) + (1,) * (pixels.ndim - 1))
+    return np.moveaxis(np.clip(acc >> RESAMPLE_BITS, 0, 255).astype(np.uint8), 0, axis)
+
+
+def resize_bilinear(pixels, size):
+    """`np.array(Image.fromarray(pixels).resize(size, Image.BILINEAR))` for uint8 `[h, w, c]`, `size = (width, height)`, without
+    Pillow: the horizontal pass first, rounded to bytes, then the vertical pass on those bytes; a pass that would not change
+    the length is skipped."""
+    pixels = np.asarray(pixels)
+    width, height = int(size[0]), int(size[1])
+    if pixels.shape[1] != width:
+        pixels = _resample_pass(pixels, *resample_weights(pixels.shape[1], width), axis=1)
+    if pixels.shape[0] != height:
+        pixels = _resample_pass(pixels, *resample_weights(pixels.shape[0], height), axis=0)
+    return np.ascontiguousarray(pixels)
+
+
+# -- a batch of source images in one buffer -----------------------------------------------------------------------------------------
+IMAGE_DTYPE = np.dtype([('src_offset', '<u8'), ('src_width', '<i4'), ('src_height', '<i4'), ('src_pitch', '<i4'),
+                        ('out_width', '<i4'), ('out_height', '<i4'), ('mirror', '<i4'), ('x_table', '<i4'), ('y_table', '<i4'),
+                        ('x_taps', '<i4'), ('y_taps', '<i4')])      # odtk_image_t (include/odtk_hip.h)
+_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, 0, 0, 0
+_up16 = lambda n: (n + 15) // 16 * 16
+
+
+class SourceBatch:
+    """What a worker hands over with `device_resize=True`: ONE uint8 buffer per batch =
+        header (8 int32) | odtk_image_t per image | the resampling tables of the batch (int32) | source pixels, 3 bytes each
+    so that the source-size pixels, not the resized ones, cross shared memory and PCIe, in one upload.  `pack` writes it (inside
+    a loader worker, straight into shared memory), `descriptors` / `tables` read it back, `apply_cpu` is the pipeline in numpy and
+    torch: resize, mirror, pad, normalise -- the CPU implementation of `odtk_preprocess_images`."""
+
+    @staticmethod
+    def pack(sources, geometry, stride):
+        """sources: uint8 `[h, w, 3]` tensors; geometry: `(out_width, out_height, mirror)` per image."""
+        up = lambda d: d + (stride - d % stride) % stride
+        height = max(up(g[1]) for g in geometry)
+        width = max(up(g[0]) for g in geometry)
+        tables, where, length = [], {}, 0
+        def table(in_size, out_size):
+            nonlocal length
+            if in_size == out_size:
+                return -1, 0
+            if (in_size, out_size) not in where:
+                bounds, weights = resample_weights(in_size, out_size)
+                where[(in_size, out_size)] = (length, weights.shape[1])
+                tables.extend((bounds.reshape(-1), weights.reshape(-1)))
+                length += bounds.size + weights.size
+            return where[(in_size, out_size)]
+        images = np.zeros(len(sources), dtype=IMAGE_DTYPE)
+        for im, p, (ow, oh, mirror) in zip(images, sources, geometry):
+            h, w = p.shape[:2]
+            im['src_width'], im['src_height'], im['src_pitch'] = w, h, 3 * w
+            im['out_width'], im['out_height'], im['mirror'] = ow, oh, int(bool(mirror))
+            im['x_table'], im['x_taps'] = table(w, ow)
+            im['y_table'], im['y_taps'] = table(h, oh)
+        tables_at = _up16(4 * _HEADER_WORDS + images.nbytes)
+        at = _up16(tables_at + 4 * length)
+        for im in images:
+            im['src_offset'] = at
+            at = _up16(at + int(im['src_pitch']) * int(im['src_height']))
+        buffer = _batch_buffer((at,))
+        view = buffer.numpy()
+        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, 0, 0, 0)
+        view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + images.nbytes] = images.view(np.uint8)
+        if tables:
+            view[tables_at:tables_at + 4 * length].view(np.int32)[:] = np.concatenate(tables)
+        for im, p in zip(images, sources):
+            start = int(im['src_offset'])
+            view[start:start + p.numel()] = p.numpy().reshape(-1)
+        return buffer
+
+    def __init__(self, buffer):
+        """buffer: the packed uint8 tensor, in HOST memory (the descriptors are kernel arguments)."""
+        self.buffer = buffer
+        self.view = buffer.numpy()
+        header = self.view[:4 * _HEADER_WORDS].view(np.int32)
+        self.batch, self.height, self.width, self.tables_at, self.tables_len = (int(v) for v in header[:5])
+        self.images = self.view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + self.batch * IMAGE_DTYPE.itemsize].view(IMAGE_DTYPE)
+
+    def tables(self, buffer=None):
+        """The int32 tables as a view of `buffer` (default: the host copy; pass the uploaded one for the device's view)."""
+        buffer = self.buffer if buffer is None else buffer
+        return buffer[self.tables_at:self.tables_at + 4 * self.tables_len].view(torch.int32)
+
+    def source(self, k):
+        im = self.images[k]
+        start, h, w = int(im['src_offset']), int(im['src_height']), int(im['src_width'])
+        return self.view[start:start + 3 * w * h].reshape(h, w, 3)
+
+    def apply_cpu(self, table, dtype=torch.float32):
+        """-> `[B, 3, H, W]` `dtype`, channels_last storage: what `odtk_preprocess_images` writes, computed on the host."""
+        table = table.to(device='cpu', dtype=dtype).reshape(-1)
+        out = torch.zeros((self.batch, self.height, self.width, 3), dtype=dtype)
+        channel = torch.tensor([0, 256, 512])
+        for k, im in enumerate(self.images):
+            pixels = resize_bilinear(self.source(k), (int(im['out_width']), int(im['out_height'])))
+            if im['mirror']:
+                pixels = pixels[:, ::-1].copy()
+            out[k, :pixels.shape[0], :pixels.shape[1]] = table[torch.from_numpy(pixels).long() + channel]
+        return out.permute(0, 3, 1, 2)
+
+
+
 def _adjust_hue(im, factor):
     """Shift the hue channel by `factor` turns (|factor| <= 0.5), wrapping: what torchvision's PIL
     `adjust_hue` does (the reference calls it, data.py:101-105; torchvision is absent here)."""
@@ -145,8 +302,17 @@ class CocoDataset(data.dataset.Dataset):
     box_fields = 4
 
     def __init__(self, path, resize, max_size, stride, annotations=None, training=False, rotate_augment=False,
-                 augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0):
+                 augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, device_resize=False):
         super().__init__()
+        if device_resize:
+            # quarter turns and the colour augmentations act on the RESIZED PIL image in the reference: they stay on the host path
+            for name, value in (('rotate_augment', rotate_augment), ('augment_brightness', augment_brightness),
+                                ('augment_contrast', augment_contrast), ('augment_hue', augment_hue),
+                                ('augment_saturation', augment_saturation)):
+                if value:
+                    raise ValueError('device_resize=True cannot be combined with %s=%r: that augmentation works on the resized '
+                                     'image on the host (use the default loader)' % (name, value))
+        self.device_resize = device_resize
         self.path = os.path.expanduser(path)
         self.resize, self.max_size, self.stride = resize, max_size, stride
         self.mean, self.std = list(MEAN), list(STD)
@@ -163,7 +329,8 @@ class CocoDataset(data.dataset.Dataset):
         return len(self.ids)
 
     # -- geometry ---------------------------------------------------------------------------------------
-    def _open_resized(self, image_id):
+    def _open(self, image_id):
+        """-> the decoded image, the resize ratio (with its jitter draw) and the size the ratio asks for."""
         name = self.coco.loadImgs(image_id)[0]['file_name']
         im = Image.open(os.path.join(self.path, name)).convert('RGB')
         resize = self.resize
@@ -172,7 +339,11 @@ class CocoDataset(data.dataset.Dataset):
         ratio = resize / min(im.size)
         if ratio * max(im.size) > self.max_size:
             ratio = self.max_size / max(im.size)
-        return im.resize(tuple(int(ratio * d) for d in im.size), Image.BILINEAR), ratio
+        return im, ratio, tuple(int(ratio * d) for d in im.size)
+
+    def _open_resized(self, image_id):
+        im, ratio, size = self._open(image_id)
+        return im.resize(size, Image.BILINEAR), ratio
 
     def _quarter_turn(self, im, boxes, angle):
         """Rotate the image by `angle` in {90, 180, 270} on its own canvas and move the boxes with it
@@ -195,8 +366,11 @@ class CocoDataset(data.dataset.Dataset):
 
     def _flip(self, im, boxes):
         im = im.transpose(Image.FLIP_LEFT_RIGHT)
-        boxes[:, 0] = im.size[0] - boxes[:, 0] - boxes[:, 2]
-        return im, boxes
+        return im, self._flip_boxes(boxes, im.size[0])
+
+    def _flip_boxes(self, boxes, width):
+        boxes[:, 0] = width - boxes[:, 0] - boxes[:, 2]
+        return boxes
 
     def _colour(self, im):
         if self.augment_brightness:
@@ -210,8 +384,26 @@ class CocoDataset(data.dataset.Dataset):
         return im
 
     # -- items --------------------------------------------------------------------------------------------
+    def _source_item(self, image_id):
+        """The item of `device_resize=True`: `(source pixels uint8 [h, w, 3], (out_width, out_height, mirror), ...)` -- the same
+        draws from `random` in the same order as the host path (jitter, quarter turn, flip), the targets scaled and flipped as
+        there; the image itself is resized and mirrored on the device."""
+        im, ratio, size = self._open(image_id)
+        pixels = torch.from_numpy(np.array(im, dtype=np.uint8))
+        if not self.training:
+            return pixels, size + (0,), image_id, ratio
+        boxes, categories = self._get_target(image_id)
+        boxes[:, :4] *= ratio
+        random.randint(0, 3)                                            # the quarter turn's draw (rotate_augment is off here)
+        mirror = random.randint(0, 1)
+        if mirror:
+            boxes = self._flip_boxes(boxes, size[0])
+        return pixels, size + (mirror,), torch.cat([boxes, categories], dim=1)
+
     def __getitem__(self, index):
         image_id = self.ids[index]
+        if self.device_resize:
+            return self._source_item(image_id)
         im, ratio = self._open_resized(image_id)
         target = None
         if self.training:
@@ -257,16 +449,20 @@ class CocoDataset(data.dataset.Dataset):
         (reference data.py:119-121, 166-176)."""
         pixels = [item[0] for item in batch]
         stride = self.stride
-        up = lambda d: d + (stride - d % stride) % stride
-        height = max(up(p.shape[0]) for p in pixels)
-        width = max(up(p.shape[1]) for p in pixels)
-        packed = _batch_buffer((len(pixels), height, width, 4))
-        view = packed.numpy()
-        for k, p in enumerate(pixels):
-            h, w = p.shape[:2]
-            view[k, :h, :w] = p.numpy()                                     # rows of 4 * w contiguous bytes
-            view[k, :h, w:] = 0                                             # only the padding is cleared
-            view[k, h:] = 0
+        if self.device_resize:                                              # -> (SourceBatch buffer uint8 [bytes], ...) instead of packed
+            packed = SourceBatch.pack(pixels, [item[1] for item in batch], stride)
+            batch = [item[:1] + item[2:] for item in batch]
+        else:
+            up = lambda d: d + (stride - d % stride) % stride
+            height = max(up(p.shape[0]) for p in pixels)
+            width = max(up(p.shape[1]) for p in pixels)
+            packed = _batch_buffer((len(pixels), height, width, 4))
+            view = packed.numpy()
+            for k, p in enumerate(pixels):
+                h, w = p.shape[:2]
+                view[k, :h, :w] = p.numpy()                                 # rows of 4 * w contiguous bytes
+                view[k, :h, w:] = 0                                         # only the padding is cleared
+                view[k, h:] = 0
         if self.training:
             targets = [item[1] for item in batch]
             rows = max(t.shape[0] for t in targets)
@@ -315,10 +511,10 @@ class RotatedCocoDataset(CocoDataset):
         boxes[:, 4] = t
         return im, boxes
 
-    def _flip(self, im, boxes):
-        im, boxes = super()._flip(im, boxes)
+    def _flip_boxes(self, boxes, width):
+        boxes = super()._flip_boxes(boxes, width)
         boxes[:, 4] = -boxes[:, 4]
-        return im, boxes
+        return boxes
 
 
 class DataIterator:
@@ -331,8 +527,12 @@ class DataIterator:
 
     def __init__(self, path, resize, max_size, batch_size, stride, world, annotations, training=False,
                  rotate_augment=False, augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0,
-                 augment_saturation=0.0, device=None, dtype=torch.float32, num_workers=2, rank=None, **dataset_args):
+                 augment_saturation=0.0, device=None, dtype=torch.float32, num_workers=2, rank=None, device_resize=False,
+                 **dataset_args):
         self.resize, self.max_size = resize, max_size
+        self.device_resize = device_resize
+        if device_resize:
+            dataset_args = dict(dataset_args, device_resize=True)
         self.dataset = self.dataset_class(path, resize=resize, max_size=max_size, stride=stride,
                                           annotations=annotations, training=training, rotate_augment=rotate_augment,
                                           augment_brightness=augment_brightness, augment_contrast=augment_contrast,
@@ -357,14 +557,31 @@ class DataIterator:
                                           persistent_workers=bool(training and num_workers > 0))
 
     def __repr__(self):
-        return '\n'.join(['    loader: pytorch', '    resize: {}, max: {}'.format(self.resize, self.max_size)])
+        lines = ['    loader: pytorch', '    resize: {}, max: {}'.format(self.resize, self.max_size)]
+        if self.device_resize:
+            lines.append('    resize on: {}'.format('the device (odtk_preprocess_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
+        return '\n'.join(lines)
 
     def __len__(self):
         return len(self.dataloader)
 
+    def _preprocess(self, packed):
+        """`device_resize=True`: the batch from a `SourceBatch` buffer -- one upload and one HIP launch on a GPU (the descriptors
+        are read from the host copy: they are kernel arguments), the same arithmetic in numpy on the CPU."""
+        batch = SourceBatch(packed)
+        if self.device.type != 'cuda':
+            return batch.apply_cpu(self.table, self.dtype)
+        from . import _C
+        uploaded = packed.to(self.device, non_blocking=True)
+        images = (_C.Image * batch.batch).from_buffer_copy(batch.images.tobytes())
+        return _C.preprocess_images(uploaded, images, batch.tables(uploaded), self.table, batch.height, batch.width)
+
     def __iter__(self):
         for packed, *rest in self.dataloader:
-            images = normalise_batch(packed.to(self.device, non_blocking=True), self.table, self.dtype)
+            if self.device_resize:
+                images = self._preprocess(packed)
+            else:
+                images = normalise_batch(packed.to(self.device, non_blocking=True), self.table, self.dtype)
             yield (images, *(t.to(self.device, non_blocking=True) for t in rest))
 
 

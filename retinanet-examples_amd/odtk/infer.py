@@ -136,7 +136,7 @@ def infer_batches(model, batches, rotated_bbox=False, category_ids=None, detecti
 
 def infer(model, path, detections_file, resize, max_size, batch_size, mixed_precision=True, is_master=True, world=0,
           annotations=None, with_apex=False, use_dali=False, is_validation=False, verbose=True, rotated_bbox=False,
-          num_workers=2):
+          num_workers=2, device_resize=False):
     """Run inference on the images under `path` -- the reference's `infer.infer` (infer.py:18-177), same
     arguments.  Returns `COCOeval.stats` (mAP first) when ground truth was given, None when nothing was
     detected, 0 otherwise (and on the ranks other than the master), as the reference does.
@@ -144,7 +144,8 @@ def infer(model, path, detections_file, resize, max_size, batch_size, mixed_prec
     `mixed_precision` on a GPU = fp16 autocast, like the reference's (apex O2 / torch.cuda.amp, infer.py:54-58), which
     routes `Model.forward` to the fp16 BN-folded engine (measured AP against the fp32 pipeline: 0.995-1.000, the bf16
     engine 0.963-0.988; profiles/r04_bf16_ablation.txt).  `with_apex` / `use_dali` name dependencies the north star
-    drops: asking for them is an error, not a silent fallback."""
+    drops: asking for them is an error, not a silent fallback.  `device_resize`: the loader hands over source-size pixels and
+    the resize runs on the device with the rest of the input pipeline (odtk/data.py), bit-identical to the default."""
     from .cocoeval import COCOeval
     from .data import DataIterator, RotatedDataIterator
     from .utils import Profiler
@@ -164,7 +165,7 @@ def infer(model, path, detections_file, resize, max_size, batch_size, mixed_prec
     else:
         device = torch.device('cuda', torch.cuda.current_device())
     data_iterator = iterator_class(path, resize, max_size, batch_size, net.stride, max(world, 1), annotations,
-                                   training=False, device=device, num_workers=num_workers)
+                                   training=False, device=device, num_workers=num_workers, device_resize=device_resize)
     if verbose:
         print(data_iterator)
     if not is_validation and device.type == 'cuda':

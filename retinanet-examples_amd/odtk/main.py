@@ -11,6 +11,8 @@ What differs from the reference, and why:
     weights.
   * `--with-apex` / `--with-dali` and TensorRT engines (`.plan` / `.engine`, `export` to anything) name
     dependencies the north star drops; they are accepted by the parser and refused with a clear error.
+  * `--device-resize` (train, infer) is new: what DALI did for the reference -- resize, flip, pad, normalise on the GPU -- as one
+    HIP launch per batch (odtk/data.py), bit-identical to the default loader.
 """
 import argparse
 import os
@@ -30,6 +32,8 @@ def _flag(name, kind=None, default=None, text='', **extra):
     spec = dict(extra, help=text)
     if kind is bool:
         spec['action'] = 'store_true'
+        if default is not None:                                         # argparse.SUPPRESS: no attribute unless the switch is given
+            spec['default'] = default
     else:
         spec.update(type=kind, default=default)
     return name, spec
@@ -40,7 +44,10 @@ _SIZES = [_flag('--batch', int, None, 'images per step over all GPUs (default: 2
           _flag('--resize', int, 800, 'short side after resizing', metavar='scale'),
           _flag('--max-size', int, 1333, 'cap on the long side after resizing', metavar='max')]
 _COMMON = [_flag('--with-apex', bool, text=_DROPPED), _flag('--with-dali', bool, text=_DROPPED),
-           _flag('--workers', int, 8, 'loader processes per GPU (the reference hard-codes 2; ~6 feed one MI355X)', metavar='num')]
+           _flag('--workers', int, 8, 'loader processes per GPU (the reference hard-codes 2; ~6 feed one MI355X)', metavar='num'),
+           # not a flag of the reference: absent from the namespace unless given (read with getattr)
+           _flag('--device-resize', bool, text='resize, flip, pad and normalise the images on the device, bit-identical to the '
+                 'host loader (train: not with --augment-rotate or non-zero colour augmentations)', default=argparse.SUPPRESS)]
 
 # same names, types and defaults as the reference's parser (main.py:15-118)
 TRAIN_FLAGS = [
@@ -180,12 +187,13 @@ def worker(rank, args, world, spawned=False):
                                augment_contrast=args.augment_contrast, augment_hue=args.augment_hue,
                                augment_saturation=args.augment_saturation, regularization_l2=args.regularization_l2,
                                rotated_bbox=args.rotated_bbox, absolute_angle=args.absolute_angle,
-                               num_workers=args.workers)
+                               num_workers=args.workers, device_resize=getattr(args, 'device_resize', False))
         if args.command == 'infer':
             return infer.infer(model, args.images, args.output, args.resize, args.max_size, args.batch,
                                annotations=args.annotations, mixed_precision=not args.full_precision,
                                is_master=(rank == 0), world=world, with_apex=args.with_apex, use_dali=args.with_dali,
-                               verbose=(rank == 0), rotated_bbox=args.rotated_bbox, num_workers=args.workers)
+                               verbose=(rank == 0), rotated_bbox=args.rotated_bbox, num_workers=args.workers,
+                               device_resize=getattr(args, 'device_resize', False))
         return model.export(args.size, args.dynamic_batch_opts)     # raises: TensorRT is dropped
     finally:
         if torch.distributed.is_available() and torch.distributed.is_initialized():

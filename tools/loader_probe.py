@@ -1,6 +1,14 @@
 #!/usr/bin/env python
 """Where the time of the file-based loader goes (odtk/data.py): first-batch latency (worker start-up) vs steady rate,
-for several worker counts, on N synthetic 1280x800 JPEGs; plus the per-stage cost in the main process."""
+for several worker counts, on N synthetic JPEGs; plus the per-stage cost in the main process -- for the host path (workers resize
+with Pillow and ship the resized RGBA pixels) and for device_resize=True (workers ship the source pixels, one HIP launch resizes,
+pads and normalises).
+
+  PROBE_IMAGES=192  PROBE_REPEAT=1  PROBE_WORKERS=0,4,16,32  PROBE_SIZE=1280x800  PROBE_MODES=host,device
+PROBE_REPEAT lists every file that many times (a longer pass without writing more files): the steady rate is taken over the SECOND
+HALF of the pass, which must be well beyond what the workers prefetch (2 batches each) while the main process waits for the first
+batch.  PROBE_SIZE is the size of the JPEGs.  At the default, resize=800 / max_size=1333 asks for the size the images already have and
+Pillow returns a copy: the resize is NOT in the host path's figures.  PROBE_SIZE=640x480 (COCO's usual size, -> 1066x800) makes it real."""
 import json
 import os
 import sys
@@ -16,42 +24,52 @@ from PIL import Image
 from odtk.data import CocoDataset, DataIterator, normalise_batch
 
 N = int(os.environ.get('PROBE_IMAGES', 192))
+REPEAT = int(os.environ.get('PROBE_REPEAT', 1))
+WIDTH, HEIGHT = (int(v) for v in os.environ.get('PROBE_SIZE', '1280x800').split('x'))
+MODES = os.environ.get('PROBE_MODES', 'host,device').split(',')
 scratch = tempfile.mkdtemp(prefix='odtk_probe_')
-yy, xx = np.mgrid[0:800, 0:1280]
+yy, xx = np.mgrid[0:HEIGHT, 0:WIDTH]
 images = []
 for k in range(N):
     base = np.stack([(xx + 3 * k) % 256, (yy * 2 + k) % 256, ((xx + yy) // 2) % 256], 2).astype(np.uint8)
     Image.fromarray(base, 'RGB').save(os.path.join(scratch, 'im%04d.jpg' % k), quality=90)
-    images.append({'id': k, 'file_name': 'im%04d.jpg' % k, 'width': 1280, 'height': 800})
+images = [{'id': r * N + k, 'file_name': 'im%04d.jpg' % k, 'width': WIDTH, 'height': HEIGHT} for r in range(REPEAT) for k in range(N)]
 ann = os.path.join(scratch, 'ann.json')
 json.dump({'images': images}, open(ann, 'w'))
 cuda = torch.cuda.is_available()
 sync = torch.cuda.synchronize if cuda else (lambda: None)
 if cuda:
     torch.zeros(1, device='cuda')
-print('host cores', os.cpu_count(), 'images', N)
+print('host cores', os.cpu_count(), 'images', N * REPEAT, '(%d files)' % N, 'of %dx%d' % (WIDTH, HEIGHT), 'resize 800 max 1333 stride 128, batches of 8')
 
-ds = CocoDataset(scratch, 800, 1333, 128, ann)
-t = time.time(); items = [ds[i] for i in range(16)]; per_item = (time.time() - t) / 16
-t = time.time(); packed = [ds.collate_fn(items[:8]) for _ in range(4)][0][0]; per_collate = (time.time() - t) / 4
-dev = packed.cuda() if cuda else packed
-sync(); t = time.time()
-for _ in range(10):
-    out = normalise_batch(packed.cuda() if cuda else packed)
-sync(); per_norm = (time.time() - t) / 10
-print('main process: item (decode + resize + to uint8) %.1f ms, collate of 8 %.1f ms, upload + normalise of 8 %.2f ms'
-      % (per_item * 1e3, per_collate * 1e3, per_norm * 1e3))
+for mode in MODES:
+    device_resize = mode == 'device'
+    print('--- %s' % ('device_resize=True: workers ship source pixels' if device_resize else 'host path: workers resize with Pillow'))
+    ds = CocoDataset(scratch, 800, 1333, 128, ann, device_resize=device_resize)
+    t = time.time(); items = [ds[i] for i in range(16)]; per_item = (time.time() - t) / 16
+    t = time.time(); packed = [ds.collate_fn(items[:8]) for _ in range(4)][0][0]; per_collate = (time.time() - t) / 4
+    it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, training=False, num_workers=0, device_resize=device_resize)
+    pinned = packed.pin_memory() if cuda else packed
+    stage = (lambda: it._preprocess(pinned)) if device_resize else (lambda: normalise_batch(pinned.to(it.device, non_blocking=True), it.table))
+    out = stage()
+    sync(); t = time.time()
+    for _ in range(10):
+        out = stage()
+    sync(); per_stage = (time.time() - t) / 10
+    print('main process: item (decode%s + to uint8) %.1f ms, collate of 8 %.1f ms, upload (pinned) + device stage of 8 %.2f ms -> %s'
+          % ('' if device_resize else ' + resize', per_item * 1e3, per_collate * 1e3, per_stage * 1e3, tuple(out.shape)))
+    print('bytes per batch of 8 through shared memory and PCIe: %d (%.2f MB)' % (packed.numel(), packed.numel() / 1e6))
 
-for workers in [int(w) for w in os.environ.get('PROBE_WORKERS', '0,4,16,32').split(',')]:
-    it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, training=False, num_workers=workers)
-    t0 = time.time()
-    first, n = None, 0
-    for data, ids, ratios in it:
-        n += data.shape[0]
-        if first is None:
-            sync()
-            first = time.time() - t0
-    sync()
-    total = time.time() - t0
-    print('%2d workers: first batch after %.2f s, then %.1f img/s; whole pass %.1f img/s'
-          % (workers, first, (n - 8) / max(total - first, 1e-9), n / total))
+    for workers in [int(w) for w in os.environ.get('PROBE_WORKERS', '0,4,16,32').split(',')]:
+        it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, training=False, num_workers=workers, device_resize=device_resize)
+        t0 = time.time()
+        stamps = []
+        for data, ids, ratios in it:
+            if not stamps:
+                sync()
+            stamps.append(time.time() - t0)
+        sync()
+        total = time.time() - t0
+        half = len(stamps) // 2
+        print('%2d workers: first batch after %.2f s; second half of the pass %.1f img/s; whole pass %.1f img/s'
+              % (workers, stamps[0], 8 * (len(stamps) - half) / max(total - stamps[half - 1], 1e-9), 8 * len(stamps) / total))
