@@ -43,6 +43,8 @@ int odtk_conv_bias_act_pads(void *y, const void *x, const void *w, const void *b
                             int c_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int pad_h_end,
                             int pad_w_end, int dtype, int relu, void *stream);
 
+/* (Views of larger channels_last buffers, element strides per tensor: include/odtk_conv_strided.h.) */
+
 /* "#index time-when-chosen instance-name" of the instance the last odtk_conv_bias_act call of this thread ran. */
 const char *odtk_conv_last_plan(void);
 

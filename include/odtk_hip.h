@@ -243,6 +243,22 @@ int odtk_upsample_nearest2x(const void *x, void *out, int batch_size, int height
                             void *stream);
 
 /*
+ * Pyramid canvas (odtk/fused.py: the head towers of the small pyramid levels as ONE convolution).  The levels lie side by side in
+ * one channels_last tensor [batch, height, width, channels] of `dtype`, each in a rectangle (y0, x0, rect_height, rect_width) --
+ * `rects`: HOST int[4 * n_rects], n_rects <= ODTK_MAX_LEVELS, every rectangle inside the canvas -- with zero pixels between them:
+ * the gutters are the zero padding of every level's convolution.  canvas 16-byte aligned, channels * sizeof(dtype) a multiple of 16.
+ *   odtk_canvas_clear  zeroes every pixel outside the rectangles (a convolution over the canvas writes act(bias + ...) there;
+ *                      the next layer must read zeros again); pixels inside are not touched.
+ *   odtk_canvas_pack   writes the whole canvas: rectangle i from `sources[i]` (HOST array of DEVICE pointers to packed
+ *                      [batch, rect_height, rect_width, channels] tensors, 16-byte aligned), zeros elsewhere.
+ * One launch each; plain streams of 16-byte vectors (bytes are copied, never decoded: any storage type).
+ */
+int odtk_canvas_clear(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects, int n_rects,
+                      void *stream);
+int odtk_canvas_pack(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects,
+                     const void *const *sources, int n_rects, void *stream);
+
+/*
  * odtk_stem_pack -- 2x2 space-to-depth pack of the network input for the ResNet stem, with the cast to the engine's dtype:
  *     out[n][y][x][(dy * 2 + dx) * 3 + c] = x[n][c][2 y + dy][2 x + dx]   for the 12 real channels, channels 12..15 = 0
  * x: device [batch, 3, height, width] of in_dtype (ODTK_F32 / BF16 / F16), NCHW-contiguous (channels_last = 0) or NHWC-contiguous

@@ -22,7 +22,9 @@
 
 #include <array>
 #include <cfloat>
+#include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -36,7 +38,7 @@
 #include "ck/tensor_operation/gpu/device/tensor_layout.hpp"
 #include "ck/tensor_operation/gpu/element/element_wise_operation.hpp"
 
-#include "../../include/odtk_conv.h"
+#include "../../include/odtk_conv_strided.h"
 #include "../../include/odtk_hip.h"
 
 namespace {
@@ -59,6 +61,14 @@ struct Problem {
   }
 };
 
+// Element strides of the activation views (image, row, pixel; the channel stride is 1).
+struct Strides {
+  index_t xn, xh, xw, yn, yh, yw;
+  bool operator<(const Strides &o) const {
+    return std::tie(xn, xh, xw, yn, yh, yw) < std::tie(o.xn, o.xh, o.xw, o.yn, o.yh, o.yw);
+  }
+};
+
 struct Plan {
   int index = -1;          // instance of the list; -1: none supports the problem
   float us = 0.0f;         // its time when it was chosen (0: chosen without timing, under a stream capture)
@@ -73,6 +83,7 @@ template <typename T>
 struct Instances {
   std::vector<std::unique_ptr<ConvOp<T>>> ops;
   std::map<Problem, Plan> plans;
+  std::map<std::tuple<Problem, Strides, int>, bool> views;   // (problem, strides of a view, instance) -> the instance takes that argument
   Instances() { ops = ck::tensor_operation::device::instance::DeviceOperationInstanceFactory<ConvOp<T>>::GetInstances(); }
 };
 
@@ -83,14 +94,14 @@ Instances<T> &instances() {
 }
 
 template <typename T>
-std::unique_ptr<ck::tensor_operation::device::BaseArgument> make_argument(ConvOp<T> &op, const Problem &p, void *y, const void *x,
-                                                                          const void *w, const void *bias, int relu) {
+std::unique_ptr<ck::tensor_operation::device::BaseArgument> make_argument(ConvOp<T> &op, const Problem &p, const Strides &st, void *y,
+                                                                          const void *x, const void *w, const void *bias, int relu) {
   const index_t G = 1, N = p.n, C = p.c, K = p.k, Hi = p.h, Wi = p.w, Y = p.r, X = p.s;
   const index_t Ho = (Hi + p.ph + p.ph1 - Y) / p.u + 1, Wo = (Wi + p.pw + p.pw1 - X) / p.v + 1;
   // lengths in the order CK wants them (G, N, C | K, spatial...), strides of the NHWGC / GKYXC / NHWGK memory layouts
-  const std::array<index_t, 5> a_len{G, N, C, Hi, Wi}, a_str{C, Hi * Wi * G * C, 1, Wi * G * C, G * C};
+  const std::array<index_t, 5> a_len{G, N, C, Hi, Wi}, a_str{C, st.xn, 1, st.xh, st.xw};
   const std::array<index_t, 5> b_len{G, K, C, Y, X}, b_str{K * Y * X * C, Y * X * C, 1, X * C, C};
-  const std::array<index_t, 5> e_len{G, N, K, Ho, Wo}, e_str{K, Ho * Wo * G * K, 1, Wo * G * K, G * K};
+  const std::array<index_t, 5> e_len{G, N, K, Ho, Wo}, e_str{K, st.yn, 1, st.yh, st.yw};
   const std::array<index_t, 5> d_str{K, 0, 1, 0, 0};                           // the bias: one value per output channel
   const std::array<index_t, 2> strides{p.u, p.v}, dilations{1, 1}, pads{p.ph, p.pw}, pads_end{p.ph1, p.pw1};
   return op.MakeArgumentPointer(x, w, std::array<const void *, 1>{bias}, y, a_len, a_str, b_len, b_str,
@@ -109,7 +120,8 @@ bool stream_is_capturing(hipStream_t stream) {
 // count is within a factor of two of this problem's (a batch of another size is tuned on its own) and its instance takes this
 // problem too.
 template <typename T>
-bool adopt_sibling(Instances<T> &inst, const Problem &p, void *y, const void *x, const void *w, const void *bias, int relu, Plan *out) {
+bool adopt_sibling(Instances<T> &inst, const Problem &p, const Strides &st, void *y, const void *x, const void *w, const void *bias, int relu,
+                   Plan *out) {
   const double pixels = static_cast<double>(p.n) * p.h * p.w;
   const Plan *best = nullptr;
   double best_ratio = 2.0;
@@ -125,7 +137,7 @@ bool adopt_sibling(Instances<T> &inst, const Problem &p, void *y, const void *x,
   }
   if (!best) return false;
   auto &op = *inst.ops[best->index];
-  auto arg = make_argument<T>(op, p, y, x, w, bias, relu);
+  auto arg = make_argument<T>(op, p, st, y, x, w, bias, relu);
   if (!op.IsSupportedArgument(arg.get()) || op.GetWorkSpaceSize(arg.get()) != 0) return false;
   *out = *best;
   out->us = 0.0f;                                           // (not measured on this problem)
@@ -133,7 +145,8 @@ bool adopt_sibling(Instances<T> &inst, const Problem &p, void *y, const void *x,
 }
 
 template <typename T>
-int run(const Problem &p, void *y, const void *x, const void *w, const void *bias, int relu, hipStream_t stream, int force_index) {
+int run(const Problem &p, const Strides &st, void *y, const void *x, const void *w, const void *bias, int relu, hipStream_t stream,
+        int force_index) {
   std::lock_guard<std::mutex> lock(g_mutex);
   Instances<T> &inst = instances<T>();
   Plan plan;
@@ -143,13 +156,13 @@ int run(const Problem &p, void *y, const void *x, const void *w, const void *bia
   if (force_index >= 0) {
     plan = Plan{};
     if (force_index < static_cast<int>(inst.ops.size())) {
-      auto arg = make_argument<T>(*inst.ops[force_index], p, y, x, w, bias, relu);
+      auto arg = make_argument<T>(*inst.ops[force_index], p, st, y, x, w, bias, relu);
       if (inst.ops[force_index]->IsSupportedArgument(arg.get()) && inst.ops[force_index]->GetWorkSpaceSize(arg.get()) == 0)
         plan.index = force_index;
     }
     if (plan.index < 0) return ODTK_ERR_UNSUPPORTED;
     plan.name = inst.ops[plan.index]->GetTypeString();
-  } else if (it == inst.plans.end() && adopt_sibling<T>(inst, p, y, x, w, bias, relu, &plan)) {
+  } else if (it == inst.plans.end() && adopt_sibling<T>(inst, p, st, y, x, w, bias, relu, &plan)) {
     // a problem that differs from a planned one in its extents only (a data set's batches are padded to the largest image of
     // the batch: dozens of geometries) runs on that sibling's instance -- no second tuning pass of 237 candidates per layer
     inst.plans[p] = plan;
@@ -169,7 +182,7 @@ int run(const Problem &p, void *y, const void *x, const void *w, const void *bia
     for (size_t i = 0; i < inst.ops.size(); ++i) {
       try {                                                   // CK throws on arguments an instance cannot run: next candidate
         auto &op = *inst.ops[i];
-        auto arg = make_argument<T>(op, p, y, x, w, bias, relu);
+        auto arg = make_argument<T>(op, p, st, y, x, w, bias, relu);
         if (!op.IsSupportedArgument(arg.get()) || op.GetWorkSpaceSize(arg.get()) != 0) continue;
         if (capturing) { plan.index = static_cast<int>(i); break; }          // no timing inside a capture: the first that fits
         auto invoker = op.MakeInvokerPointer();
@@ -197,7 +210,14 @@ int run(const Problem &p, void *y, const void *x, const void *w, const void *bia
   }
   if (plan.index < 0) return ODTK_ERR_UNSUPPORTED;
   auto &op = *inst.ops[plan.index];
-  auto arg = make_argument<T>(op, p, y, x, w, bias, relu);
+  auto arg = make_argument<T>(op, p, st, y, x, w, bias, relu);
+  // the plan is keyed on extents: a view with other strides is put to the instance itself once per (problem, strides) pair
+  // before its first launch (vector widths, the 2 GB limit of the descriptors)
+  const auto view = std::make_tuple(p, st, plan.index);
+  auto seen = inst.views.find(view);
+  if (seen == inst.views.end())
+    seen = inst.views.emplace(view, op.IsSupportedArgument(arg.get()) && op.GetWorkSpaceSize(arg.get()) == 0).first;
+  if (!seen->second) return ODTK_ERR_UNSUPPORTED;
   op.MakeInvokerPointer()->Run(arg.get(), StreamConfig{stream, false});
   char buf[64];
   std::snprintf(buf, sizeof buf, "#%d %.1f us ", plan.index, plan.us);
@@ -236,19 +256,43 @@ bool import_plan(const Problem &p, int index, const std::string &name) {
 extern "C" {
 
 // declared in include/odtk_conv.h
-int odtk_conv_bias_act_pads(void *y, const void *x, const void *w, const void *bias, int batch_size, int c_in, int height, int width,
-                            int c_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int pad_h_end,
-                            int pad_w_end, int dtype, int relu, void *stream) {
+int odtk_conv_bias_act_strided(void *y, const void *x, const void *w, const void *bias, int batch_size, int c_in, int height, int width,
+                               int c_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int pad_h_end,
+                               int pad_w_end, long long x_image_stride, long long x_row_stride, long long x_pixel_stride,
+                               long long y_image_stride, long long y_row_stride, long long y_pixel_stride, int dtype, int relu,
+                               void *stream) {
   if (!y || !x || !w || !bias || batch_size <= 0 || c_in <= 0 || c_out <= 0 || height <= 0 || width <= 0 || kernel_h <= 0 ||
       kernel_w <= 0 || stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || pad_h_end < 0 || pad_w_end < 0)
     return ODTK_ERR_INVALID;
   if (height + pad_h + pad_h_end < kernel_h || width + pad_w + pad_w_end < kernel_w) return ODTK_ERR_INVALID;
   const Problem p{batch_size, c_in, height, width, c_out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, pad_h_end, pad_w_end, dtype};
+  const long long out_h = (height + pad_h + pad_h_end - kernel_h) / stride_h + 1, out_w = (width + pad_w + pad_w_end - kernel_w) / stride_w + 1;
+  // a view: pixels that do not overlap, rows that hold their pixels, images that hold their rows -- and every stride a multiple
+  // of 8 elements from a 16-byte aligned base, or the instances' 16-byte vector accesses are misaligned
+  const long long limit = 0x7fffffffll;
+  if (x_pixel_stride < c_in || x_row_stride < (width - 1) * x_pixel_stride + c_in || x_image_stride < (height - 1) * x_row_stride + (width - 1) * x_pixel_stride + c_in ||
+      y_pixel_stride < c_out || y_row_stride < (out_w - 1) * y_pixel_stride + c_out || y_image_stride < (out_h - 1) * y_row_stride + (out_w - 1) * y_pixel_stride + c_out ||
+      x_image_stride > limit || y_image_stride > limit)
+    return ODTK_ERR_INVALID;
+  const bool x_packed = x_pixel_stride == c_in && x_row_stride == width * x_pixel_stride && x_image_stride == height * x_row_stride;
+  const bool y_packed = y_pixel_stride == c_out && y_row_stride == out_w * y_pixel_stride && y_image_stride == out_h * y_row_stride;
+  // (a packed tensor is taken as before, whatever its channel count: the instances say themselves which they support)
+  if (!x_packed && (((x_pixel_stride | x_row_stride | x_image_stride) & 7) || (reinterpret_cast<uintptr_t>(x) & 15u))) return ODTK_ERR_INVALID;
+  if (!y_packed) {
+    if (((y_pixel_stride | y_row_stride | y_image_stride) & 7) || (reinterpret_cast<uintptr_t>(y) & 15u)) return ODTK_ERR_INVALID;
+    // The instances read x through a descriptor that carries all three strides, but they address y as ONE run of
+    // batch * out_h * out_w pixels at the pixel stride (transform_conv_fwd_to_gemm.hpp: MakeCDescriptor_M_N): an output whose
+    // rows or images are further apart than that -- a rectangle of a wider buffer -- would be written to the wrong pixels.
+    // IsSupportedArgument does not look at it, so it is refused here.  (A wider pixel stride -- a channel slice -- is honoured.)
+    if (y_row_stride != out_w * y_pixel_stride || y_image_stride != out_h * y_row_stride) return ODTK_ERR_UNSUPPORTED;
+  }
+  const Strides st{static_cast<index_t>(x_image_stride), static_cast<index_t>(x_row_stride), static_cast<index_t>(x_pixel_stride),
+                   static_cast<index_t>(y_image_stride), static_cast<index_t>(y_row_stride), static_cast<index_t>(y_pixel_stride)};
   int force = -1;
   if (const char *f = std::getenv("ODTK_CONV_INSTANCE")) force = std::atoi(f);   // A/B knob for measurements
   try {
-    if (dtype == ODTK_BF16) return run<ck::bhalf_t>(p, y, x, w, bias, relu, static_cast<hipStream_t>(stream), force);
-    if (dtype == ODTK_F16) return run<ck::half_t>(p, y, x, w, bias, relu, static_cast<hipStream_t>(stream), force);
+    if (dtype == ODTK_BF16) return run<ck::bhalf_t>(p, st, y, x, w, bias, relu, static_cast<hipStream_t>(stream), force);
+    if (dtype == ODTK_F16) return run<ck::half_t>(p, st, y, x, w, bias, relu, static_cast<hipStream_t>(stream), force);
   } catch (const std::exception &e) {                                            // CK throws on arguments it cannot run
     g_last_plan = std::string("exception: ") + e.what();
     return ODTK_ERR_UNSUPPORTED;
@@ -257,6 +301,18 @@ int odtk_conv_bias_act_pads(void *y, const void *x, const void *w, const void *b
     return ODTK_ERR_UNSUPPORTED;
   }
   return ODTK_ERR_UNSUPPORTED;
+}
+
+int odtk_conv_bias_act_pads(void *y, const void *x, const void *w, const void *bias, int batch_size, int c_in, int height, int width,
+                            int c_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int pad_h_end,
+                            int pad_w_end, int dtype, int relu, void *stream) {
+  if (c_in <= 0 || c_out <= 0 || height <= 0 || width <= 0 || kernel_h <= 0 || kernel_w <= 0 || stride_h <= 0 || stride_w <= 0 ||
+      pad_h < 0 || pad_w < 0 || pad_h_end < 0 || pad_w_end < 0 || height + pad_h + pad_h_end < kernel_h || width + pad_w + pad_w_end < kernel_w)
+    return ODTK_ERR_INVALID;
+  const long long out_h = (height + pad_h + pad_h_end - kernel_h) / stride_h + 1, out_w = (width + pad_w + pad_w_end - kernel_w) / stride_w + 1;
+  return odtk_conv_bias_act_strided(y, x, w, bias, batch_size, c_in, height, width, c_out, kernel_h, kernel_w, stride_h, stride_w, pad_h,
+                                    pad_w, pad_h_end, pad_w_end, 1ll * height * width * c_in, 1ll * width * c_in, c_in,
+                                    out_h * out_w * c_out, out_w * c_out, c_out, dtype, relu, stream);
 }
 
 int odtk_conv_bias_act(void *y, const void *x, const void *w, const void *bias, int batch_size, int c_in, int height, int width,

@@ -234,6 +234,37 @@ __global__ __launch_bounds__(256) void upsample_nearest2x_kernel(const vuint4 *_
   }
 }
 
+// ---- pyramid canvas ---------------------------------------------------------------------------------------------------------------
+// The small pyramid levels side by side in one channels_last tensor, zero pixels between them (include/odtk_hip.h:
+// odtk_canvas_clear / odtk_canvas_pack; odtk/fused.py: _towers).  One thread = one 16-byte vector of one canvas pixel, grid-stride:
+// a pixel inside rectangle l is copied from that level's packed tensor (pack) or left alone (clear: src[l] == nullptr), a pixel
+// outside every rectangle becomes zero.  HBM-bound; 25 MB written (+ 22 MB read) by the pack, 3 MB by the clear at the flagship shape.
+struct CanvasArgs {
+  uint32_t n;
+  uint32_t y0[ODTK_MAX_LEVELS], x0[ODTK_MAX_LEVELS], h[ODTK_MAX_LEVELS], w[ODTK_MAX_LEVELS];
+  const vuint4 *src[ODTK_MAX_LEVELS];
+};
+
+__global__ __launch_bounds__(256) void canvas_fill_kernel(vuint4 *__restrict__ canvas, const CanvasArgs a, uint32_t groups, uint32_t total,
+                                                          const FastDiv by_groups, const FastDiv by_w, const FastDiv by_h) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {   // total < 2^32 - grid (checked by the host)
+    uint32_t g, x, y;
+    uint32_t p = fastdivmod(i, by_groups, &g);
+    p = fastdivmod(p, by_w, &x);
+    const uint32_t b = fastdivmod(p, by_h, &y);
+    bool inside = false;
+#pragma unroll
+    for (uint32_t l = 0; l < ODTK_MAX_LEVELS; ++l) {
+      const uint32_t dy = y - a.y0[l], dx = x - a.x0[l];                  // (unsigned: a pixel before the origin wraps beyond h / w)
+      if (l < a.n && dy < a.h[l] && dx < a.w[l]) {
+        inside = true;
+        if (a.src[l]) canvas[i] = a.src[l][((static_cast<uint64_t>(b) * a.h[l] + dy) * a.w[l] + dx) * groups + g];
+      }
+    }
+    if (!inside) canvas[i] = vuint4{0u, 0u, 0u, 0u};
+  }
+}
+
 // ---- stem: space-to-depth pack of the network input ---------------------------------------------------------------------------
 // The ResNet stem is a 7x7 / stride-2 convolution over THREE input channels: as an implicit GEMM its reduction runs over
 // 3-element channel vectors (MIOpen's pick for it: 230 us at bs 8, a quarter of the matrix-core rate of the other layers, + a

@@ -1156,6 +1156,42 @@ int odtk_upsample_nearest2x(const void *x, void *out, int batch_size, int height
   return ODTK_OK;
 }
 
+int odtk_canvas_pack(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects,
+                     const void *const *sources, int n_rects, void *stream) {
+  if (!canvas || !rects || batch_size <= 0 || height <= 0 || width <= 0 || channels <= 0 || n_rects < 0 || n_rects > ODTK_MAX_LEVELS)
+    return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned long long row_bytes = 1ull * channels * (dtype == ODTK_F32 ? 4 : 2);
+  if (row_bytes % 16) return ODTK_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(canvas) & 15u) return ODTK_ERR_INVALID;
+  const unsigned long long groups = row_bytes / 16;
+  const unsigned long long total = 1ull * batch_size * height * width * groups;
+  if (total > 0xf0000000ull) return ODTK_ERR_INVALID;
+  odtk::CanvasArgs a{};
+  a.n = static_cast<uint32_t>(n_rects);
+  for (int l = 0; l < n_rects; ++l) {
+    const int y0 = rects[4 * l], x0 = rects[4 * l + 1], h = rects[4 * l + 2], w = rects[4 * l + 3];
+    if (y0 < 0 || x0 < 0 || h <= 0 || w <= 0 || y0 > height - h || x0 > width - w) return ODTK_ERR_INVALID;   // inside the canvas
+    if (sources && (!sources[l] || (reinterpret_cast<uintptr_t>(sources[l]) & 15u))) return ODTK_ERR_INVALID;
+    a.y0[l] = static_cast<uint32_t>(y0); a.x0[l] = static_cast<uint32_t>(x0);
+    a.h[l] = static_cast<uint32_t>(h); a.w[l] = static_cast<uint32_t>(w);
+    a.src[l] = sources ? static_cast<const odtk::vuint4 *>(sources[l]) : nullptr;
+  }
+  unsigned long long blocks = (total + 256ull * 4 - 1) / (256ull * 4);           // ~4 vectors per lane
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(odtk::canvas_fill_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<odtk::vuint4 *>(canvas), a, static_cast<uint32_t>(groups), static_cast<uint32_t>(total),
+                     odtk::fastdiv_make(static_cast<uint32_t>(groups)), odtk::fastdiv_make(static_cast<uint32_t>(width)),
+                     odtk::fastdiv_make(static_cast<uint32_t>(height)));
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_canvas_clear(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects, int n_rects,
+                      void *stream) {
+  return odtk_canvas_pack(canvas, batch_size, height, width, channels, dtype, rects, nullptr, n_rects, stream);
+}
+
 int odtk_stem_pack(const void *x, void *out, int batch_size, int height, int width, int in_dtype, int channels_last, int out_dtype,
                    void *stream) {
   if (!x || !out || batch_size <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return ODTK_ERR_INVALID;

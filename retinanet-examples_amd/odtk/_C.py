@@ -119,6 +119,9 @@ _SIGNATURES = {
     'odtk_prefilter_thresholds': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp]),
     'odtk_upsample_nearest2x': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_void_p]),
+    'odtk_canvas_clear': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_void_p]),
+    'odtk_canvas_pack': (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int), _vpp, ctypes.c_int,
+                                        ctypes.c_void_p]),
     'odtk_stem_pack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'odtk_preprocess_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), _vp, _sz, _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int,
@@ -780,6 +783,50 @@ def upsample2x(x):
     return out
 
 
+def _canvas_args(canvas, rects, what):
+    if not canvas.is_cuda or canvas.dim() != 4 or canvas.dtype not in _DTYPES:
+        raise RuntimeError('%s: canvas must be a 4-d CUDA tensor of float32/bfloat16/float16' % what)
+    n, c, h, w = canvas.shape
+    if not canvas.is_contiguous(memory_format=torch.channels_last) or (c * canvas.element_size()) % 16:
+        raise RuntimeError('%s: canvas must be channels_last with channels * element size a multiple of 16 bytes' % what)
+    if len(rects) > MAX_LEVELS:
+        raise RuntimeError('%s: at most %d rectangles' % (what, MAX_LEVELS))
+    flat = [int(v) for r in rects for v in r]
+    if len(flat) != 4 * len(rects):
+        raise RuntimeError('%s: a rectangle is (y0, x0, height, width)' % what)
+    return n, c, h, w, (ctypes.c_int * max(len(flat), 1))(*flat)
+
+
+def canvas_clear_(canvas, rects):
+    """In place: zero every pixel of the channels_last `canvas` outside `rects` = [(y0, x0, height, width), ...] (the gutters of the
+    engine's pyramid canvas; include/odtk_hip.h: odtk_canvas_clear).  One launch; pixels inside the rectangles are not touched."""
+    n, c, h, w, arr = _canvas_args(canvas, rects, 'canvas_clear_')
+    with torch.cuda.device(canvas.device):
+        stream = torch.cuda.current_stream(canvas.device).cuda_stream
+        _check(library().odtk_canvas_clear(canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr, len(rects), stream), 'canvas_clear')
+    return canvas
+
+
+def canvas_pack(levels, rects, height, width):
+    """The pyramid canvas [B, C, height, width] (channels_last) of the channels_last activations `levels`: level i in rectangle
+    rects[i] = (y0, x0, height_i, width_i), zeros elsewhere (include/odtk_hip.h: odtk_canvas_pack).  One launch."""
+    first = levels[0]
+    n, c = first.shape[:2]
+    if len(levels) != len(rects):
+        raise RuntimeError('canvas_pack: one rectangle per level')
+    for t, r in zip(levels, rects):
+        if (not t.is_cuda or t.dim() != 4 or t.dtype != first.dtype or t.device != first.device or tuple(t.shape) != (n, c, r[2], r[3])
+                or not (t.is_contiguous(memory_format=torch.channels_last))):
+            raise RuntimeError('canvas_pack: every level must be a channels_last [B, C, h, w] CUDA tensor of one dtype filling its rectangle')
+    canvas = torch.empty((n, c, height, width), dtype=first.dtype, device=first.device, memory_format=torch.channels_last)
+    n, c, h, w, arr = _canvas_args(canvas, rects, 'canvas_pack')
+    with torch.cuda.device(canvas.device):
+        stream = torch.cuda.current_stream(canvas.device).cuda_stream
+        _check(library().odtk_canvas_pack(canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr, _ptrs(list(levels)), len(rects), stream),
+               'canvas_pack')
+    return canvas
+
+
 def stem_pack(x, dtype):
     """2x2 space-to-depth pack of the network input [B, 3, H, W] (float32 / bfloat16 / float16, NCHW- or channels_last-contiguous, H and
     W even) into [B, 16, H/2, W/2] channels_last of `dtype` (bf16 / fp16): channel (dy*2+dx)*3+c of pixel (y, x) is x[:, c, 2y+dy, 2x+dx],
@@ -900,6 +947,9 @@ def conv_library():
             lib.odtk_conv_bias_act.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 13 + [ctypes.c_void_p]
             lib.odtk_conv_bias_act_pads.restype = ctypes.c_int
             lib.odtk_conv_bias_act_pads.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 15 + [ctypes.c_void_p]
+            lib.odtk_conv_bias_act_strided.restype = ctypes.c_int
+            lib.odtk_conv_bias_act_strided.argtypes = ([ctypes.c_void_p] * 4 + [ctypes.c_int] * 13 + [ctypes.c_longlong] * 6 +
+                                                       [ctypes.c_int] * 2 + [ctypes.c_void_p])
             lib.odtk_conv_last_plan.restype = ctypes.c_char_p
             lib.odtk_conv_last_plan.argtypes = []
             lib.odtk_conv_instance_count.restype = ctypes.c_int
@@ -932,8 +982,6 @@ def conv_bias_act(x, weight, bias, stride=(1, 1), padding=(1, 1), relu=True, out
     k, c2, kh, kw = weight.shape
     if c2 != c or weight.dtype != x.dtype or not weight.is_contiguous(memory_format=torch.channels_last):
         raise RuntimeError('conv_bias_act: weight must be [Cout, Cin, kh, kw] of x.dtype, channels_last')
-    if not x.is_contiguous(memory_format=torch.channels_last):
-        raise RuntimeError('conv_bias_act: x must be channels_last')
     if bias.dtype != x.dtype or bias.numel() != k or not bias.is_cuda or not bias.is_contiguous():
         raise RuntimeError('conv_bias_act: bias must be a CUDA vector of length Cout in the dtype of x')
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
@@ -944,14 +992,27 @@ def conv_bias_act(x, weight, bias, stride=(1, 1), padding=(1, 1), relu=True, out
     if out is None:
         y = torch.empty((b, k, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     else:                                                    # caller-owned output (the engine's head-tensor arena)
-        if tuple(out.shape) != (b, k, ho, wo) or out.dtype != x.dtype or out.device != x.device or \
-                not out.is_contiguous(memory_format=torch.channels_last):
+        if tuple(out.shape) != (b, k, ho, wo) or out.dtype != x.dtype or out.device != x.device:
             raise RuntimeError('conv_bias_act: out must be a channels_last %s tensor of shape %s' % (x.dtype, (b, k, ho, wo)))
         y = out
+    # channels_last tensors, or views of larger ones (a rectangle of the engine's pyramid canvas, a channel slice): the channel
+    # stride is 1 and the library takes the other three (include/odtk_conv_strided.h -- it says which views it refuses)
+    views = []
+    for t, name in ((x, 'x'), (y, 'out')):
+        sn, sc, srow, spix = t.stride()
+        if t.shape[1] != 1 and sc != 1:
+            raise RuntimeError('conv_bias_act: %s must be channels_last (or a view of a channels_last tensor)' % name)
+        ch, hh, ww = t.shape[1], t.shape[2], t.shape[3]
+        # (torch reports arbitrary strides for dimensions of size 1: take the packed ones there)
+        spix = spix if ww > 1 else ch
+        srow = srow if hh > 1 else ww * spix
+        sn = sn if t.shape[0] > 1 else hh * srow
+        views += [sn, srow, spix]
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        _check(lib.odtk_conv_bias_act_pads(y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), b, c, h, w, k, kh, kw,
-                                           sh, sw, ph0, pw0, ph1, pw1, _DTYPES[x.dtype], 1 if relu else 0, stream), 'conv_bias_act')
+        _check(lib.odtk_conv_bias_act_strided(y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), b, c, h, w, k, kh, kw,
+                                              sh, sw, ph0, pw0, ph1, pw1, *views, _DTYPES[x.dtype], 1 if relu else 0, stream),
+               'conv_bias_act')
     return y
 
 

@@ -14,6 +14,8 @@ Measured on MI355X those passes cost more than the convolutions between them.  H
   * 1x1 stride-1 convolutions (two of the three convs of every bottleneck, the FPN laterals) are a
     plain GEMM on the channels_last activation: they run as ONE hipBLASLt call with bias, skip and ReLU
     in the GEMM epilogue (`odtk_gemm_bias_act`, csrc/gemm_lt.hpp) -- no epilogue pass at all;
+  * the head towers of the pyramid levels below P3 run as ONE convolution per layer over a packed canvas with zero gutters
+    between the levels (`pyramid_canvas_layout`, `_canvas_towers`; DESIGN.md section 5) instead of one launch per level;
   * the post-processing reads the raw head tensors in place (odtk.box.detect(..., logits=True)); in
     `forward` even the bias of the heads' LAST convolutions is not applied by a pass of its own: it is
     handed to the post-processing kernels (`cls_bias` / `box_bias`), which add it in fp32 to the few values
@@ -93,6 +95,37 @@ def space_to_depth_pack(x):
     return torch.cat([xs, torch.zeros(b, 4, h // 2, w // 2, dtype=x.dtype, device=x.device)], 1)
 
 
+def pyramid_canvas_layout(shapes, gutter=1):
+    """Packs pyramid levels of extents `shapes` = [(h, w), ...] into one canvas: -> ((H, W), [(y0, x0), ...]).
+    The first level lies at the origin; the others fill a shelf to its right, left to right with `gutter` pixels between them, a
+    new shelf row underneath once a level no longer fits beside its neighbours and the height still allows one (otherwise the row
+    grows to the right).  The rectangles are disjoint, at least `gutter` apart and inside the canvas for ANY extents (a 128-pixel
+    image's P7 is 1 x 1).  P4..P7 of an 800 x 1280 input: 50 x 121 -- P4 | P5 over (P6, P7)."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    if not shapes or min(min(s) for s in shapes) <= 0 or gutter < 0:
+        raise ValueError('pyramid_canvas_layout: needs positive extents and a gutter >= 0')
+    height = max(h for h, _ in shapes)
+    origins = [(0, 0)]
+    shelf_x = shapes[0][1] + gutter
+    shelf_w, row_y, row_h, cursor = None, 0, 0, shelf_x
+    for h, w in shapes[1:]:
+        if shelf_w is None:
+            shelf_w = w                                                 # the first shelf level sets the shelf's width
+        elif cursor + w > shelf_x + shelf_w and row_y + row_h + gutter + h <= height:
+            row_y, row_h, cursor = row_y + row_h + gutter, 0, shelf_x   # a new shelf row underneath
+        origins.append((row_y, cursor))
+        shelf_w = max(shelf_w, cursor + w - shelf_x)
+        row_h = max(row_h, h)
+        cursor += w + gutter
+    return ((max(y + h for (y, _), (h, _) in zip(origins, shapes)), max(x + w for (_, x), (_, w) in zip(origins, shapes))), origins)
+
+
+def _window(x):
+    """A spatial window of a channels_last tensor whose strides the convolution library takes (include/odtk_conv_strided.h)."""
+    return (x.dim() == 4 and x.shape[1] > 1 and x.stride(1) == 1 and x.stride(3) >= x.shape[1]
+            and all(v % 8 == 0 for v in (x.stride(0), x.stride(2), x.stride(3))))
+
+
 class _Conv(nn.Module):
     """Convolution + bias (+ residual) (+ ReLU).  Three native routes, by kernel shape:
       * 1x1: ONE hipBLASLt GEMM with the whole epilogue (`odtk_gemm_bias_act`);
@@ -145,6 +178,32 @@ class _Conv(nn.Module):
         y = self._miopen_only(x)
         return y if out is None else out.copy_(y)                       # (MIOpen owns its output: an arena then costs a copy)
 
+    def on_view(self, x, only=False, out=None):
+        """`forward` (or `conv_only`) on a spatial window of a larger channels_last tensor -- a level's rectangle of the pyramid
+        canvas.  Where this geometry is routed to the convolution library the window is read in place; otherwise, and where the
+        library refuses the view, it is copied out first.  (The route of the packed geometry is left alone either way.)"""
+        if x.is_contiguous(memory_format=torch.channels_last):
+            return self.conv_only(x, out) if only else self(x)
+        if self.library_ok and _Conv.use_conv_library and x.is_cuda and _window(x) and _C.conv_available():
+            if only and self.zero_bias is None:
+                self.zero_bias = torch.zeros_like(self.bias_lp)
+            key = (('only',) + tuple(x.shape)) if only else tuple(x.shape)
+            two, one = (self._miopen_only, self._library_only) if only else (self._two_pass, self._one_pass)
+            if self._routed(key, 'only' if only else 'act', x, two, one):
+                try:
+                    return self._library_only(x, out) if only else self._one_pass(x)
+                except RuntimeError:
+                    pass
+        x = x.contiguous(memory_format=torch.channels_last)
+        return self.conv_only(x, out) if only else self(x)
+
+    def _torch(self, x, residual=None):
+        """Plain torch (CPU tensors: the engine's logic without a GPU; no hot path)."""
+        y = F.conv2d(x, self.weight, None, self.stride, self.padding, groups=self.groups) + self.bias.to(x.dtype).view(1, -1, 1, 1)
+        if residual is not None:
+            y = y + residual
+        return (F.relu(y) if self.relu else y).contiguous(memory_format=torch.channels_last)
+
     def _miopen_only(self, x):
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, groups=self.groups)
         return y if y.is_contiguous(memory_format=torch.channels_last) else y.contiguous(memory_format=torch.channels_last)
@@ -188,6 +247,8 @@ class _Conv(nn.Module):
         return (t_one < t_two, t_one, t_two)
 
     def forward(self, x, residual=None):
+        if not x.is_cuda:
+            return self._torch(x, residual)
         if self.pointwise and _C.gemm_available():
             if tuple(self.stride) != (1, 1):
                 # a strided 1x1 convolution (the downsample branches): the GEMM wants the subsampled pixels as a dense matrix -- a
@@ -226,6 +287,8 @@ class _Conv(nn.Module):
 
     def conv_then_pool(self, x):
         """conv -> bias -> ReLU -> maxpool 3x3/s2 with the epilogue folded into the pooling pass."""
+        if not x.is_cuda:
+            return F.max_pool2d(self._torch(x), 3, 2, 1)
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, groups=self.groups)
         if y.dtype in (torch.bfloat16, torch.float16) and y.shape[1] % 8 == 0:
             return _C.bias_act_maxpool(y.contiguous(memory_format=torch.channels_last), self.bias, self.relu)
@@ -306,6 +369,9 @@ class FusedRetinaNet(nn.Module):
         self.cls_head = head(model.cls_head)
         self.box_head = head(model.box_head)
         self.level_streams = True                                       # small pyramid levels on side HIP streams
+        # the levels below P3 packed into ONE canvas per image, their towers as one convolution per layer (_canvas_towers);
+        # ODTK_PYRAMID_CANVAS=0: one launch per level and layer (A/B).  'always': CPU tensors too (tests; plain torch)
+        self.pyramid_canvas = os.environ.get('ODTK_PYRAMID_CANVAS', '1') != '0'
         self._streams = None
         self.tower_plan = 0
         self._planned = set()                                           # input geometries whose k x k convolutions were routed (plan pass)
@@ -379,11 +445,71 @@ class FusedRetinaNet(nn.Module):
             t = c(t)
         return t
 
+    def _canvas_gutter(self, feats):
+        """Zero pixels between the levels of the pyramid canvas = the largest padding of the towers' convolutions; None when the
+        canvas does not apply: switched off, fewer than two levels below P3, or a tower convolution that is not stride 1 with
+        "same" padding (the gutters stand in for exactly that padding)."""
+        if not self.pyramid_canvas or len(feats) < 3 or not (feats[0].is_cuda or self.pyramid_canvas == 'always'):
+            return None
+        gutter = 0
+        for c in list(self.cls_head[:-1]) + list(self.box_head[:-1]):
+            kh, kw = c.weight.shape[2:]
+            if (tuple(c.stride) != (1, 1) or c.groups != 1 or kh % 2 == 0 or kw % 2 == 0 or tuple(c.padding) != (kh // 2, kw // 2)
+                    or c.weight.shape[0] != c.weight.shape[1]):
+                return None
+            gutter = max(gutter, kh // 2, kw // 2)
+        first = feats[1]
+        if any(t.shape[:2] != first.shape[:2] or t.dtype != first.dtype for t in feats[2:]):
+            return None
+        if first.is_cuda and ((first.shape[1] * first.element_size()) % 16 or len(feats) - 1 > _C.MAX_LEVELS
+                              or not all(t.is_contiguous(memory_format=torch.channels_last) for t in feats[1:])):
+            return None
+        return gutter
+
+    def _canvas_towers(self, feats, gutter, last_bias, arena=None):
+        """Both head towers on the levels below P3 -- a quarter of the pyramid's pixels, but four launches per layer of which the
+        smallest are pure latency (a P7 layer: 24 us for 1 us of arithmetic) -- as ONE convolution per layer.  The levels lie side
+        by side in one channels_last canvas per image (pyramid_canvas_layout) with `gutter` zero pixels between them: the tower
+        weights are shared across levels, and to a "same"-padded convolution a zero gutter is each level's zero padding.  A layer
+        writes act(bias + ...) into the gutters, so they are cleared (one launch, `odtk_canvas_clear`) before the next layer reads
+        them; the fourth layer's are never read.  The heads' last convolutions run per level on their rectangle of the last canvas,
+        read in place (`_Conv.on_view`), and write the same per-level tensors as the per-level path.
+        Every buffer is allocated inside the call (a captured graph owns them)."""
+        shapes = [(t.shape[2], t.shape[3]) for t in feats]
+        (height, width), origins = pyramid_canvas_layout(shapes, gutter)
+        rects = [(y, x, h, w) for (y, x), (h, w) in zip(origins, shapes)]
+        if feats[0].is_cuda:
+            canvas = _C.canvas_pack(feats, rects, height, width)
+            mask = None
+        else:
+            first = feats[0]
+            canvas = torch.zeros((first.shape[0], first.shape[1], height, width), dtype=first.dtype).contiguous(memory_format=torch.channels_last)
+            mask = torch.ones((1, 1, height, width), dtype=torch.bool)
+            for t, (y, x, h, w) in zip(feats, rects):
+                canvas[:, :, y:y + h, x:x + w] = t
+                mask[:, :, y:y + h, x:x + w] = False
+        out = []
+        for which, head in enumerate((self.cls_head, self.box_head)):
+            t = canvas
+            for j, c in enumerate(head[:-1]):
+                t = c(t)
+                if gutter and j + 2 < len(head):
+                    t = _C.canvas_clear_(t, rects) if t.is_cuda else t.masked_fill_(mask, 0)
+            last = head[-1]
+            views = [t[:, :, y:y + h, x:x + w] for y, x, h, w in rects]
+            if last_bias:
+                out.append([last.on_view(v) for v in views])
+            else:
+                out.append([last.on_view(v, True, None if (arena is None or which) else arena[i]) for i, v in enumerate(views)])
+        return list(zip(*out))
+
     def _towers(self, feats, last_bias, level_streams=None):
         """Both head towers on every pyramid level.  The levels are independent and the small ones (P5-P7:
         8000 / 2080 / 560 pixels at bs 8) cannot fill 256 CUs on their own, so they run on side HIP streams
-        next to P3's convolutions: [P3] on the caller's stream, [P4] and [P5, P6, P7] on two others."""
+        next to P3's convolutions: [P3] on the caller's stream and the pyramid canvas of P4..P7 (`_canvas_towers`) on another --
+        or, without the canvas, [P4] and [P5, P6, P7] on two others."""
         arena = self._cls_arena(feats) if (self.cls_arena and not last_bias and feats[0].is_cuda and not _planning()) else None
+        out = [None] * len(feats)
 
         def level(t, i):
             if last_bias:
@@ -391,10 +517,20 @@ class FusedRetinaNet(nn.Module):
             return (self.cls_head[-1].conv_only(self._run(self.cls_head[:-1], t), None if arena is None else arena[i]),
                     self.box_head[-1].conv_only(self._run(self.box_head[:-1], t)))
 
+        def unit(i):
+            """One pyramid level -- or, for i == 'canvas', all the levels below P3 at once."""
+            if i == 'canvas':
+                out[1:] = self._canvas_towers(feats[1:], gutter, last_bias, None if arena is None else arena[1:])
+                return out[1:]
+            out[i] = level(feats[i], i)
+            return [out[i]]
+
+        gutter = self._canvas_gutter(feats)
         if level_streams is None:
             level_streams = self.level_streams
         if not level_streams or not feats[0].is_cuda or len(feats) < 3:
-            out = [level(t, i) for i, t in enumerate(feats)]
+            for i in ([0, 'canvas'] if gutter is not None else range(len(feats))):
+                unit(i)
             return [o[0] for o in out], [o[1] for o in out]
         main = torch.cuda.current_stream(feats[0].device)
         if self._streams is None or self._streams[0].device != feats[0].device:
@@ -402,25 +538,27 @@ class FusedRetinaNet(nn.Module):
         n = len(feats)
         # (levels on `main`, levels of each side stream).  One A/B run (bench.py --tower-plan): 7.52 / 7.37 / 7.34 ms
         # per step for plans 0 / 1 / 2 in that order on one box -- within its drift; 0 is the tested default
-        mine, groups = {0: ([0], [[1], list(range(2, n))]),
-                        1: (list(range(2, n)) + [1], [[0]]),
-                        2: ([0], [[1], [2], list(range(3, n))])}[self.tower_plan]
+        if gutter is not None:                                          # the canvas is one unit where a level was one before
+            mine, groups = {0: ([0], [['canvas']]), 1: (['canvas'], [[0]]), 2: ([0], [['canvas']])}[self.tower_plan]
+        else:
+            mine, groups = {0: ([0], [[1], list(range(2, n))]),
+                            1: (list(range(2, n)) + [1], [[0]]),
+                            2: ([0], [[1], [2], list(range(3, n))])}[self.tower_plan]
         ready = torch.cuda.Event()
         ready.record(main)
-        out = [None] * len(feats)
         done = []
         for stream, group in zip(self._streams, groups):
             stream.wait_event(ready)                                    # the pyramid is complete
             with torch.cuda.stream(stream):
                 for i in group:
-                    out[i] = level(feats[i], i)
-                    for t in out[i]:
-                        t.record_stream(main)                           # consumed by the post-processing on `main`
+                    for pair in unit(i):
+                        for t in pair:
+                            t.record_stream(main)                       # consumed by the post-processing on `main`
                 e = torch.cuda.Event()
                 e.record(stream)
                 done.append(e)
         for i in mine:
-            out[i] = level(feats[i], i)
+            unit(i)
         for e in done:
             main.wait_event(e)
         return [o[0] for o in out], [o[1] for o in out]
@@ -471,7 +609,7 @@ class FusedRetinaNet(nn.Module):
         m = self.model[0]                                                # (post-processing parameters are baked into the launches)
         bias = self.cls_head[-1].bias                                    # its state is baked in too: the prefilter's threshold table
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
-               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, bias.data_ptr(), bias._version)
+               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, bias.data_ptr(), bias._version)
         entry = self._graphs.get(key)
         if entry is None:
             static_x = torch.empty_like(x)
