@@ -65,8 +65,8 @@ extern "C" {
 
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
- * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t; -1 for any other value (4 stays
- * unassigned: tests/test_abi_host.py probes it as the first unknown id).  A binding compiled (or
+ * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t; -1 for any other value
+ * (4 stays unassigned: tests/test_abi_host.py probes it as the first unknown id).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -304,6 +304,43 @@ typedef struct odtk_image {
 int odtk_preprocess_images(int batch_size, const odtk_image_t *images, const void *src, size_t src_bytes, const int32_t *tables,
                            size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *stream);
 
+/*
+ * odtk_augment_images -- odtk_preprocess_images with the training augmentations of the reference's dataset between the resize and
+ * the normalisation (odtk/data.py:68-109 there: `im.rotate` by a quarter turn, FLIP_LEFT_RIGHT, ImageEnhance.Brightness / Contrast,
+ * torchvision's adjust_hue, ImageEnhance.Color), bit-identical to Pillow on the host; per image, in this order:
+ *   resize (as odtk_preprocess_images; images[i].mirror must be 0, the flip is part of the map)
+ *   -> canvas[y][x] = resized[(map[5] + map[3] x + map[4] y) >> 16][(map[2] + map[0] x + map[1] y) >> 16] for x < canvas_width,
+ *      y < canvas_height, black (0, 0, 0) where that index lies outside the resized image: Pillow's 16.16 fixed-point NEAREST affine
+ *      transform; a transpose, the flip and the identity {65536, 0, 0, 0, 65536, 0} are maps of the same form (odtk/data.py:
+ *      quarter_turn_map computes them on the host, in double)
+ *   -> brightness, contrast, saturation: byte = (uint8)(d + factor * (byte - d)) in float32 (product, then sum), clamped to
+ *      [0, 255] first unless 0 <= factor <= 1; d = 0 | the image's grey level int(mean of L + 0.5) over the canvas as it is after
+ *      the brightness | L of the pixel, L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  Hue (between contrast and saturation):
+ *      RGB -> HSV, H += hue (wrapping byte), HSV -> RGB as Pillow's `convert` does them; it runs, lossy, also for hue = 0
+ *   -> out[b][y][x][c] = norm_table[c][byte], +0.0 outside the canvas.  Every element is written.
+ * An image with flags = 0 and the identity map comes out exactly as odtk_preprocess_images writes it.
+ *   augments    HOST odtk_augment_t[batch_size], like images
+ *   workspace   DEVICE scratch, 16-byte aligned: the resized bytes of every image and one 64-bit sum per image.  Two-phase:
+ *               workspace == NULL returns the bytes needed for (batch_size, height, width).
+ * Everything else as odtk_preprocess_images.  A short chain of launches on `stream` (the grey level of the contrast has to exist
+ * before any output pixel does): resize to bytes, sum of L (only if some image has contrast on), gather + colours + table + pad.
+ * Everything is checked on the host before anything touches HIP; a workspace that is too small is ODTK_ERR_INVALID.
+ */
+#define ODTK_AUGMENT_BRIGHTNESS 1u
+#define ODTK_AUGMENT_CONTRAST   2u
+#define ODTK_AUGMENT_HUE        4u
+#define ODTK_AUGMENT_SATURATION 8u
+typedef struct odtk_augment {
+  int32_t canvas_width, canvas_height;      /* size after the turn (<= width, height of the batch)      */
+  int32_t map[6];                           /* 16.16 fixed point, see above                             */
+  uint32_t flags;                           /* ODTK_AUGMENT_*                                           */
+  float brightness, contrast, saturation;   /* blend factors (finite), read only if their flag is set   */
+  uint8_t hue;                              /* added to H modulo 256                                    */
+  uint8_t pad_[3];                          /* zero                                                     */
+} odtk_augment_t;
+int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const void *src, size_t src_bytes,
+                        const int32_t *tables, size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype,
+                        void *workspace, size_t workspace_bytes, void *stream);
 /*
  * odtk_gemm_bias_act -- 1x1 (pointwise) convolution of a channels_last activation as ONE GEMM with
  * the whole epilogue fused:

@@ -20,6 +20,9 @@
 //   3. footprints beyond kPreLdsRows rows (down-scaling by more than ~2) are walked in chunks of that many rows; the vertical sum
 //      is an integer sum, so accumulating it across chunks is exact.
 // Elements outside an image's out_h x out_w are +0.0 (all bits zero), like F.pad of the normalised image.
+//
+// BYTES = true is the same tile code as pass A of the augmentation chain (augment.hpp): the resized R G B bytes themselves go to
+// the image's slot of the workspace, rows 3 * out_width bytes apart, instead of through the table; nothing is padded.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,6 +50,9 @@ struct PreArgs {
   int32_t height, width;
   int32_t first;           // batch index of images[0]
   int32_t vector_rows;     // every output row is a whole number of 16-byte vectors and starts on one
+  uint8_t *bytes;          // BYTES only: slot of image b = bytes + b * slot, 16-byte aligned
+  unsigned long long *sums;  // BYTES only: one per image of the batch, zeroed here for the sum of L (augment.hpp)
+  uint64_t slot;
   odtk_image_t images[kPreMaxImages];
 };
 
@@ -71,8 +77,8 @@ __device__ __forceinline__ void pre_bounds(const int32_t *tables, int32_t table,
   *n = c > in_size - f ? in_size - f : c;
 }
 
-template <int ES>   // bytes per output element: 4 (fp32) or 2 (bf16 / fp16 -- the table holds the bits, nothing is converted here)
-__global__ __launch_bounds__(256) void preprocess_images_kernel(const PreArgs a) {
+template <int ES, bool BYTES = false>   // bytes per output element: 4 (fp32) or 2 (bf16 / fp16 -- the table holds the bits, nothing is
+__global__ __launch_bounds__(256) void preprocess_images_kernel(const PreArgs a) {   // converted here); BYTES: 4, see above
   constexpr int EPT = 16 / ES;                                    // elements per 16-byte store
   constexpr int VPR = kPreRowBytes / EPT;                         // vectors per tile row
   constexpr int ITEMS = (kPreTileH * VPR + 255) / 256;            // vectors per thread
@@ -88,7 +94,11 @@ __global__ __launch_bounds__(256) void preprocess_images_kernel(const PreArgs a)
   const bool live = x0 < ow && y0 < oh;                           // (workgroup-uniform) otherwise the tile is padding only
   const int32_t *tables = a.tables;
 
-  for (int i = tid; i < 3 * 256; i += 256) norm[i] = static_cast<const elem_t *>(a.norm)[i];
+  if constexpr (BYTES) {
+    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) a.sums[a.first + blockIdx.z] = 0ull;
+  } else {
+    for (int i = tid; i < 3 * 256; i += 256) norm[i] = static_cast<const elem_t *>(a.norm)[i];
+  }
 
   // this thread's vectors: tile row, first element in the row, vertical taps
   int32_t acc[ITEMS][EPT], ymin[ITEMS], yn[ITEMS];
@@ -161,6 +171,29 @@ __global__ __launch_bounds__(256) void preprocess_images_kernel(const PreArgs a)
   }
   __syncthreads();                                                // norm[] is written (a tile of padding never entered the loop)
 
+  if constexpr (BYTES) {
+    static_assert(ES == 4 && EPT == 4, "four bytes per item");
+    uint8_t *slot = a.bytes + static_cast<size_t>(a.first + blockIdx.z) * a.slot;
+    const int32_t row_bytes = ow * 3;
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const int item = tid + it * 256;
+      const int32_t y = y0 + item / VPR, first = x0 * 3 + (item % VPR) * EPT;
+      if (item >= kPreTileH * VPR || y >= oh || first >= row_bytes) continue;
+      uint8_t *dst = slot + static_cast<size_t>(y) * row_bytes + first;
+      uint32_t w = 0;
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) w |= static_cast<uint32_t>(pre_byte(acc[it][e])) << (8 * e);
+      if ((row_bytes & 3) == 0) {                                   // rows start on a word, and so does `first`
+        *reinterpret_cast<uint32_t *>(dst) = w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e)
+          if (first + e < row_bytes) dst[e] = static_cast<uint8_t>(w >> (8 * e));
+      }
+    }
+    return;
+  }
   elem_t *out = static_cast<elem_t *>(a.out) + static_cast<size_t>(a.first + blockIdx.z) * a.height * a.width * 3;
   const int32_t row_elems = a.width * 3;
 #pragma unroll

@@ -72,6 +72,13 @@ class Image(ctypes.Structure):
                 ('x_taps', ctypes.c_int32), ('y_taps', ctypes.c_int32)]
 
 
+class Augment(ctypes.Structure):
+    """odtk_augment_t"""
+    _fields_ = [('canvas_width', ctypes.c_int32), ('canvas_height', ctypes.c_int32), ('map', ctypes.c_int32 * 6),
+                ('flags', ctypes.c_uint32), ('brightness', ctypes.c_float), ('contrast', ctypes.c_float),
+                ('saturation', ctypes.c_float), ('hue', ctypes.c_uint8), ('pad_', ctypes.c_uint8 * 3)]
+
+
 _SIGNATURES = {
     'odtk_version': (ctypes.c_char_p, []),
     'odtk_abi_struct_size': (ctypes.c_int, [ctypes.c_int]),
@@ -126,6 +133,8 @@ _SIGNATURES = {
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'odtk_preprocess_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), _vp, _sz, _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, _vp]),
+    'odtk_augment_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), ctypes.POINTER(Augment), _vp, _sz, _vp, _sz, _vp, _vp,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_nms_sorted_runs': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_gemm_init': (ctypes.c_int, [ctypes.c_char_p]),
@@ -170,7 +179,7 @@ def library():
             fn.restype = res
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
-        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image)):
+        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -871,6 +880,35 @@ def preprocess_images(src, images, tables, table, height, width):
         _check(library().odtk_preprocess_images(batch, images, src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None,
                                                 tables.numel(), table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype],
                                                 stream), 'preprocess_images')
+    return out
+
+
+def augment_images(src, images, augments, tables, table, height, width):
+    """`preprocess_images` with the training augmentations between the resize and the normalisation (include/odtk_hip.h:
+    odtk_augment_images): quarter turn and flip as an index map, brightness, contrast, hue, saturation, Pillow-exact.
+    augments: a ctypes array (or sequence) of `Augment`, one per image, HOST memory; the rest as `preprocess_images`.
+    -> [len(images), 3, height, width] with channels_last strides."""
+    if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise RuntimeError('augment_images: src must be a contiguous uint8 CUDA tensor')
+    if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
+        raise RuntimeError('augment_images: tables must be a contiguous int32 tensor on the device of src')
+    if table.device != src.device or table.dtype not in _DTYPES or tuple(table.shape) != (3, 256) or not table.is_contiguous():
+        raise RuntimeError('augment_images: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src')
+    if not isinstance(images, ctypes.Array):
+        images = (Image * len(images))(*images)
+    if not isinstance(augments, ctypes.Array):
+        augments = (Augment * len(augments))(*augments)
+    batch = len(images)
+    if len(augments) != batch:
+        raise RuntimeError('augment_images: %d images but %d augment descriptors' % (batch, len(augments)))
+    out = torch.empty((batch, 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
+    lib = library()
+    with torch.cuda.device(src.device):
+        args = (batch, images, augments, src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None, tables.numel(),
+                table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype])
+        size = _check(lib.odtk_augment_images(*args, None, 0, None), 'augment_images (workspace query)')
+        ws, stream = _workspace(src.device, size)
+        _check(lib.odtk_augment_images(*args, ws.data_ptr(), ws.numel(), stream), 'augment_images')
     return out
 
 

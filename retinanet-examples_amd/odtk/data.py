@@ -20,6 +20,9 @@ split of the work between the host and the GPU:
 With `device_resize=True` the resize moves to the device as well: workers hand over the decoded SOURCE pixels (uint8 RGB, 3
 bytes per pixel) with the tables of Pillow's fixed-point bilinear resampling (`resample_weights`), and one HIP launch per batch
 (`odtk_preprocess_images`) resizes, mirrors, pads and normalises -- bit-identical to the host path, see `SourceBatch`.
+`device_augment=True` is that hand-over plus the training augmentations: the workers draw the quarter turn, the flip and the
+colour factors and ship them as descriptors; the turn (Pillow's fixed-point index map), brightness, contrast, hue and saturation
+run on the device between the resize and the normalisation (`odtk_augment_images`), bit-identical to Pillow on the host.
 
 `CocoIndex` is the part of `pycocotools.coco.COCO` (nvidia/cocoapi master, un-pinned and absent from this
 image) that the reference touches: `dataset`, `imgs`, `getCatIds`, `getAnnIds`, `loadAnns`, `loadImgs`,
@@ -193,11 +196,182 @@ def resize_bilinear(pixels, size):
     return np.ascontiguousarray(pixels)
 
 
+# -- Pillow's quarter turns and colour enhancements, restated ------------------------------------------------------------------------
+# What `__getitem__` does to the resized image in training -- `Image.rotate` by a quarter turn, FLIP_LEFT_RIGHT, ImageEnhance's
+# Brightness / Contrast / Color and `_adjust_hue` -- in numpy, every step in the number format Pillow's C uses.  They are the CPU
+# implementation of `device_augment=True` and what the device path (include/odtk_hip.h: odtk_augment_images) is pinned to.
+
+AUGMENT_BRIGHTNESS, AUGMENT_CONTRAST, AUGMENT_HUE, AUGMENT_SATURATION = 1, 2, 4, 8     # odtk_augment_t.flags
+_FIX_ONE = 1 << 16
+
+
+def _fix(v):
+    """Pillow's FIX(): a double to 16.16 fixed point."""
+    return int(math.floor(v * 65536.0 + 0.5))
+
+
+def quarter_turn_map(width, height, angle, expand=False, flip=False):
+    """`im.rotate(angle[, expand=True])` of a `width` x `height` image for angle in {0, 90, 180, 270}, then (flip) FLIP_LEFT_RIGHT, as
+    an index map: -> (canvas width, canvas height, (a0, a1, a2, a3, a4, a5)) with
+        out[y][x] = in[(a5 + a3 x + a4 y) >> 16][(a2 + a0 x + a1 y) >> 16],   black where that lies outside the image.
+    180 degrees, and 90 / 270 with `expand` or on a square image, are transposes in Pillow; 90 / 270 otherwise is its NEAREST affine
+    transform on the same canvas, evaluated in 16.16 fixed point from the matrix `Image.rotate` builds in double."""
+    width, height, angle = int(width), int(height), int(angle) % 360
+    if angle not in (0, 90, 180, 270):
+        raise ValueError('quarter_turn_map: angle must be a multiple of 90, got %r' % angle)
+    cw, ch = width, height
+    if angle == 0:
+        a = [_FIX_ONE, 0, 0, 0, _FIX_ONE, 0]
+    elif angle == 180:
+        a = [-_FIX_ONE, 0, (width - 1) * _FIX_ONE, 0, -_FIX_ONE, (height - 1) * _FIX_ONE]
+    elif expand or width == height:
+        cw, ch = height, width
+        if angle == 90:                                             # ROTATE_90: out[y][x] = in[x][width - 1 - y]
+            a = [0, -_FIX_ONE, (width - 1) * _FIX_ONE, _FIX_ONE, 0, 0]
+        else:                                                       # ROTATE_270: out[y][x] = in[height - 1 - x][y]
+            a = [0, _FIX_ONE, 0, -_FIX_ONE, 0, (height - 1) * _FIX_ONE]
+    else:
+        radians = -math.radians(angle)
+        m = [round(math.cos(radians), 15), round(math.sin(radians), 15), 0.0,
+             round(-math.sin(radians), 15), round(math.cos(radians), 15), 0.0]
+        cx, cy = width / 2, height / 2
+        m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
+        m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+        a = [_fix(m[0]), _fix(m[1]), _fix(m[2] + m[0] * 0.5 + m[1] * 0.5), _fix(m[3]), _fix(m[4]), _fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+    if flip:                                                        # after the turn: x -> canvas width - 1 - x, in integers
+        a[2], a[0] = a[2] + a[0] * (cw - 1), -a[0]
+        a[5], a[3] = a[5] + a[3] * (cw - 1), -a[3]
+    return cw, ch, tuple(a)
+
+
+def index_map(pixels, canvas_width, canvas_height, coefficients):
+    """The gather of `quarter_turn_map` on uint8 `[h, w, c]` -> `[canvas_height, canvas_width, c]`."""
+    pixels = np.asarray(pixels)
+    a0, a1, a2, a3, a4, a5 = (int(v) for v in coefficients)
+    x = np.arange(canvas_width, dtype=np.int64)[None, :]
+    y = np.arange(canvas_height, dtype=np.int64)[:, None]
+    xin, yin = (a2 + a0 * x + a1 * y) >> 16, (a5 + a3 * x + a4 * y) >> 16
+    inside = (xin >= 0) & (xin < pixels.shape[1]) & (yin >= 0) & (yin < pixels.shape[0])
+    out = pixels[np.clip(yin, 0, pixels.shape[0] - 1), np.clip(xin, 0, pixels.shape[1] - 1)]
+    out[~inside] = 0
+    return np.ascontiguousarray(out)
+
+
+def luma(pixels):
+    """`convert('L')` of uint8 RGB `[..., 3]`: (19595 R + 38470 G + 7471 B + 0x8000) >> 16."""
+    p = np.asarray(pixels).astype(np.int64)
+    return ((19595 * p[..., 0] + 38470 * p[..., 1] + 7471 * p[..., 2] + 0x8000) >> 16).astype(np.uint8)
+
+
+def blend(degenerate, pixels, factor):
+    """`Image.blend(degenerate, image, factor)` per byte, in float32: t = d + alpha * (x - d); truncated to a byte when
+    0 <= alpha <= 1, clamped to [0, 255] first otherwise (ImageEnhance's `enhance`)."""
+    alpha = np.float32(factor)
+    d = np.asarray(degenerate).astype(np.float32)
+    diff = np.asarray(pixels).astype(np.int32) - np.asarray(degenerate).astype(np.int32)
+    t = d + alpha * diff.astype(np.float32)                         # two roundings: product, then sum (no FMA)
+    if not 0.0 <= alpha <= 1.0:
+        t = np.clip(t, np.float32(0), np.float32(255))
+    return t.astype(np.uint8)
+
+
+def contrast_mean(pixels):
+    """The byte `ImageEnhance.Contrast` blends towards: int(mean of L + 0.5), the mean taken as sum / count in double."""
+    grey = luma(pixels)
+    return int(int(grey.sum(dtype=np.int64)) / grey.size + 0.5)
+
+
+def adjust_brightness(pixels, factor):
+    return blend(np.zeros_like(pixels), pixels, factor)
+
+
+def adjust_contrast(pixels, factor):
+    return blend(np.full_like(pixels, contrast_mean(pixels)), pixels, factor)
+
+
+def adjust_saturation(pixels, factor):
+    return blend(np.repeat(luma(pixels)[..., None], 3, axis=-1), pixels, factor)
+
+
+def _clip8(v):
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def rgb_to_hsv(pixels):
+    """`convert('HSV')` of uint8 RGB `[..., 3]` (Pillow's rgb2hsv_row): float32 quotients, the hue assembled in double and
+    rounded to float32, the products with 255 in double, truncated."""
+    p = np.asarray(pixels)
+    r, g, b = (p[..., k].astype(np.int32) for k in range(3))
+    maxc, minc = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    grey = maxc == minc
+    f32 = np.float32
+    cr = np.where(grey, 1, maxc - minc).astype(f32)
+    s = cr / np.where(grey, 1, maxc).astype(f32)
+    rc, gc, bc = ((maxc - c).astype(f32) / cr for c in (r, g, b))
+    rc64, gc64, bc64 = (c.astype(np.float64) for c in (rc, gc, bc))
+    h = np.where(r == maxc, bc64 - gc64, np.where(g == maxc, 2.0 + rc64 - bc64, 4.0 + gc64 - rc64)).astype(f32)
+    h = np.fmod(h.astype(np.float64) / 6.0 + 1.0, 1.0).astype(f32)
+    hue = _clip8((h.astype(np.float64) * 255.0).astype(np.int64))
+    sat = _clip8((s.astype(np.float64) * 255.0).astype(np.int64))
+    return np.stack([np.where(grey, 0, hue), np.where(grey, 0, sat), maxc], axis=-1).astype(np.uint8)
+
+
+def hsv_to_rgb(pixels):
+    """`convert('RGB')` of uint8 HSV `[..., 3]` (Pillow's hsv2rgb_row), in double."""
+    p = np.asarray(pixels)
+    h, s, v = (p[..., k].astype(np.float64) for k in range(3))
+    hh = h * 6.0 / 255.0
+    i = np.floor(hh)
+    f = hh - i
+    fs = s / 255.0
+    x = _clip8(np.rint(v * (1.0 - fs)))
+    q = _clip8(np.rint(v * (1.0 - fs * f)))
+    t = _clip8(np.rint(v * (1.0 - fs * (1.0 - f))))
+    v8 = p[..., 2]
+    sextant = i.astype(np.int64) % 6
+    r = np.choose(sextant, [v8, q, x, x, t, v8])
+    g = np.choose(sextant, [t, v8, v8, q, x, x])
+    b = np.choose(sextant, [x, x, t, v8, v8, q])
+    grey = p[..., 1] == 0
+    return np.stack([np.where(grey, v8, r), np.where(grey, v8, g), np.where(grey, v8, b)], axis=-1).astype(np.uint8)
+
+
+def hue_shift_byte(factor):
+    """The byte `_adjust_hue` adds to the hue channel."""
+    return int(factor * 255) % 256
+
+
+def adjust_hue(pixels, shift):
+    """`_adjust_hue`: RGB -> HSV, hue + `shift` (a byte, wrapping), HSV -> RGB.  Lossy even for a shift of 0."""
+    hsv = rgb_to_hsv(pixels)
+    hsv[..., 0] = (hsv[..., 0].astype(np.int32) + int(shift)) & 255
+    return hsv_to_rgb(hsv)
+
+
+def augment_pixels(pixels, aug):
+    """Resized uint8 RGB `[h, w, 3]` and one AUGMENT_DTYPE record -> the augmented canvas: turn and flip (the index map), then
+    brightness, contrast, hue, saturation, in `__getitem__`'s order."""
+    pixels = index_map(pixels, int(aug['canvas_width']), int(aug['canvas_height']), aug['map'])
+    flags = int(aug['flags'])
+    if flags & AUGMENT_BRIGHTNESS:
+        pixels = adjust_brightness(pixels, aug['brightness'])
+    if flags & AUGMENT_CONTRAST:
+        pixels = adjust_contrast(pixels, aug['contrast'])
+    if flags & AUGMENT_HUE:
+        pixels = adjust_hue(pixels, int(aug['hue']))
+    if flags & AUGMENT_SATURATION:
+        pixels = adjust_saturation(pixels, aug['saturation'])
+    return pixels
+
+
 # -- a batch of source images in one buffer -----------------------------------------------------------------------------------------
-IMAGE_DTYPE = np.dtype([('src_offset', '<u8'), ('src_width', '<i4'), ('src_height', '<i4'), ('src_pitch', '<i4'),
+AUGMENT_DTYPE = np.dtype([('canvas_width', '<i4'), ('canvas_height', '<i4'), ('map', '<i4', (6,)), ('flags', '<u4'),
+                          ('brightness', '<f4'), ('contrast', '<f4'), ('saturation', '<f4'), ('hue', 'u1'), ('pad_', 'u1', (3,))])
+                                                                    # odtk_augment_t (include/odtk_hip.h)
+IMAGE_DTYPE =np.dtype([('src_offset', '<u8'), ('src_width', '<i4'), ('src_height', '<i4'), ('src_pitch', '<i4'),
                         ('out_width', '<i4'), ('out_height', '<i4'), ('mirror', '<i4'), ('x_table', '<i4'), ('y_table', '<i4'),
                         ('x_taps', '<i4'), ('y_taps', '<i4')])      # odtk_image_t (include/odtk_hip.h)
-_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, 0, 0, 0
+_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, augments at byte (0: none), 0, 0
 _up16 = lambda n: (n + 15) // 16 * 16
 
 
@@ -206,14 +380,24 @@ class SourceBatch:
         header (8 int32) | odtk_image_t per image | the resampling tables of the batch (int32) | source pixels, 3 bytes each
     so that the source-size pixels, not the resized ones, cross shared memory and PCIe, in one upload.  `pack` writes it (inside
     a loader worker, straight into shared memory), `descriptors` / `tables` read it back, `apply_cpu` is the pipeline in numpy and
-    torch: resize, mirror, pad, normalise -- the CPU implementation of `odtk_preprocess_images`."""
+    torch: resize, mirror, pad, normalise -- the CPU implementation of `odtk_preprocess_images`.
+
+    With `device_augment=True` the geometry tuples are longer (`CocoDataset._augment_item`) and the buffer carries one
+    odtk_augment_t per image between the image descriptors and the tables (the header's sixth word says where): the index map of
+    the quarter turn and the flip, and the colour operations.  The batch is then padded to the canvases AFTER the turn, and
+    `apply_cpu` is the CPU implementation of `odtk_augment_images`."""
 
     @staticmethod
     def pack(sources, geometry, stride):
-        """sources: uint8 `[h, w, 3]` tensors; geometry: `(out_width, out_height, mirror)` per image."""
+        """sources: uint8 `[h, w, 3]` tensors; geometry: `(out_width, out_height, mirror)` per image, or (device_augment)
+        `(out_width, out_height, 0, canvas_width, canvas_height, map, flags, brightness, contrast, saturation, hue)`."""
         up = lambda d: d + (stride - d % stride) % stride
-        height = max(up(g[1]) for g in geometry)
-        width = max(up(g[0]) for g in geometry)
+        augmented = any(len(g) > 3 for g in geometry)
+        if augmented:                                               # plain images of such a batch get the identity map
+            geometry = [g if len(g) > 3 else g[:2] + (0,) + quarter_turn_map(g[0], g[1], 0, flip=g[2]) + (0, 1.0, 1.0, 1.0, 0)
+                        for g in geometry]
+        height = max(up(g[4] if augmented else g[1]) for g in geometry)
+        width = max(up(g[3] if augmented else g[0]) for g in geometry)
         tables, where, length = [], {}, 0
         def table(in_size, out_size):
             nonlocal length
@@ -226,21 +410,28 @@ class SourceBatch:
                 length += bounds.size + weights.size
             return where[(in_size, out_size)]
         images = np.zeros(len(sources), dtype=IMAGE_DTYPE)
-        for im, p, (ow, oh, mirror) in zip(images, sources, geometry):
+        for im, p, (ow, oh, mirror) in zip(images, sources, (g[:3] for g in geometry)):
             h, w = p.shape[:2]
             im['src_width'], im['src_height'], im['src_pitch'] = w, h, 3 * w
             im['out_width'], im['out_height'], im['mirror'] = ow, oh, int(bool(mirror))
             im['x_table'], im['x_taps'] = table(w, ow)
             im['y_table'], im['y_taps'] = table(h, oh)
-        tables_at = _up16(4 * _HEADER_WORDS + images.nbytes)
+        augments = np.zeros(len(sources) if augmented else 0, dtype=AUGMENT_DTYPE)
+        for aug, g in zip(augments, geometry):
+            aug['canvas_width'], aug['canvas_height'], aug['map'], aug['flags'] = g[3], g[4], g[5], g[6]
+            aug['brightness'], aug['contrast'], aug['saturation'], aug['hue'] = g[7], g[8], g[9], g[10]
+        augments_at = _up16(4 * _HEADER_WORDS + images.nbytes) if augmented else 0
+        tables_at = _up16(max(augments_at, 4 * _HEADER_WORDS + images.nbytes) + augments.nbytes)
         at = _up16(tables_at + 4 * length)
         for im in images:
             im['src_offset'] = at
             at = _up16(at + int(im['src_pitch']) * int(im['src_height']))
         buffer = _batch_buffer((at,))
         view = buffer.numpy()
-        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, 0, 0, 0)
+        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, augments_at, 0, 0)
         view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + images.nbytes] = images.view(np.uint8)
+        if augmented:
+            view[augments_at:augments_at + augments.nbytes] = augments.view(np.uint8)
         if tables:
             view[tables_at:tables_at + 4 * length].view(np.int32)[:] = np.concatenate(tables)
         for im, p in zip(images, sources):
@@ -253,8 +444,11 @@ class SourceBatch:
         self.buffer = buffer
         self.view = buffer.numpy()
         header = self.view[:4 * _HEADER_WORDS].view(np.int32)
-        self.batch, self.height, self.width, self.tables_at, self.tables_len = (int(v) for v in header[:5])
+        self.batch, self.height, self.width, self.tables_at, self.tables_len, augments_at = (int(v) for v in header[:6])
         self.images = self.view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + self.batch * IMAGE_DTYPE.itemsize].view(IMAGE_DTYPE)
+        self.augments = None                                        # one AUGMENT_DTYPE record per image with `device_augment`
+        if augments_at:
+            self.augments = self.view[augments_at:augments_at + self.batch * AUGMENT_DTYPE.itemsize].view(AUGMENT_DTYPE)
 
     def tables(self, buffer=None):
         """The int32 tables as a view of `buffer` (default: the host copy; pass the uploaded one for the device's view)."""
@@ -267,7 +461,8 @@ class SourceBatch:
         return self.view[start:start + 3 * w * h].reshape(h, w, 3)
 
     def apply_cpu(self, table, dtype=torch.float32):
-        """-> `[B, 3, H, W]` `dtype`, channels_last storage: what `odtk_preprocess_images` writes, computed on the host."""
+        """-> `[B, 3, H, W]` `dtype`, channels_last storage: what `odtk_preprocess_images` (with augment descriptors:
+        `odtk_augment_images`) writes, computed on the host."""
         table = table.to(device='cpu', dtype=dtype).reshape(-1)
         out = torch.zeros((self.batch, self.height, self.width, 3), dtype=dtype)
         channel = torch.tensor([0, 256, 512])
@@ -275,6 +470,8 @@ class SourceBatch:
             pixels = resize_bilinear(self.source(k), (int(im['out_width']), int(im['out_height'])))
             if im['mirror']:
                 pixels = pixels[:, ::-1].copy()
+            if self.augments is not None:
+                pixels = augment_pixels(pixels, self.augments[k])
             out[k, :pixels.shape[0], :pixels.shape[1]] = table[torch.from_numpy(pixels).long() + channel]
         return out.permute(0, 3, 1, 2)
 
@@ -297,14 +494,18 @@ class CocoDataset(data.dataset.Dataset):
     padding are done per BATCH (see the module docstring); everything else follows reference data.py:13-181.
 
     The random decisions of training are drawn from `random` in the reference's order (resize jitter,
-    quarter-turn, flip, brightness, contrast, hue, saturation), so a seeded run makes the same choices."""
+    quarter-turn, flip, brightness, contrast, hue, saturation), so a seeded run makes the same choices.
+
+    `device_resize=True`: items are source pixels and the target geometry (`_source_item`); it refuses the quarter turns and the
+    colour options.  `device_augment=True`: the same hand-over, and those five travel as descriptors (`_augment_item`)."""
 
     box_fields = 4
 
     def __init__(self, path, resize, max_size, stride, annotations=None, training=False, rotate_augment=False,
-                 augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, device_resize=False):
+                 augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, device_resize=False,
+                 device_augment=False):
         super().__init__()
-        if device_resize:
+        if device_resize and not device_augment:
             # quarter turns and the colour augmentations act on the RESIZED PIL image in the reference: they stay on the host path
             for name, value in (('rotate_augment', rotate_augment), ('augment_brightness', augment_brightness),
                                 ('augment_contrast', augment_contrast), ('augment_hue', augment_hue),
@@ -312,7 +513,8 @@ class CocoDataset(data.dataset.Dataset):
                 if value:
                     raise ValueError('device_resize=True cannot be combined with %s=%r: that augmentation works on the resized '
                                      'image on the host (use the default loader)' % (name, value))
-        self.device_resize = device_resize
+        # device_augment: the source-pixel hand-over of device_resize, and the five augmentations travel as descriptors
+        self.device_resize, self.device_augment = bool(device_resize or device_augment), bool(device_augment)
         self.path = os.path.expanduser(path)
         self.resize, self.max_size, self.stride = resize, max_size, stride
         self.mean, self.std = list(MEAN), list(STD)
@@ -348,9 +550,13 @@ class CocoDataset(data.dataset.Dataset):
     def _quarter_turn(self, im, boxes, angle):
         """Rotate the image by `angle` in {90, 180, 270} on its own canvas and move the boxes with it
         (reference data.py:68-85)."""
-        im = im.rotate(angle)
+        return im.rotate(angle), self._turn_boxes(boxes, angle, *im.size)
+
+    turn_expands = False                                                # `Image.rotate(angle, expand=...)` of `_quarter_turn`
+
+    def _turn_boxes(self, boxes, angle, width, height):
+        """The boxes' half of `_quarter_turn`; `width`, `height`: the image BEFORE the turn."""
         x, y, w, h = (boxes[:, k].clone() for k in range(4))
-        width, height = im.size
         if angle == 90:
             boxes[:, 0] = y - height / 2 + width / 2
             boxes[:, 1] = width / 2 + height / 2 - x - w
@@ -362,7 +568,7 @@ class CocoDataset(data.dataset.Dataset):
             boxes[:, 0] = width / 2 + height / 2 - y - h
             boxes[:, 1] = x - width / 2 + height / 2
             boxes[:, 2], boxes[:, 3] = h, w
-        return im, boxes
+        return boxes
 
     def _flip(self, im, boxes):
         im = im.transpose(Image.FLIP_LEFT_RIGHT)
@@ -400,8 +606,40 @@ class CocoDataset(data.dataset.Dataset):
             boxes = self._flip_boxes(boxes, size[0])
         return pixels, size + (mirror,), torch.cat([boxes, categories], dim=1)
 
+    def _augment_item(self, image_id):
+        """The training item of `device_augment=True`: `(source pixels, (out_width, out_height, 0, canvas_width, canvas_height, map,
+        flags, brightness, contrast, saturation, hue), target)`.  Every draw from `random` happens here, in the host path's order
+        (jitter, quarter turn, flip, brightness, contrast, hue, saturation) and with `_colour`'s clamps; the turn and the flip
+        become the index map of `quarter_turn_map`, the colour operations flags and factors -- the pixels are untouched."""
+        im, ratio, size = self._open(image_id)
+        pixels = torch.from_numpy(np.array(im, dtype=np.uint8))
+        boxes, categories = self._get_target(image_id)
+        boxes[:, :4] *= ratio
+        angle = random.randint(0, 3) * 90
+        if self.rotate_augment and angle != 0:
+            boxes = self._turn_boxes(boxes, angle, *size)
+        else:
+            angle = 0
+        mirror = random.randint(0, 1)
+        cw, ch, coefficients = quarter_turn_map(size[0], size[1], angle, self.turn_expands, mirror)
+        if mirror:
+            boxes = self._flip_boxes(boxes, cw)
+        flags, brightness, contrast, saturation, hue = 0, 1.0, 1.0, 1.0, 0
+        if self.augment_brightness:
+            flags, brightness = flags | AUGMENT_BRIGHTNESS, max(0, random.normalvariate(1, self.augment_brightness))
+        if self.augment_contrast:
+            flags, contrast = flags | AUGMENT_CONTRAST, max(0, random.normalvariate(1, self.augment_contrast))
+        if self.augment_hue:
+            flags, hue = flags | AUGMENT_HUE, hue_shift_byte(min(0.5, max(-0.5, random.normalvariate(0, self.augment_hue))))
+        if self.augment_saturation:
+            flags, saturation = flags | AUGMENT_SATURATION, max(0, random.normalvariate(1, self.augment_saturation))
+        geometry = size + (0, cw, ch, coefficients, flags, brightness, contrast, saturation, hue)
+        return pixels, geometry, torch.cat([boxes, categories], dim=1)
+
     def __getitem__(self, index):
         image_id = self.ids[index]
+        if self.device_augment and self.training:
+            return self._augment_item(image_id)
         if self.device_resize:
             return self._source_item(image_id)
         im, ratio = self._open_resized(image_id)
@@ -493,9 +731,12 @@ class RotatedCocoDataset(CocoDataset):
         assert len(box) == 5, 'Bounding box for id %i does not contain five entries.' % image_id
         return box
 
+    turn_expands = True
+
     def _quarter_turn(self, im, boxes, angle):
-        width, height = im.size                                            # before the turn
-        im = im.rotate(angle, expand=True)
+        return im.rotate(angle, expand=True), self._turn_boxes(boxes, angle, *im.size)
+
+    def _turn_boxes(self, boxes, angle, width, height):
         x, y, w, h, t = (boxes[:, k].clone() for k in range(5))
         if angle == 90:
             boxes[:, 0], boxes[:, 1] = y, width - x - w
@@ -509,7 +750,7 @@ class RotatedCocoDataset(CocoDataset):
             t = t + math.radians(angle)
             t = torch.remainder(torch.abs(t), math.pi) * torch.sign(t)
         boxes[:, 4] = t
-        return im, boxes
+        return boxes
 
     def _flip_boxes(self, boxes, width):
         boxes = super()._flip_boxes(boxes, width)
@@ -528,11 +769,13 @@ class DataIterator:
     def __init__(self, path, resize, max_size, batch_size, stride, world, annotations, training=False,
                  rotate_augment=False, augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0,
                  augment_saturation=0.0, device=None, dtype=torch.float32, num_workers=2, rank=None, device_resize=False,
-                 **dataset_args):
+                 device_augment=False, **dataset_args):
         self.resize, self.max_size = resize, max_size
-        self.device_resize = device_resize
+        self.device_resize, self.device_augment = bool(device_resize or device_augment), bool(device_augment)
         if device_resize:
             dataset_args = dict(dataset_args, device_resize=True)
+        if device_augment:
+            dataset_args = dict(dataset_args, device_augment=True)
         self.dataset = self.dataset_class(path, resize=resize, max_size=max_size, stride=stride,
                                           annotations=annotations, training=training, rotate_augment=rotate_augment,
                                           augment_brightness=augment_brightness, augment_contrast=augment_contrast,
@@ -560,13 +803,15 @@ class DataIterator:
         lines = ['    loader: pytorch', '    resize: {}, max: {}'.format(self.resize, self.max_size)]
         if self.device_resize:
             lines.append('    resize on: {}'.format('the device (odtk_preprocess_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
+        if self.device_augment:
+            lines.append('    augmentations on: {}'.format('the device (odtk_augment_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
         return '\n'.join(lines)
 
     def __len__(self):
         return len(self.dataloader)
 
     def _preprocess(self, packed):
-        """`device_resize=True`: the batch from a `SourceBatch` buffer -- one upload and one HIP launch on a GPU (the descriptors
+        """`device_resize=True` / `device_augment=True`: the batch from a `SourceBatch` buffer -- one upload and one HIP launch on a GPU (the descriptors
         are read from the host copy: they are kernel arguments), the same arithmetic in numpy on the CPU."""
         batch = SourceBatch(packed)
         if self.device.type != 'cuda':
@@ -574,6 +819,9 @@ class DataIterator:
         from . import _C
         uploaded = packed.to(self.device, non_blocking=True)
         images = (_C.Image * batch.batch).from_buffer_copy(batch.images.tobytes())
+        if batch.augments is not None:                              # resize to bytes, (sum of L,) gather + colour chain + table + pad
+            augments = (_C.Augment * batch.batch).from_buffer_copy(batch.augments.tobytes())
+            return _C.augment_images(uploaded, images, augments, batch.tables(uploaded), self.table, batch.height, batch.width)
         return _C.preprocess_images(uploaded, images, batch.tables(uploaded), self.table, batch.height, batch.width)
 
     def __iter__(self):

@@ -13,6 +13,8 @@ What differs from the reference, and why:
     dependencies the north star drops; they are accepted by the parser and refused with a clear error.
   * `--device-resize` (train, infer) is new: what DALI did for the reference -- resize, flip, pad, normalise on the GPU -- as one
     HIP launch per batch (odtk/data.py), bit-identical to the default loader.
+  * `--device-augment` (train) is new as well: `--device-resize` plus the training augmentations (`--augment-rotate` and the four
+    colour options) on the GPU, as a short chain of HIP launches per batch, bit-identical to Pillow on the host.
 """
 import argparse
 import os
@@ -72,6 +74,8 @@ TRAIN_FLAGS = [
     _flag('--logdir', str, None, 'directory for scalar logs', metavar='logdir'),
     _flag('--val-iters', int, 8000, 'iterations between two validations', metavar='number'),
     *_COMMON,
+    _flag('--device-augment', bool, text='--device-resize, and the quarter turns and colour augmentations run on the device as '
+          'well, bit-identical to the host loader', default=argparse.SUPPRESS),
     _flag('--augment-rotate', bool, text='random quarter turns'),
     _flag('--augment-free-rotate', float, [0, 0], 'accepted for compatibility (unused by the reference as well)', nargs=2,
           metavar='value value'),
@@ -187,7 +191,8 @@ def worker(rank, args, world, spawned=False):
                                augment_contrast=args.augment_contrast, augment_hue=args.augment_hue,
                                augment_saturation=args.augment_saturation, regularization_l2=args.regularization_l2,
                                rotated_bbox=args.rotated_bbox, absolute_angle=args.absolute_angle,
-                               num_workers=args.workers, device_resize=getattr(args, 'device_resize', False))
+                               num_workers=args.workers, device_resize=getattr(args, 'device_resize', False),
+                               device_augment=getattr(args, 'device_augment', False))
         if args.command == 'infer':
             return infer.infer(model, args.images, args.output, args.resize, args.max_size, args.batch,
                                annotations=args.annotations, mixed_precision=not args.full_precision,

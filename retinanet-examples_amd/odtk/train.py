@@ -253,13 +253,14 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
           val_iterations, lr, warmup, milestones, gamma, rank=0, world=1, mixed_precision=True, with_apex=False,
           use_dali=False, verbose=True, metrics_url=None, logdir=None, rotate_augment=False, augment_brightness=0.0,
           augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, regularization_l2=0.0001, rotated_bbox=False,
-          absolute_angle=False, num_workers=2, device=None, device_resize=False):
+          absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False):
     """Train `model` on the images under `path` -- the reference's `train.train` (train.py:18-214), same
     arguments: COCO-style annotations through odtk/data.py (`jitter` = the range of short-side sizes),
     `train_batches` above, periodic validation through `infer.infer`, checkpoints to `state['path']`, scalars
     to `logdir`, metrics to `metrics_url`.  `with_apex` / `use_dali` are errors (dropped dependencies).  `device_resize`: resize,
     flip, padding and normalisation of the images run on the device (odtk/data.py), for training and validation alike; it excludes
-    `rotate_augment` and the colour augmentations (ValueError)."""
+    `rotate_augment` and the colour augmentations (ValueError).  `device_augment`: `device_resize`, and those augmentations run on the
+    device as well (odtk_augment_images), bit-identical to the host loader."""
     from . import infer as infer_module
     from .data import DataIterator, RotatedDataIterator
     if use_dali or with_apex:
@@ -273,7 +274,7 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
         path, jitter, max_size, batch_size, model.stride, world, annotations, training=True,
         rotate_augment=rotate_augment, augment_brightness=augment_brightness, augment_contrast=augment_contrast,
         augment_hue=augment_hue, augment_saturation=augment_saturation, device=device, num_workers=num_workers, device_resize=device_resize,
-        **extra)
+        device_augment=device_augment, **extra)
     if verbose:
         print(data_iterator)
         print('    device: {} {}'.format(world, 'cpu' if device.type == 'cpu' else 'GPU' if world == 1 else 'GPUs'))
@@ -297,7 +298,7 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
         stats = infer_module.infer(net, val_path, None, resize, max_size, batch_size, annotations=val_annotations,
                                    mixed_precision=mixed_precision, is_master=is_master, world=world,
                                    is_validation=True, verbose=False, rotated_bbox=rotated_bbox, num_workers=num_workers,
-                                   device_resize=device_resize)
+                                   device_resize=device_resize or device_augment)
         validate.last = stats
         if log is not None and stats is not None and not isinstance(stats, int):
             for tag, value in zip(VALIDATION_TAGS, stats):

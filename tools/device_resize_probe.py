@@ -6,7 +6,12 @@ device stage it replaces: `normalise_batch` on the already resized [8, 896, 1152
 does strictly less work: no resize).  Event-timed back to back; under `rocprofv3 --kernel-trace --stats` the same launches show
 up as preprocess_images_kernel<2> / <4>.
 
-  python tools/device_resize_probe.py [--iters 200] [--batch 8] [--source 640x480]"""
+`--augment` times the augmentation chain instead (odtk_augment_images, csrc/augment.hpp: resize to bytes, sum of L, gather + colour
+chain + table + pad) on the same batch, with all five options on, next to the plain launch and to its own bound (source read, the
+byte image written once and read twice, the output written).  It runs the chain with every image unturned, every image turned by
+90 degrees (expand: the gather walks columns of the byte image) and with the loader's mix of turns.
+
+  python tools/device_resize_probe.py [--iters 200] [--batch 8] [--source 640x480] [--augment]"""
 import argparse
 import os
 import sys
@@ -35,11 +40,45 @@ def timed(fn, iters):
     return start.elapsed_time(stop) * 1e3 / iters                   # us per call
 
 
+def augment_probe(args, sources, ow, oh):
+    colour = (15, 1.1, 0.9, 1.2, 5)
+    plain = D.SourceBatch(D.SourceBatch.pack(sources, [(ow, oh, k % 2) for k in range(args.batch)], 128))
+    plain_up = plain.buffer.cuda()
+    plain_images = (_C.Image * plain.batch).from_buffer_copy(plain.images.tobytes())
+    turns = {'no turn': lambda k: 0, 'all 90 degrees': lambda k: 90, 'mixed turns': lambda k: 90 * (k % 4)}
+    for dtype in (torch.bfloat16, torch.float32):
+        table = D.normalisation_table(dtype).cuda()
+        us_plain = timed(lambda: _C.preprocess_images(plain_up, plain_images, plain.tables(plain_up), table, plain.height, plain.width), args.iters)
+        print('%-8s preprocess_images (no augmentation) %.1f us per batch [%d, 3, %d, %d]' % (str(dtype).replace('torch.', ''), us_plain,
+                                                                                             plain.batch, plain.height, plain.width))
+        for colours, label in ((colour, 'five options'), ((0, 1.0, 1.0, 1.0, 0), 'turn and flip only')):
+            for name, angle in turns.items():
+                geometry = [(ow, oh, 0) + D.quarter_turn_map(ow, oh, angle(k), True, k % 2) + colours for k in range(args.batch)]
+                batch = D.SourceBatch(D.SourceBatch.pack(sources, geometry, 128))
+                uploaded = batch.buffer.cuda()
+                images = (_C.Image * batch.batch).from_buffer_copy(batch.images.tobytes())
+                augments = (_C.Augment * batch.batch).from_buffer_copy(batch.augments.tobytes())
+                run = lambda: _C.augment_images(uploaded, images, augments, batch.tables(uploaded), table, batch.height, batch.width)
+                out = run()
+                if name == 'no turn' and not colours[0]:
+                    assert torch.equal(out, _C.preprocess_images(plain_up, plain_images, plain.tables(plain_up), table, plain.height, plain.width))
+                us = timed(run, args.iters)
+                resized = 3 * ow * oh * args.batch
+                moved = (sum(s.numel() for s in sources) + 4 * batch.tables_len + resized * (3 if colours[0] else 2) +
+                         out.numel() * out.element_size() + table.numel() * table.element_size())
+                bound = moved / HBM_PEAK * 1e6
+                print('%-8s augment_images, %-18s %-14s [%d, 3, %d, %d]: %.1f us per batch (events, back to back, %d calls); algorithmic '
+                      'bytes %d -> bound %.1f us at 8 TB/s (%.1f %% of that rate); %.2fx the plain launch'
+                      % (str(dtype).replace('torch.', ''), label + ',', name, batch.batch, batch.height, batch.width, us, args.iters, moved,
+                         bound, 100 * bound / us, us / us_plain))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--source', default='640x480')
+    ap.add_argument('--augment', action='store_true', help='time the augmentation chain (odtk_augment_images)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU: a timing from anywhere else says nothing'
     sw, sh = (int(v) for v in args.source.split('x'))
@@ -49,6 +88,8 @@ def main():
     ow, oh = int(ratio * sw), int(ratio * sh)
     rng = np.random.default_rng(0)
     sources = [torch.from_numpy(rng.integers(0, 256, (sh, sw, 3), dtype=np.uint8)) for _ in range(args.batch)]
+    if args.augment:
+        return augment_probe(args, sources, ow, oh)
     buffer = D.SourceBatch.pack(sources, [(ow, oh, k % 2) for k in range(args.batch)], 128)
     batch = D.SourceBatch(buffer)
     uploaded = buffer.cuda()

@@ -8,7 +8,12 @@ pads and normalises).
 PROBE_REPEAT lists every file that many times (a longer pass without writing more files): the steady rate is taken over the SECOND
 HALF of the pass, which must be well beyond what the workers prefetch (2 batches each) while the main process waits for the first
 batch.  PROBE_SIZE is the size of the JPEGs.  At the default, resize=800 / max_size=1333 asks for the size the images already have and
-Pillow returns a copy: the resize is NOT in the host path's figures.  PROBE_SIZE=640x480 (COCO's usual size, -> 1066x800) makes it real."""
+Pillow returns a copy: the resize is NOT in the host path's figures.  PROBE_SIZE=640x480 (COCO's usual size, -> 1066x800) makes it real.
+
+  python tools/loader_probe.py --augment
+the same for TRAINING items with all five augmentations on (quarter turns, brightness, contrast, hue, saturation): the host path
+(workers resize, turn and enhance with Pillow) against device_augment=True (workers ship source pixels and descriptors, the chain
+of odtk_augment_images does the rest)."""
 import json
 import os
 import sys
@@ -26,6 +31,9 @@ from odtk.data import CocoDataset, DataIterator, normalise_batch
 N = int(os.environ.get('PROBE_IMAGES', 192))
 REPEAT = int(os.environ.get('PROBE_REPEAT', 1))
 WIDTH, HEIGHT = (int(v) for v in os.environ.get('PROBE_SIZE', '1280x800').split('x'))
+AUGMENT = '--augment' in sys.argv[1:]
+OPTIONS = dict(training=True, rotate_augment=True, augment_brightness=0.002, augment_contrast=0.002, augment_hue=0.0002,
+               augment_saturation=0.002) if AUGMENT else {}                # the sigmas are `odtk train`'s defaults
 MODES = os.environ.get('PROBE_MODES', 'host,device').split(',')
 scratch = tempfile.mkdtemp(prefix='odtk_probe_')
 yy, xx = np.mgrid[0:HEIGHT, 0:WIDTH]
@@ -44,11 +52,16 @@ print('host cores', os.cpu_count(), 'images', N * REPEAT, '(%d files)' % N, 'of 
 
 for mode in MODES:
     device_resize = mode == 'device'
-    print('--- %s' % ('device_resize=True: workers ship source pixels' if device_resize else 'host path: workers resize with Pillow'))
-    ds = CocoDataset(scratch, 800, 1333, 128, ann, device_resize=device_resize)
+    switch = {'device_augment' if AUGMENT else 'device_resize': device_resize}
+    if AUGMENT:
+        print('--- training items, five augmentations on: %s' % ('device_augment=True: workers ship source pixels and descriptors' if device_resize
+                                                                 else 'host path: workers resize, turn and enhance with Pillow'))
+    else:
+        print('--- %s' % ('device_resize=True: workers ship source pixels' if device_resize else 'host path: workers resize with Pillow'))
+    ds = CocoDataset(scratch, 800, 1333, 128, ann, **switch, **OPTIONS)
     t = time.time(); items = [ds[i] for i in range(16)]; per_item = (time.time() - t) / 16
     t = time.time(); packed = [ds.collate_fn(items[:8]) for _ in range(4)][0][0]; per_collate = (time.time() - t) / 4
-    it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, training=False, num_workers=0, device_resize=device_resize)
+    it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, **dict(dict(training=False, num_workers=0, **switch), **OPTIONS))
     pinned = packed.pin_memory() if cuda else packed
     stage = (lambda: it._preprocess(pinned)) if device_resize else (lambda: normalise_batch(pinned.to(it.device, non_blocking=True), it.table))
     out = stage()
@@ -57,14 +70,14 @@ for mode in MODES:
         out = stage()
     sync(); per_stage = (time.time() - t) / 10
     print('main process: item (decode%s + to uint8) %.1f ms, collate of 8 %.1f ms, upload (pinned) + device stage of 8 %.2f ms -> %s'
-          % ('' if device_resize else ' + resize', per_item * 1e3, per_collate * 1e3, per_stage * 1e3, tuple(out.shape)))
+          % ('' if device_resize else ' + resize + augmentations' if AUGMENT else ' + resize', per_item * 1e3, per_collate * 1e3, per_stage * 1e3, tuple(out.shape)))
     print('bytes per batch of 8 through shared memory and PCIe: %d (%.2f MB)' % (packed.numel(), packed.numel() / 1e6))
 
     for workers in [int(w) for w in os.environ.get('PROBE_WORKERS', '0,4,16,32').split(',')]:
-        it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, training=False, num_workers=workers, device_resize=device_resize)
+        it = DataIterator(scratch, 800, 1333, 8, 128, 1, ann, **dict(dict(training=False, num_workers=workers, **switch), **OPTIONS))
         t0 = time.time()
         stamps = []
-        for data, ids, ratios in it:
+        for data, *_ in it:
             if not stamps:
                 sync()
             stamps.append(time.time() - t0)
@@ -73,3 +86,4 @@ for mode in MODES:
         half = len(stamps) // 2
         print('%2d workers: first batch after %.2f s; second half of the pass %.1f img/s; whole pass %.1f img/s'
               % (workers, stamps[0], 8 * (len(stamps) - half) / max(total - stamps[half - 1], 1e-9), 8 * len(stamps) / total))
+        del it                                                      # (training keeps its workers: let them go before the next count)
