@@ -202,6 +202,25 @@ int odtk_nms_sorted_runs(int batch_size, const void *const *inputs, void *const 
                          void *workspace, size_t workspace_size, void *stream);
 
 /*
+ * odtk_soft_nms -- class-aware Soft-NMS (Bodla et al. 2017) on axis-aligned boxes; no reference equivalent.  Inputs, outputs
+ * and the optional 4th int32 output as for odtk_nms_ex.  Per image, in float32: w = scores, a candidate is alive iff w > 0; at
+ * most detections_per_im times the alive candidate with the largest w (ties: lowest position) is emitted with its CURRENT w
+ * and retired, and every alive candidate j of its class is decayed with the IoU of odtk_nms (+1 pixel convention):
+ *   ODTK_SOFT_NMS_LINEAR    if !(iou <= nms_thresh)  w_j *= 1 - iou
+ *   ODTK_SOFT_NMS_GAUSSIAN  w_j *= exp((-(iou * iou)) / sigma)     (correctly rounded exp; nms_thresh is not used)
+ * and stays alive iff w_j >= min_score.  Emitted scores are non-increasing; unused slots are zero (index -1).
+ * sigma and min_score must be finite and > 0, method one of the two above: otherwise ODTK_ERR_INVALID, as for any undefined
+ * flag bit.  ODTK_FLAG_ROTATED and count > ODTK_MAX_NMS_COUNT (the candidates of an image live in the registers and the LDS of
+ * one workgroup; csrc/soft_nms.hpp) are ODTK_ERR_UNSUPPORTED.  Workspace: two-phase query as everywhere; a token size.
+ * One launch, timed under ODTK_KERNEL_NMS.
+ */
+#define ODTK_SOFT_NMS_LINEAR   1
+#define ODTK_SOFT_NMS_GAUSSIAN 2
+int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs,
+                  size_t count, int detections_per_im, float nms_thresh, int method, float sigma, float min_score,
+                  uint32_t flags, void *workspace, size_t workspace_size, void *stream);
+
+/*
  * odtk_detect -- decode_levels + nms back to back on one stream (the whole post-processing of
  * odtk/model.py:153-165 in 3 launches).  outputs as odtk_nms; workspace holds the candidates.
  */

@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue).  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue) and `soft_nms`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -114,6 +114,34 @@ std::vector<torch::Tensor> nms(torch::Tensor scores, torch::Tensor boxes, torch:
   return {out_scores, out_boxes, out_classes};
 }
 
+// Soft-NMS (odtk_soft_nms: no reference equivalent), the signature of odtk/_C.py:soft_nms
+std::vector<torch::Tensor> soft_nms(torch::Tensor scores, torch::Tensor boxes, torch::Tensor classes, float nms_thresh,
+                                    int detections_per_im, int method, float sigma, float min_score, bool return_indices) {
+  require_gpu_contiguous(scores, "scores");
+  require_gpu_contiguous(boxes, "boxes");
+  require_gpu_contiguous(classes, "classes");
+  TORCH_CHECK(scores.dim() == 2 && boxes.dim() == 3 && boxes.size(2) == 4 && boxes.size(0) == scores.size(0) &&
+              boxes.size(1) == scores.size(1) && classes.sizes() == scores.sizes(), "soft_nms: inconsistent shapes");
+  const int64_t batch = scores.size(0), count = scores.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+  auto opt = scores.options();
+  std::vector<torch::Tensor> result = {torch::empty({batch, detections_per_im}, opt), torch::empty({batch, detections_per_im, 4}, opt),
+                                       torch::empty({batch, detections_per_im}, opt)};
+  if (return_indices) result.push_back(torch::empty({batch, detections_per_im}, opt.dtype(torch::kInt32)));
+  const void *in[3] = {scores.data_ptr(), boxes.data_ptr(), classes.data_ptr()};
+  void *out[4] = {result[0].data_ptr(), result[1].data_ptr(), result[2].data_ptr(), return_indices ? result[3].data_ptr() : nullptr};
+  const int n_out = return_indices ? 4 : 3;
+  void *stream = current_stream(scores);
+  {
+    pybind11::gil_scoped_release nogil;
+    with_scratch(scores, "soft_nms", [&](void *ws, size_t size) {
+      return odtk_soft_nms(static_cast<int>(batch), ws ? in : nullptr, ws ? out : nullptr, n_out, static_cast<size_t>(count),
+                           detections_per_im, nms_thresh, method, sigma, min_score, 0u, ws, size, ws ? stream : nullptr);
+    });
+  }
+  return result;
+}
+
 std::vector<torch::Tensor> iou(torch::Tensor boxes, torch::Tensor anchors) {
   require_gpu_contiguous(boxes, "boxes");
   require_gpu_contiguous(anchors, "anchors");
@@ -201,6 +229,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("top_n"), py::arg("rotated") = false);
   m.def("nms", &nms, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("nms_thresh"), py::arg("detections_per_im"),
         py::arg("rotated") = false);
+  m.def("soft_nms", &soft_nms, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("nms_thresh"),
+        py::arg("detections_per_im"), py::arg("method"), py::arg("sigma"), py::arg("min_score"), py::arg("return_indices") = false);
   m.def("iou", &iou, py::arg("boxes"), py::arg("anchors"));
   m.def("detect", &detect, py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors"), py::arg("strides"), py::arg("score_thresh"),
         py::arg("top_n"), py::arg("nms_thresh"), py::arg("detections_per_im"), py::arg("rotated") = false, py::arg("logits") = false);

@@ -21,6 +21,7 @@
 #include "epilogue.hpp"
 #include "iou.hpp"
 #include "nms.hpp"
+#include "soft_nms.hpp"
 #include "prefilter.hpp"
 #include "select_decode.hpp"
 #include "targets.hpp"
@@ -535,6 +536,18 @@ int nms_impl(int batch, const void *const *inputs, void *const *outputs, int n_o
   return global_keys ? nms_launch<4, true>(na, batch, lds, stream) : nms_launch<4, false>(na, batch, lds, stream);
 }
 
+// Soft-NMS (csrc/soft_nms.hpp): one workgroup per image, boxes and classes in count x 20 bytes of dynamic LDS
+template <bool kGaussian>
+int soft_nms_launch(const odtk::SoftNmsArgs &sa, int batch, hipStream_t stream) {
+  const size_t lds = odtk::soft_nms_lds_bytes(sa.count);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(&odtk::soft_nms_kernel<kGaussian>), odtk::soft_nms_lds_bytes(ODTK_MAX_NMS_COUNT),
+                                   "hipFuncSetAttribute(soft_nms_kernel)");
+  if (rc != ODTK_OK) return rc;
+  timed_launch(ODTK_KERNEL_NMS, odtk::soft_nms_kernel<kGaussian>, dim3(batch), dim3(odtk::kSoftThreads), lds, stream, sa);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
 template <typename T, bool kRes, bool kRelu>
 int bias_act_launch(void *y, const float *bias, const void *res, uint64_t n, uint32_t channels, hipStream_t stream) {
   constexpr int per = T::kPerLoad;
@@ -905,6 +918,41 @@ int odtk_nms_sorted_runs(int batch_size, const void *const *inputs, void *const 
   if (workspace && workspace_size && !run_valid) return ODTK_ERR_INVALID;
   return nms_impl(batch_size, inputs, outputs, n_outputs, count, detections_per_im, nms_thresh, flags, workspace, workspace_size,
                   static_cast<hipStream_t>(stream), static_cast<uint32_t>(run_len), run_valid);
+}
+
+// everything is validated here, on the host, before anything touches the device
+int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                  int detections_per_im, float nms_thresh, int method, float sigma, float min_score, uint32_t flags,
+                  void *workspace, size_t workspace_size, void *stream) {
+  if (batch_size <= 0 || count == 0 || detections_per_im <= 0 || detections_per_im > ODTK_MAX_NMS_DETECTIONS) return ODTK_ERR_INVALID;
+  if (method != ODTK_SOFT_NMS_LINEAR && method != ODTK_SOFT_NMS_GAUSSIAN) return ODTK_ERR_INVALID;
+  if (!std::isfinite(sigma) || !(sigma > 0.0f) || !std::isfinite(min_score) || !(min_score > 0.0f)) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  if (count > ODTK_MAX_NMS_COUNT) return ODTK_ERR_UNSUPPORTED;
+  // nothing lives in global scratch: a token size keeps the two-phase calling convention
+  const size_t need = kAlign;
+  if (!workspace || !workspace_size) return static_cast<int>(need);
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!inputs || !outputs || n_outputs < 3) return ODTK_ERR_INVALID;
+  for (int i = 0; i < 3; ++i)
+    if (!inputs[i] || !outputs[i]) return ODTK_ERR_INVALID;
+  odtk::SoftNmsArgs sa;
+  std::memset(&sa, 0, sizeof sa);
+  sa.scores = static_cast<const float *>(inputs[0]);
+  sa.boxes = static_cast<const float *>(inputs[1]);
+  sa.classes = static_cast<const float *>(inputs[2]);
+  sa.out_scores = static_cast<float *>(outputs[0]);
+  sa.out_boxes = static_cast<float *>(outputs[1]);
+  sa.out_classes = static_cast<float *>(outputs[2]);
+  sa.out_indices = n_outputs > 3 ? static_cast<int32_t *>(outputs[3]) : nullptr;
+  sa.count = static_cast<uint32_t>(count);
+  sa.ndet = detections_per_im;
+  sa.thresh = nms_thresh;
+  sa.sigma = sigma;
+  sa.min_score = min_score;
+  return method == ODTK_SOFT_NMS_GAUSSIAN ? soft_nms_launch<true>(sa, batch_size, static_cast<hipStream_t>(stream))
+                                          : soft_nms_launch<false>(sa, batch_size, static_cast<hipStream_t>(stream));
 }
 
 int odtk_iou(const void *const *inputs, void *const *outputs, int num_boxes, int num_anchors, void *stream) {

@@ -10,7 +10,7 @@ conventions, so `from ._C import decode, nms, iou` in a box.py keeps working:
     Engine                                                                        -> placeholder (TensorRT dropped)
 
 plus the MI355X-first batched forms (`decode_levels`, `detect`) that cover all pyramid levels of
-the whole batch in one enqueue.
+the whole batch in one enqueue, and `soft_nms` (linear / Gaussian Soft-NMS: no reference equivalent).
 
 There is NO CPU fallback: tensors must live on the GPU and the shared library must be present
 (build it with `python __graft_entry__.py` or `make -C retinanet-examples_amd/csrc`); anything
@@ -29,6 +29,7 @@ OK, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
 FLAG_ROTATED, FLAG_LOGITS, FLAG_ROTATED_NMS_FIXED_ANGLE = 1, 2, 4
 MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32, 16384, 7680, 1 << 22
+SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 
 _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
@@ -137,6 +138,8 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_nms_sorted_runs': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_uint32, _vp, _sz, _vp]),
+    'odtk_soft_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_gemm_init': (ctypes.c_int, [ctypes.c_char_p]),
     'odtk_gemm_plan_export': (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
     'odtk_gemm_plan_import': (ctypes.c_int, [ctypes.c_char_p]),
@@ -312,6 +315,31 @@ def nms(scores, boxes, classes, nms_thresh, detections_per_im, rotated=False, re
         _check(lib.odtk_nms_ex(batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
                                int(detections_per_im), float(nms_thresh), flags, ws.data_ptr(), ws.numel(), stream),
                'nms')
+    return out
+
+
+def soft_nms(scores, boxes, classes, nms_thresh, detections_per_im, method, sigma, min_score, return_indices=False):
+    """Class-aware Soft-NMS on axis-aligned boxes (include/odtk_hip.h: odtk_soft_nms; no reference equivalent): one launch.
+    method: SOFT_NMS_LINEAR / SOFT_NMS_GAUSSIAN; emitted scores are the decayed ones."""
+    _check_input(scores, 'scores')
+    _check_input(boxes, 'boxes')
+    _check_input(classes, 'classes')
+    lib = library()
+    batch, count = scores.shape
+    if boxes.shape != (batch, count, 4) or classes.shape != (batch, count):
+        raise RuntimeError('soft_nms: inconsistent shapes')
+    dev = scores.device
+    with torch.cuda.device(dev):
+        out = [torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev),
+               torch.empty((batch, detections_per_im, 4), dtype=torch.float32, device=dev),
+               torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev)]
+        if return_indices:
+            out.append(torch.empty((batch, detections_per_im), dtype=torch.int32, device=dev))
+        args = (len(out), count, int(detections_per_im), float(nms_thresh), int(method), float(sigma), float(min_score), 0)
+        size = _check(lib.odtk_soft_nms(batch, None, None, *args, None, 0, None), 'soft_nms (workspace query)')
+        ws, stream = _workspace(dev, size)
+        _check(lib.odtk_soft_nms(batch, _ptrs([scores, boxes, classes]), _ptrs(out), *args, ws.data_ptr(), ws.numel(), stream),
+               'soft_nms')
     return out
 
 

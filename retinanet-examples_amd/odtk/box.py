@@ -19,6 +19,8 @@ Differences, all deliberate:
     enqueue, with no host synchronisation (GPU only).
 """
 
+import math
+
 import torch
 
 from . import _C
@@ -340,6 +342,46 @@ def _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections):
     return scores_out, boxes_out, classes_out
 
 
+def _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score):
+    """CPU branch of `soft_nms`: Soft-NMS (Bodla et al. 2017), class-aware, with `_nms_cpu`'s +1 pixel IoU in its operation order.
+    Working scores w start as the scores (alive iff w > 0); up to `ndetections` times the alive candidate with the largest w
+    (ties: lowest position) is emitted with its current w and retired, and every alive candidate of its class is decayed --
+    linear: w *= 1 - IoU where not IoU <= nms; gaussian: w *= exp(-(IoU * IoU) / sigma) -- and stays alive iff w >= min_score."""
+    all_scores, all_boxes, all_classes = all_scores.float(), all_boxes.float(), all_classes.float()
+    batch = all_scores.shape[0]
+    scores_out = all_scores.new_zeros((batch, ndetections))
+    boxes_out = all_scores.new_zeros((batch, ndetections, 4))
+    classes_out = all_scores.new_zeros((batch, ndetections))
+    index_out = torch.full((batch, ndetections), -1, dtype=torch.int32)
+    sigma = torch.tensor(sigma, dtype=torch.float32)
+    for image in range(batch):
+        boxes, classes = all_boxes[image], all_classes[image]
+        w = all_scores[image].clone()
+        alive = w > 0
+        area = (boxes[:, 2] - boxes[:, 0] + 1) * (boxes[:, 3] - boxes[:, 1] + 1)
+        for kept in range(ndetections):
+            if not bool(alive.any()):
+                break
+            ranked = torch.where(alive, w, torch.full_like(w, -1))
+            i = int(torch.nonzero(ranked == ranked.max()).view(-1)[0])   # largest w, lowest position
+            scores_out[image, kept], boxes_out[image, kept], classes_out[image, kept] = w[i], boxes[i], classes[i]
+            index_out[image, kept] = i
+            alive[i] = False
+            visit = alive & (classes == classes[i])
+            lo = torch.max(boxes[:, :2], boxes[i, :2])
+            hi = torch.min(boxes[:, 2:], boxes[i, 2:])
+            inter = torch.prod((hi - lo + 1).clamp(0), 1)
+            iou = inter / (area + area[i] - inter)
+            if method == 'gaussian':
+                # (float64 exp rounded once: what csrc/common.hpp's exp_cr is)
+                decayed = w * torch.exp(((-(iou * iou)) / sigma).double()).float()
+            else:
+                decayed = torch.where(~(iou <= nms), w * (1 - iou), w)
+            w = torch.where(visit, decayed, w)
+            alive &= ~visit | (w >= min_score)
+    return scores_out, boxes_out, classes_out, index_out
+
+
 def decode(all_cls_head, all_box_head, stride=1, threshold=0.05, top_n=1000, anchors=None, rotated=False):
     """Box decoding and filtering for one pyramid level (reference box.py:255-309).
 
@@ -361,6 +403,28 @@ def nms(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100):
         return _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections)
     return _C.nms(all_scores.float().contiguous(), all_boxes.float().contiguous(),
                   all_classes.float().contiguous(), nms, ndetections, False)
+
+
+SOFT_NMS_METHODS = {'linear': _C.SOFT_NMS_LINEAR, 'gaussian': _C.SOFT_NMS_GAUSSIAN}
+
+
+def _soft_nms_options(method, sigma, min_score):
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError("soft_nms: method must be 'linear' or 'gaussian', not %r" % (method,))
+    sigma, min_score = float(sigma), float(min_score)
+    if not (math.isfinite(sigma) and sigma > 0 and math.isfinite(min_score) and min_score > 0):
+        raise ValueError('soft_nms: sigma and min_score must be finite and > 0')
+    return method, sigma, min_score
+
+
+def soft_nms(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, method='linear', sigma=0.5, min_score=0.001):
+    """Batched class-aware Soft-NMS on axis-aligned boxes (no reference equivalent; definition at `_soft_nms_cpu`): neighbours of
+    a kept box have their scores decayed instead of being dropped; the returned scores are the decayed ones, non-increasing."""
+    method, sigma, min_score = _soft_nms_options(method, sigma, min_score)
+    if not all_scores.is_cuda:
+        return _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score)[:3]
+    return _C.soft_nms(all_scores.float().contiguous(), all_boxes.float().contiguous(), all_classes.float().contiguous(),
+                       nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score)
 
 
 def nms_rotated(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100):
@@ -401,15 +465,33 @@ def decode_levels(cls_heads, box_heads, strides, threshold, top_n, anchors_per_s
 
 
 def detect(cls_heads, box_heads, strides, anchors_per_stride, threshold=0.05, top_n=1000, nms=0.5,
-           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None):
+           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None, soft_nms=None):
     """sigmoid (logits=True) + decode of all levels + nms: the whole inference post-processing of the
     reference (model.py:140-165) in one enqueue of three launches (rotated: five to seven), reading the head tensors in place.
     cls_bias / box_bias: the heads' last-conv biases, added inside the kernels (see _C.decode_levels); cls_thresholds: the
-    prefilter's threshold table for that cls_bias, made once by _C.prefilter_thresholds (optional)."""
+    prefilter's threshold table for that cls_bias, made once by _C.prefilter_thresholds (optional).
+    soft_nms: None, or a dict with `method` ('linear' / 'gaussian'), `sigma` and `min_score` -- the suppression is then Soft-NMS
+    (`soft_nms` above) on decode_levels' candidates: three launches as well."""
+    if soft_nms is not None and rotated:
+        raise ValueError('detect: Soft-NMS is not available for rotated boxes')
     anchors = [anchors_per_stride[s][0] if rotated else anchors_per_stride[s] for s in strides]
     for t in cls_heads:
         _require_gpu(t, 'detect')
     pairs = [_pair(c, b) for c, b in zip(cls_heads, box_heads)]
+    if soft_nms is not None:
+        method, sigma, min_score = _soft_nms_options(soft_nms.get('method', 'linear'), soft_nms.get('sigma', 0.5),
+                                                     soft_nms.get('min_score', threshold))
+        def bias_of(bias, lo, hi):
+            return bias[lo:hi] if isinstance(bias, (list, tuple)) else bias
+        parts = []
+        for lo in range(0, len(pairs), _C.MAX_LEVELS):
+            hi = min(lo + _C.MAX_LEVELS, len(pairs))
+            parts.append(_C.decode_levels([p[0] for p in pairs[lo:hi]], [p[1] for p in pairs[lo:hi]], anchors[lo:hi],
+                                          strides[lo:hi], threshold, top_n, False, logits=logits,
+                                          cls_bias=bias_of(cls_bias, lo, hi), box_bias=bias_of(box_bias, lo, hi),
+                                          cls_thresholds=cls_thresholds if len(pairs) <= _C.MAX_LEVELS else None))
+        candidates = parts[0] if len(parts) == 1 else [torch.cat(t, 1) for t in zip(*parts)]
+        return _C.soft_nms(*candidates, nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score)
     if len(pairs) > _C.MAX_LEVELS:
         # a model with several backbones has 5 levels per backbone (reference model.py:138): the level table of one call
         # holds MAX_LEVELS, so decode in groups and hand the concatenation to nms (its candidate count is not capped)

@@ -609,7 +609,8 @@ class FusedRetinaNet(nn.Module):
         m = self.model[0]                                                # (post-processing parameters are baked into the launches)
         bias = self.cls_head[-1].bias                                    # its state is baked in too: the prefilter's threshold table
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
-               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, bias.data_ptr(), bias._version)
+               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, bias.data_ptr(), bias._version,
+               tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None)     # (the suppression rule is baked in as well)
         entry = self._graphs.get(key)
         if entry is None:
             static_x = torch.empty_like(x)
@@ -765,4 +766,5 @@ class FusedRetinaNet(nn.Module):
                     if not bool(torch.isfinite(t).all()):
                         raise FloatingPointError('FusedRetinaNet: non-finite values in the %s head tensor of level %d' % (name, i))
         return box_ops.detect(cls_heads, box_heads, strides, m.anchors, m.threshold, m.top_n, m.nms, m.detections,
-                              m.rotated_bbox, logits=True, cls_bias=cls_bias, box_bias=box_bias, cls_thresholds=table)
+                              m.rotated_bbox, logits=True, cls_bias=cls_bias, box_bias=box_bias, cls_thresholds=table,
+                              soft_nms=getattr(m, 'soft_nms', None))

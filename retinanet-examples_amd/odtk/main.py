@@ -15,6 +15,8 @@ What differs from the reference, and why:
     HIP launch per batch (odtk/data.py), bit-identical to the default loader.
   * `--device-augment` (train) is new as well: `--device-resize` plus the training augmentations (`--augment-rotate` and the four
     colour options) on the GPU, as a short chain of HIP launches per batch, bit-identical to Pillow on the host.
+  * `--soft-nms {linear,gaussian}` (infer; train: its validation passes) with `--soft-nms-sigma` / `--soft-nms-min-score` is new:
+    Soft-NMS (odtk/box.py:soft_nms, one HIP launch) instead of the reference's hard suppression.  Never stored in a checkpoint.
 """
 import argparse
 import os
@@ -49,7 +51,12 @@ _COMMON = [_flag('--with-apex', bool, text=_DROPPED), _flag('--with-dali', bool,
            _flag('--workers', int, 8, 'loader processes per GPU (the reference hard-codes 2; ~6 feed one MI355X)', metavar='num'),
            # not a flag of the reference: absent from the namespace unless given (read with getattr)
            _flag('--device-resize', bool, text='resize, flip, pad and normalise the images on the device, bit-identical to the '
-                 'host loader (train: not with --augment-rotate or non-zero colour augmentations)', default=argparse.SUPPRESS)]
+                 'host loader (train: not with --augment-rotate or non-zero colour augmentations)', default=argparse.SUPPRESS),
+           _flag('--soft-nms', str, argparse.SUPPRESS, 'Soft-NMS instead of hard suppression: neighbours of a kept box keep a decayed '
+                 'score (train: in the validation passes; not with --rotated-bbox)', choices=['linear', 'gaussian']),
+           _flag('--soft-nms-sigma', float, argparse.SUPPRESS, 'width of the gaussian decay (default 0.5)', metavar='value'),
+           _flag('--soft-nms-min-score', float, argparse.SUPPRESS, 'decayed scores below this are dropped (default: the '
+                 "model's score threshold)", metavar='value')]
 
 # same names, types and defaults as the reference's parser (main.py:15-118)
 TRAIN_FLAGS = [
@@ -124,7 +131,21 @@ def parse(args):
             if flag == '--batch':
                 spec['default'] = per_gpu
             sub.add_argument(flag, **spec)
-    return parser.parse_args(args)
+    parsed = parser.parse_args(args)
+    soft = [f for f in ('soft_nms', 'soft_nms_sigma', 'soft_nms_min_score') if hasattr(parsed, f)]
+    if soft and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--soft-nms is not available with --rotated-bbox')
+    if soft and 'soft_nms' not in soft:
+        parser.error('--soft-nms-sigma / --soft-nms-min-score need --soft-nms {linear,gaussian}')
+    return parsed
+
+
+def soft_nms_options(args, model):
+    """What `--soft-nms*` ask for, as `Model.soft_nms` takes it (None: the flags were not given)."""
+    if not hasattr(args, 'soft_nms'):
+        return None
+    return {'method': args.soft_nms, 'sigma': getattr(args, 'soft_nms_sigma', 0.5),
+            'min_score': getattr(args, 'soft_nms_min_score', model.threshold)}
 
 
 def load_model(args, verbose=False):
@@ -179,6 +200,10 @@ def worker(rank, args, world, spawned=False):
     model, state = load_model(args, verbose=(rank == 0))
     if model.angles is not None:
         args.rotated_bbox = True
+    if args.command != 'export':
+        model.soft_nms = soft_nms_options(args, model)
+        if model.soft_nms is not None and args.rotated_bbox:
+            raise RuntimeError('--soft-nms is not available for a model with rotated boxes')
     try:
         if args.command == 'train':
             return train.train(model, state, args.images, args.annotations, args.val_images or args.images,

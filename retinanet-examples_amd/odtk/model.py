@@ -81,6 +81,9 @@ class Model(nn.Module):
         self.top_n = config.get('top_n', 1000)
         self.nms = config.get('nms', 0.5)
         self.detections = config.get('detections', 100)
+        # Soft-NMS instead of the reference's hard rule (odtk/box.py:soft_nms): None, or a dict with `method` ('linear' /
+        # 'gaussian'), `sigma` and `min_score` (default: `threshold`).  A run-time option: never written into checkpoints
+        self.soft_nms = None
         self.exporting = False
         self.fused_postprocess = True
         self.fused_graph = True                             # eval on a GPU runs the BN-folded engine (odtk/fused.py)
@@ -245,13 +248,19 @@ class Model(nn.Module):
 
     def postprocess(self, cls_heads, box_heads, strides):
         """Raw head tensors -> (scores [B, D], boxes [B, D, 4|6], classes [B, D])."""
+        if self.soft_nms is not None and self.rotated_bbox:
+            raise ValueError('Model.soft_nms is not available for rotated boxes')
         if self.fused_postprocess and cls_heads[0].is_cuda:
             # sigmoid + decode x5 + nms on the head tensors as the convolutions wrote them
             return box_ops.detect(cls_heads, box_heads, strides, self.anchors, self.threshold, self.top_n,
-                                  self.nms, self.detections, self.rotated_bbox, logits=True)
+                                  self.nms, self.detections, self.rotated_bbox, logits=True, soft_nms=self.soft_nms)
         # the reference's sequence, call for call (model.py:140, :153-165); on CPU tensors this is the
         # pure-torch branch of odtk/box.py
         suppress = box_ops.nms_rotated if self.rotated_bbox else box_ops.nms
+        if self.soft_nms is not None:
+            def suppress(scores, boxes, classes, nms, detections):
+                return box_ops.soft_nms(scores, boxes, classes, nms, detections, self.soft_nms.get('method', 'linear'),
+                                        self.soft_nms.get('sigma', 0.5), self.soft_nms.get('min_score', self.threshold))
         per_level = [box_ops.decode(c.sigmoid().contiguous(), b.contiguous(), s, self.threshold, self.top_n,
                                     self.anchors[s], self.rotated_bbox)
                      for c, b, s in zip(cls_heads, box_heads, strides)]
