@@ -556,6 +556,11 @@ int odtk_debug_loss_tuning(int which, int fp32_heads, int threads, int blocks_pe
  * writes one vector per cell, 0 = in depth's order, one element per store (rounds 2-5).  Results do not depend on any of
  * them beyond the order of the partial sums. */
 int odtk_debug_loss_layout(int which, int fp32_heads, int per_wave, int window, int box_rows);
+/* Debug: reads back what the two setters above hold for one form and head width: out = threads, blocks_per_cu, unroll,
+ * box_blocks, per_wave, window, box_rows.  Before any setter ran these are the shipped defaults.  Never touches HIP; a bad
+ * `which` or a NULL `out` returns ODTK_ERR_INVALID.  A caller that changes the launch shape snapshots it here first and puts
+ * the snapshot back afterwards, so that no copy of the defaults lives outside the library. */
+int odtk_debug_loss_tuning_get(int which, int fp32_heads, int out[7]);
 /* Debug / A-B: arithmetic form of the classification walk of the loss kernels when gamma == 2 (csrc/loss.hpp).
  * 0: every logit through the symmetric form (one select on the target, one on the sign);  1: 16-byte vectors that hold no
  * positive element and no logit above 64 (all but ~1 in 1000) through the negatives-only form u = exp(x), q = u / (1 + u),
@@ -568,6 +573,8 @@ int odtk_debug_loss_layout(int which, int fp32_heads, int per_wave, int window, 
  * accepts 0 and 1.  Returns ODTK_ERR_INVALID for any other value. */
 #define ODTK_LOSS_FORM_DEFAULT 1
 int odtk_debug_loss_form(int form);
+/* Debug: the form odtk_debug_loss_form last set (ODTK_LOSS_FORM_DEFAULT before any call).  Never touches HIP. */
+int odtk_debug_loss_form_get(void);
 int odtk_profile_collect(double total_ms[ODTK_KERNEL_COUNT], int launches[ODTK_KERNEL_COUNT]);
 
 #ifdef __cplusplus

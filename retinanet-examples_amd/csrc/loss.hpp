@@ -133,6 +133,16 @@ __device__ __forceinline__ float smooth_l1_element(float pred, float target, flo
   return x >= beta ? x - 0.5f * beta : 0.5f * x * x / beta;
 }
 
+// What every box-delta walk of the backward stores for one parameter: g * grad, rounded to fp32 HERE and with a zero always +0.
+// Without the barrier the compiler folds the product into the fp16 conversion of the walks that store element by element
+// (v_fma_mixlo_f16: the exact product rounded once, and -0 + 0 = +0) but not into the walk that stores a vector, and d(deltas)
+// differed with box_rows in the sign of a zero -- and could in the last bit (tests/test_gpu_loss_shapes.py).
+__device__ __forceinline__ float box_grad_value(float g, float grad) {
+  float v = g * grad + 0.0f;
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 template <typename T>
 __device__ __forceinline__ void store_elem(void *base, uint64_t idx, float v) {
   if constexpr (std::is_same_v<T, F32>) {
@@ -413,6 +423,7 @@ __device__ __forceinline__ void retina_loss_block(const LossArgs &a, uint32_t bl
       // partial-line writes per wave and store, as many L2 requests again as half the logit stream
       // (profiles/r05_loss_pmc.txt: 4.56 M requests in the backward for 2.9 M of logits).  depth / box_target are gathered
       // (planes of hw floats); only foreground cells (~0.5 %) read the deltas and the targets at all.
+      const float g0 = box_grad_value(g, 0.0f);              // what a cell that is not foreground stores (0 for a finite g)
       for (uint32_t cell = (block - a.cls_blocks) * blockDim.x + threadIdx.x; cell < cells; cell += stride) {
         uint32_t pix, an;
         const uint32_t ip = fastdivmod(cell, a.by_anchors, &an);   // img * hw + pix
@@ -421,13 +432,13 @@ __device__ __forceinline__ void retina_loss_block(const LossArgs &a, uint32_t bl
         const bool fg = a.depth[ia * hw + pix] > 0.0f;                          // model.py:204 box_mask
         const uint64_t off = static_cast<uint64_t>(cell) * NB;
         if (NB == 4) {                                                           // (launch-uniform)
-          float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+          float out[4] = {g0, g0, g0, g0};
           if (fg) {
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k) {
               float grad;
               smooth_l1_element<true>(load_raw<T>(a.box, off + k), a.box_target[(static_cast<uint64_t>(ia) * 4 + k) * hw + pix], a.beta, &grad);
-              out[k] = g * grad;
+              out[k] = box_grad_value(g, grad);
             }
           }
           store_vec4<T>(a.dbox, cell, out);
@@ -435,7 +446,7 @@ __device__ __forceinline__ void retina_loss_block(const LossArgs &a, uint32_t bl
           for (uint32_t k = 0; k < NB; ++k) {
             float grad = 0.0f;
             if (fg) smooth_l1_element<true>(load_raw<T>(a.box, off + k), a.box_target[(static_cast<uint64_t>(ia) * NB + k) * hw + pix], a.beta, &grad);
-            store_elem<T>(a.dbox, off + k, g * grad);
+            store_elem<T>(a.dbox, off + k, box_grad_value(g, grad));
           }
         }
       }
@@ -456,7 +467,7 @@ __device__ __forceinline__ void retina_loss_block(const LossArgs &a, uint32_t bl
                                                        a.box_target[(static_cast<uint64_t>(ia) * NB + k) * hw + pix], a.beta, &grad);
           if constexpr (!kBackward) sum_box += l;
         }
-        if constexpr (kBackward) store_elem<T>(a.dbox, off, g * grad);
+        if constexpr (kBackward) store_elem<T>(a.dbox, off, box_grad_value(g, grad));
       }
     }
     }

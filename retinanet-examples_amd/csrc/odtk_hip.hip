@@ -839,6 +839,20 @@ int odtk_debug_loss_layout(int which, int fp32_heads, int per_wave, int window, 
   return ODTK_OK;
 }
 
+int odtk_debug_loss_tuning_get(int which, int fp32_heads, int out[7]) {
+  if (which < 0 || which > 2 || !out) return ODTK_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  const LossTuning &t = g_loss_tuning[fp32_heads != 0][which];
+  out[0] = t.threads; out[1] = t.per_cu; out[2] = t.unroll; out[3] = t.box_blocks;
+  out[4] = t.per_wave; out[5] = t.window; out[6] = t.box_rows;
+  return ODTK_OK;
+}
+
+int odtk_debug_loss_form_get(void) {
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  return g_loss_form;
+}
+
 int odtk_debug_loss_form(int form) {
 #ifdef ODTK_LOSS_ABLATIONS
   if (form < 0 || form > 7 || form == 5) return ODTK_ERR_INVALID;

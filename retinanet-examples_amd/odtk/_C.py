@@ -119,6 +119,8 @@ _SIGNATURES = {
     'odtk_debug_loss_tuning': (ctypes.c_int, [ctypes.c_int] * 6),
     'odtk_debug_loss_layout': (ctypes.c_int, [ctypes.c_int] * 5),
     'odtk_debug_loss_form': (ctypes.c_int, [ctypes.c_int]),
+    'odtk_debug_loss_tuning_get': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    'odtk_debug_loss_form_get': (ctypes.c_int, []),
     'odtk_bias_act_maxpool': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'odtk_snap_to_anchors_rotated_levels': (ctypes.c_int, [ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
@@ -1132,6 +1134,28 @@ def loss_layout(which, fp32_heads, per_wave=0, window=0, box_rows=1):
     box-delta walk in memory order (include/odtk_hip.h: odtk_debug_loss_layout)."""
     _check(library().odtk_debug_loss_layout(int(which), int(bool(fp32_heads)), int(bool(per_wave)), int(bool(window)),
                                             int(bool(box_rows))), 'loss_layout')
+
+
+LOSS_TUNING_FIELDS = ('threads', 'blocks_per_cu', 'unroll', 'box_blocks', 'per_wave', 'window', 'box_rows')
+
+
+def loss_tuning_state(which, fp32_heads):
+    """What loss_tuning / loss_layout hold for one form and head width, as a dict over LOSS_TUNING_FIELDS (include/odtk_hip.h:
+    odtk_debug_loss_tuning_get); the shipped defaults until a setter ran.  Never touches the GPU."""
+    out = (ctypes.c_int * 7)()
+    _check(library().odtk_debug_loss_tuning_get(int(which), int(bool(fp32_heads)), out), 'loss_tuning_state')
+    return dict(zip(LOSS_TUNING_FIELDS, out))
+
+
+def loss_tuning_restore(which, fp32_heads, state):
+    """Puts back what loss_tuning_state returned."""
+    loss_tuning(which, fp32_heads, state['threads'], state['blocks_per_cu'], state['unroll'], state['box_blocks'])
+    loss_layout(which, fp32_heads, state['per_wave'], state['window'], state['box_rows'])
+
+
+def loss_form_state():
+    """The arithmetic form loss_form last set (include/odtk_hip.h: odtk_debug_loss_form_get)."""
+    return library().odtk_debug_loss_form_get()
 
 
 LOSS_FORM_DEFAULT = 1      # = ODTK_LOSS_FORM_DEFAULT of include/odtk_hip.h (tests/test_abi_host.py compares the two)

@@ -204,6 +204,59 @@ def test_loss_layout_hook_validates_without_a_gpu():
         _C.loss_layout(0, 1, 1, 0, 1)
 
 
+def test_loss_tuning_read_back_round_trips_without_a_gpu():
+    """odtk_debug_loss_tuning_get reads what the two setters hold, per (form, head width): set -> get round-trips for all six,
+    each setter leaves the other's fields alone, a refused set changes nothing, and bad arguments are refused.  The state found
+    is put back, so this test adds no copy of the defaults."""
+    lib = _C.library()
+    pairs = [(which, fp32) for which in (0, 1, 2) for fp32 in (0, 1)]
+    found = {p: _C.loss_tuning_state(*p) for p in pairs}
+    form = _C.loss_form_state()
+    try:
+        out = (ctypes.c_int * 7)()
+        for bad in (-1, 3):
+            assert lib.odtk_debug_loss_tuning_get(bad, 0, out) == _C.ERR_INVALID
+        assert lib.odtk_debug_loss_tuning_get(0, 0, None) == _C.ERR_INVALID
+        with pytest.raises(RuntimeError, match='invalid argument'):
+            _C.loss_tuning_state(3, 0)
+        # six distinct states, all set before any is read: no pair aliases another
+        want = {}
+        for i, (which, fp32) in enumerate(pairs):
+            shape = (64 * (i + 1), i + 2, (1, 2, 4)[i % 3], 100 + i)
+            layout = (int(which == 2 and fp32 == 1), i % 2, (i // 2) % 2)
+            _C.loss_tuning(which, fp32, *shape)
+            _C.loss_layout(which, fp32, *layout)
+            want[which, fp32] = shape + layout
+        for p in pairs:
+            state = _C.loss_tuning_state(*p)
+            assert tuple(state) == _C.LOSS_TUNING_FIELDS
+            assert tuple(state.values()) == want[p], p
+            assert lib.odtk_debug_loss_tuning_get(p[0], p[1], out) == 0 and tuple(out) == want[p]
+        # the layout setter leaves the four tuning fields alone, and the reverse
+        _C.loss_layout(2, 0, 1, 0, 0)
+        assert tuple(_C.loss_tuning_state(2, 0).values()) == want[2, 0][:4] + (1, 0, 0)
+        _C.loss_tuning(2, 0, 1024, 64, 4, 16384)
+        assert tuple(_C.loss_tuning_state(2, 0).values()) == (1024, 64, 4, 16384, 1, 0, 0)
+        # a refused set leaves every field as it was
+        before = {p: _C.loss_tuning_state(*p) for p in pairs}
+        assert lib.odtk_debug_loss_tuning(1, 1, 100, 1, 4, 64) == _C.ERR_INVALID
+        assert lib.odtk_debug_loss_tuning(1, 1, 256, 1, 3, 64) == _C.ERR_INVALID
+        assert lib.odtk_debug_loss_layout(1, 1, 1, 0, 0) == _C.ERR_INVALID          # per-wave sums: workspace form only
+        assert lib.odtk_debug_loss_layout(0, 0, 0, 2, 0) == _C.ERR_INVALID
+        assert {p: _C.loss_tuning_state(*p) for p in pairs} == before
+        # the form has a read-back of its own, and a refused form changes nothing
+        for f in (0, 1):
+            _C.loss_form(f)
+            assert _C.loss_form_state() == f
+            assert lib.odtk_debug_loss_form(5) == _C.ERR_INVALID and _C.loss_form_state() == f
+        assert {p: _C.loss_tuning_state(*p) for p in pairs} == before                # the form is not part of the launch shape
+    finally:
+        for p in pairs:
+            _C.loss_tuning_restore(p[0], p[1], found[p])
+        _C.loss_form(form)
+    assert {p: _C.loss_tuning_state(*p) for p in pairs} == found and _C.loss_form_state() == form
+
+
 def test_loss_form_hook_validates_without_a_gpu():
     """odtk_debug_loss_form (arithmetic form of the gamma = 2 classification walk): 0 / 1; the
     binding's default is the header's ODTK_LOSS_FORM_DEFAULT."""

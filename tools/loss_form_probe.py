@@ -169,20 +169,22 @@ def main():
         _C.loss_form(form)
         say('ablation fp32 nhwc forward, %-38s %6.2f us' % (what + ':', timed(fwd, sets, 30)))
     _C.loss_form(1)
+    # the launch shapes found at start-up (odtk_debug_loss_tuning_get) are what the sweeps below put back: no copy of the defaults here
+    found_fwd, found_ws = _C.loss_tuning_state(0, True), _C.loss_tuning_state(2, True)
     rows = []
     for threads in (256, 512, 1024):
         for per_cu in (1, 2, 4, 8):
             for unroll in (1, 2, 4):
                 _C.loss_tuning(0, True, threads, per_cu, unroll, 64)
                 rows.append((timed(fwd, sets, 20), threads, per_cu, unroll))
-    _C.loss_tuning(0, True, 512, 1, 4, 64)
+    _C.loss_tuning_restore(0, True, found_fwd)
     rows.sort()
     for r in rows[:6] + rows[-2:]:
         say('shape fp32 nhwc forward form 1: %6.2f us  threads %4d  per_cu %d  unroll %d' % r)
     for box_blocks in (16, 64, 256, 1024, 4096):
-        _C.loss_tuning(0, True, 512, 1, 4, box_blocks)
+        _C.loss_tuning(0, True, found_fwd['threads'], found_fwd['blocks_per_cu'], found_fwd['unroll'], box_blocks)
         say('box workgroups per level %4d: fp32 nhwc forward form 1 %6.2f us' % (box_blocks, timed(fwd, sets, 20)))
-    _C.loss_tuning(0, True, 512, 1, 4, 64)
+    _C.loss_tuning_restore(0, True, found_fwd)
     ws = lambda s: _C.retina_loss_levels_forward(s[0], s[1], s[2], s[3], 0.25, 2.0, 0.11, reproducible=True)
     rows = []
     for threads in (256, 512):
@@ -198,7 +200,7 @@ def main():
                 torch.cuda.synchronize()
                 got = _C.profile_collect()
                 rows.append(((got['retina_loss_kernel'][0] + got['loss_reduce_kernel'][0]) * 1e3 / 20, threads, per_cu, unroll))
-    _C.loss_tuning(2, True, 256, 4, 2, 256)          # (the default since round 6)
+    _C.loss_tuning_restore(2, True, found_ws)
     rows.sort()
     for r in rows[:4] + rows[-1:]:
         say('shape fp32 nhwc forward (workspace, 2 launches) form 1: %6.2f us  threads %4d  per_cu %2d  unroll %d' % r)

@@ -23,8 +23,9 @@ import loss_form_probe as P  # noqa: E402
 
 say = P.say
 FWD, BWD, WS = 0, 1, 2
-DEFAULT = {(FWD, True): (512, 1, 4, 64), (FWD, False): (512, 1, 2, 64), (BWD, True): (256, 8, 2, 1024), (BWD, False): (256, 4, 1, 256),
-           (WS, True): (256, 4, 2, 256), (WS, False): (256, 4, 1, 256)}
+# the launch shapes as the library holds them when this tool starts (odtk_debug_loss_tuning_get): the shipped defaults, whatever a
+# retune made of them -- no copy of the table lives here
+DEFAULT = {(which, fp32): _C.loss_tuning_state(which, fp32) for which in (FWD, BWD, WS) for fp32 in (True, False)}
 
 
 def timed(fn, sets, iters, split=False):
@@ -45,9 +46,8 @@ def timed(fn, sets, iters, split=False):
 
 
 def reset():
-    for (which, fp32), shape in DEFAULT.items():
-        _C.loss_tuning(which, fp32, *shape)
-        _C.loss_layout(which, fp32, 0, 0 if which == FWD else 1, 1)
+    for (which, fp32), state in DEFAULT.items():
+        _C.loss_tuning_restore(which, fp32, state)
 
 
 def main():
