@@ -1,0 +1,204 @@
+// engine.hip -- what the inference engine runs between convolutions: bias + activation epilogues, the max-pool, nearest
+// 2x upsampling, the pyramid canvas, the stem pack, and the hipBLASLt GEMM (gemm_lt.hpp is included here only).
+#include <cstring>
+
+#include "runtime.hpp"
+#include "epilogue.hpp"
+#include "gemm_lt.hpp"
+
+namespace {
+
+template <typename T, bool kRes, bool kRelu>
+int bias_act_launch(void *y, const float *bias, const void *res, uint64_t n, uint32_t channels, hipStream_t stream) {
+  constexpr int per = T::kPerLoad;
+  uint64_t done = 0;
+  if (channels % per == 0 && n / per >= 256) {
+    // fast form: grid stride (blocks * 256 lanes) must be a multiple of the row length in vectors
+    const uint32_t vpr = channels / per;
+    const uint64_t n_vec = n / per;                         // n is a multiple of channels, hence of per
+    uint32_t g = vpr, m = 256;                              // unit = vpr / gcd(vpr, 256) blocks
+    while (m) { const uint32_t r_ = g % m; g = m; m = r_; }
+    const uint32_t unit = vpr / g;
+    uint64_t blocks = (n_vec + 256ull * 4 - 1) / (256ull * 4);          // ~4 vectors per lane
+    if (blocks > 256 * 16) blocks = 256 * 16;                            // <= 16 workgroups per CU
+    blocks = (blocks + unit - 1) / unit * unit;
+    timed_launch(ODTK_KERNEL_EPILOGUE, odtk::bias_act_kernel<T, kRes, kRelu>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                 stream, y, bias, res, n_vec, vpr);
+    done = n_vec * per;
+  }
+  if (done < n) {
+    uint64_t blocks = (n - done + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((odtk::bias_act_scalar_kernel<T, kRes, kRelu>), dim3(static_cast<unsigned>(blocks)), dim3(256),
+                       0, stream, y, bias, res, done, n, channels);
+  }
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+template <typename T>
+int bias_act_typed(void *y, const float *bias, const void *res, uint64_t n, uint32_t c, bool relu, hipStream_t s) {
+  if (res) return relu ? bias_act_launch<T, true, true>(y, bias, res, n, c, s) : bias_act_launch<T, true, false>(y, bias, res, n, c, s);
+  return relu ? bias_act_launch<T, false, true>(y, bias, res, n, c, s) : bias_act_launch<T, false, false>(y, bias, res, n, c, s);
+}
+
+int bias_act_dispatch(void *y, const float *bias, const void *res, uint64_t n, uint32_t c, int dtype, bool relu,
+                      hipStream_t s) {
+  return dispatch_dtype(dtype, [&](auto t) { return bias_act_typed<decltype(t)>(y, bias, res, n, c, relu, s); });
+}
+
+template <typename TIn>
+int stem_pack_launch(const void *x, void *out, int batch, int height, int width, int channels_last, int out_dtype, hipStream_t stream) {
+  const unsigned long long total = 1ull * batch * (height / 2) * (width / 2);
+  unsigned long long blocks = (total + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  const odtk::FastDiv by_wo = odtk::fastdiv_make(static_cast<uint32_t>(width / 2));
+  const odtk::FastDiv by_howo = odtk::fastdiv_make(static_cast<uint32_t>(height / 2) * static_cast<uint32_t>(width / 2));
+  if (out_dtype == ODTK_BF16)
+    timed_launch(ODTK_KERNEL_STEM_PACK, odtk::stem_pack_kernel<TIn, odtk::BF16>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, x, out,
+                 static_cast<uint32_t>(batch), static_cast<uint32_t>(height), static_cast<uint32_t>(width), static_cast<uint32_t>(channels_last), by_wo, by_howo);
+  else
+    timed_launch(ODTK_KERNEL_STEM_PACK, odtk::stem_pack_kernel<TIn, odtk::F16>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, x, out,
+                 static_cast<uint32_t>(batch), static_cast<uint32_t>(height), static_cast<uint32_t>(width), static_cast<uint32_t>(channels_last), by_wo, by_howo);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int odtk_bias_act(void *y, const float *bias, const void *residual, size_t n_pixels, int channels, int dtype,
+                  int relu, void *stream) {
+  if (!y || !bias || channels <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(y) & 15u) || (reinterpret_cast<uintptr_t>(residual) & 15u)) return ODTK_ERR_INVALID;
+  const uint64_t n = static_cast<uint64_t>(n_pixels) * channels;
+  if (n == 0) return ODTK_OK;
+  return bias_act_dispatch(y, bias, residual, n, static_cast<uint32_t>(channels), dtype, relu != 0,
+                           static_cast<hipStream_t>(stream));
+}
+
+int odtk_bias_act_maxpool(const void *y, const float *bias, void *out, int batch_size, int height, int width,
+                          int channels, int dtype, int relu, void *stream) {
+  if (!y || !bias || !out || batch_size <= 0 || height <= 0 || width <= 0 || channels <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (channels % 8 != 0) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15u) return ODTK_ERR_INVALID;
+  if (1ull * height * width * channels >= (1ull << 32)) return ODTK_ERR_UNSUPPORTED;   // 32-bit offsets inside one image
+  const uint32_t ho = (static_cast<uint32_t>(height) + 1) / 2, wo = (static_cast<uint32_t>(width) + 1) / 2;
+  const uint64_t work = static_cast<uint64_t>(batch_size) * ho * wo * (channels / 8);
+  uint64_t blocks = (work + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;                              // grid-stride beyond 32 workgroups per CU
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint16_t *in = static_cast<const uint16_t *>(y);
+  uint16_t *o = static_cast<uint16_t *>(out);
+  odtk::PoolDivisors dv;
+  dv.groups = odtk::fastdiv_make(static_cast<uint32_t>(channels / 8));
+  dv.wo = odtk::fastdiv_make(wo);
+  dv.ho = odtk::fastdiv_make(ho);
+  const bool small = work < (1ull << 32);
+#define ODTK_POOL_(T, R, S)                                                                                             \
+  timed_launch(ODTK_KERNEL_POOL, odtk::bias_act_maxpool_kernel<T, R, S>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, in, \
+               bias, o, static_cast<uint32_t>(batch_size), static_cast<uint32_t>(height),                             \
+               static_cast<uint32_t>(width), static_cast<uint32_t>(channels), ho, wo, dv)
+#define ODTK_POOL(T, R) do { if (small) ODTK_POOL_(T, R, true); else ODTK_POOL_(T, R, false); } while (0)
+  if (dtype == ODTK_BF16) { if (relu) ODTK_POOL(odtk::BF16, true); else ODTK_POOL(odtk::BF16, false); }
+  else { if (relu) ODTK_POOL(odtk::F16, true); else ODTK_POOL(odtk::F16, false); }
+#undef ODTK_POOL_
+#undef ODTK_POOL
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_upsample_nearest2x(const void *x, void *out, int batch_size, int height, int width, int channels, int dtype,
+                            void *stream) {
+  if (!x || !out || batch_size <= 0 || height <= 0 || width <= 0 || channels <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned long long row_bytes = 1ull * channels * (dtype == ODTK_F32 ? 4 : 2);
+  if (row_bytes % 16) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15u) return ODTK_ERR_INVALID;
+  const unsigned long long groups = row_bytes / 16;
+  const unsigned long long total = 4ull * batch_size * height * width * groups;
+  if (total > 0xf0000000ull) return ODTK_ERR_INVALID;
+  unsigned long long blocks = (total + 256ull * 4 - 1) / (256ull * 4);           // ~4 vectors per lane
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  timed_launch(ODTK_KERNEL_UPSAMPLE, odtk::upsample_nearest2x_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+               static_cast<hipStream_t>(stream), static_cast<const odtk::vuint4 *>(x), static_cast<odtk::vuint4 *>(out),
+               static_cast<uint32_t>(height), static_cast<uint32_t>(width), static_cast<uint32_t>(groups), static_cast<uint32_t>(total),
+               odtk::fastdiv_make(static_cast<uint32_t>(groups)), odtk::fastdiv_make(2u * width), odtk::fastdiv_make(2u * height));
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_canvas_pack(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects,
+                     const void *const *sources, int n_rects, void *stream) {
+  if (!canvas || !rects || batch_size <= 0 || height <= 0 || width <= 0 || channels <= 0 || n_rects < 0 || n_rects > ODTK_MAX_LEVELS)
+    return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned long long row_bytes = 1ull * channels * (dtype == ODTK_F32 ? 4 : 2);
+  if (row_bytes % 16) return ODTK_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(canvas) & 15u) return ODTK_ERR_INVALID;
+  const unsigned long long groups = row_bytes / 16;
+  const unsigned long long total = 1ull * batch_size * height * width * groups;
+  if (total > 0xf0000000ull) return ODTK_ERR_INVALID;
+  odtk::CanvasArgs a{};
+  a.n = static_cast<uint32_t>(n_rects);
+  for (int l = 0; l < n_rects; ++l) {
+    const int y0 = rects[4 * l], x0 = rects[4 * l + 1], h = rects[4 * l + 2], w = rects[4 * l + 3];
+    if (y0 < 0 || x0 < 0 || h <= 0 || w <= 0 || y0 > height - h || x0 > width - w) return ODTK_ERR_INVALID;   // inside the canvas
+    if (sources && (!sources[l] || (reinterpret_cast<uintptr_t>(sources[l]) & 15u))) return ODTK_ERR_INVALID;
+    a.y0[l] = static_cast<uint32_t>(y0); a.x0[l] = static_cast<uint32_t>(x0);
+    a.h[l] = static_cast<uint32_t>(h); a.w[l] = static_cast<uint32_t>(w);
+    a.src[l] = sources ? static_cast<const odtk::vuint4 *>(sources[l]) : nullptr;
+  }
+  unsigned long long blocks = (total + 256ull * 4 - 1) / (256ull * 4);           // ~4 vectors per lane
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(odtk::canvas_fill_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<odtk::vuint4 *>(canvas), a, static_cast<uint32_t>(groups), static_cast<uint32_t>(total),
+                     odtk::fastdiv_make(static_cast<uint32_t>(groups)), odtk::fastdiv_make(static_cast<uint32_t>(width)),
+                     odtk::fastdiv_make(static_cast<uint32_t>(height)));
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_canvas_clear(void *canvas, int batch_size, int height, int width, int channels, int dtype, const int *rects, int n_rects,
+                      void *stream) {
+  return odtk_canvas_pack(canvas, batch_size, height, width, channels, dtype, rects, nullptr, n_rects, stream);
+}
+
+int odtk_stem_pack(const void *x, void *out, int batch_size, int height, int width, int in_dtype, int channels_last, int out_dtype,
+                   void *stream) {
+  if (!x || !out || batch_size <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return ODTK_ERR_INVALID;
+  if (channels_last != 0 && channels_last != 1) return ODTK_ERR_INVALID;
+  if (in_dtype != ODTK_F32 && in_dtype != ODTK_BF16 && in_dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (out_dtype != ODTK_BF16 && out_dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(out) & 15u) return ODTK_ERR_INVALID;
+  if (1ull * batch_size * (height / 2) * (width / 2) > 0xf0000000ull) return ODTK_ERR_INVALID;
+  if (3ull * height * width >= (1ull << 32)) return ODTK_ERR_INVALID;       // 32-bit offsets inside one image
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return dispatch_dtype(in_dtype, [&](auto t) {
+    return stem_pack_launch<decltype(t)>(x, out, batch_size, height, width, channels_last, out_dtype, s);
+  });
+}
+
+int odtk_gemm_init(const char *hipblaslt_path) { return odtk::lt::init(hipblaslt_path); }
+
+size_t odtk_gemm_plan_export(char *text, size_t capacity) { return odtk::lt::plan_export(text, capacity); }
+int odtk_gemm_plan_import(const char *text) { return odtk::lt::plan_import(text); }
+int odtk_gemm_plan_pin_misses(void) { return odtk::lt::pin_misses(); }
+
+int odtk_gemm_bias_act(void *y, const void *x, const void *w, const float *bias, const void *residual, size_t m,
+                       int n, int k, int dtype, int relu, void *workspace, size_t workspace_size, void *stream) {
+  if (!y || !x || !w || !bias || n <= 0 || k <= 0 || residual == y) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) |
+       reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(workspace)) & 15u)
+    return ODTK_ERR_INVALID;
+  if (m == 0) return ODTK_OK;
+  KernelTimer t(ODTK_KERNEL_GEMM, static_cast<hipStream_t>(stream));
+  return odtk::lt::gemm_bias_act(y, x, w, bias, residual, m, static_cast<uint32_t>(n), static_cast<uint32_t>(k), dtype,
+                                 relu, workspace, workspace_size, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

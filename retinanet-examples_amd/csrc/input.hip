@@ -1,0 +1,180 @@
+// input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise) and odtk_augment_images.
+#include <cmath>
+#include <cstring>
+
+#include "runtime.hpp"
+#include "preprocess.hpp"
+#include "augment.hpp"
+
+extern "C" {
+
+// One axis of one image: the table (or the skipped pass) is consistent with the sizes and lies inside `tables`.
+static bool preprocess_axis_ok(int32_t table, int32_t taps, int32_t in_size, int32_t out_size, size_t tables_len) {
+  if (table < 0) return table == -1 && in_size == out_size;
+  if (taps <= 0) return false;
+  const unsigned long long need = 1ull * static_cast<uint32_t>(out_size) * (2ull + static_cast<uint32_t>(taps));
+  return need < (1ull << 31) && static_cast<unsigned long long>(table) + need <= tables_len;
+}
+
+// The images of a batch against their buffers; `canvas` = false: the resized image is not held to height x width (it is turned later).
+static int preprocess_images_ok(int batch_size, const odtk_image_t *images, size_t src_bytes, const int32_t *tables, size_t tables_len,
+                                int height, int width, bool canvas) {
+  for (int b = 0; b < batch_size; ++b) {
+    const odtk_image_t &im = images[b];
+    if (im.src_width <= 0 || im.src_height <= 0 || im.out_width <= 0 || im.out_height <= 0) return ODTK_ERR_INVALID;
+    if (canvas && (im.out_width > width || im.out_height > height)) return ODTK_ERR_INVALID;
+    if (im.mirror != 0 && im.mirror != 1) return ODTK_ERR_INVALID;
+    if (im.src_pitch <= 0 || 3ll * im.src_width > im.src_pitch) return ODTK_ERR_INVALID;
+    const unsigned long long extent = 1ull * (im.src_height - 1) * im.src_pitch + 3ull * im.src_width;   // 32-bit offsets inside one image
+    if (extent >= (1ull << 31) || im.src_offset > src_bytes || extent > src_bytes - im.src_offset) return ODTK_ERR_INVALID;
+    if ((im.x_table >= 0 || im.y_table >= 0) && !tables) return ODTK_ERR_INVALID;
+    if (!preprocess_axis_ok(im.x_table, im.x_taps, im.src_width, im.out_width, tables_len) ||
+        !preprocess_axis_ok(im.y_table, im.y_taps, im.src_height, im.out_height, tables_len))
+      return ODTK_ERR_INVALID;
+  }
+  return ODTK_OK;
+}
+
+int odtk_preprocess_images(int batch_size, const odtk_image_t *images, const void *src, size_t src_bytes, const int32_t *tables,
+                           size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *stream) {
+  if (!images || !src || !norm_table || !out || batch_size <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned es = dtype == ODTK_F32 ? 4u : 2u;
+  if ((reinterpret_cast<uintptr_t>(norm_table) | reinterpret_cast<uintptr_t>(out)) & (es - 1u)) return ODTK_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(tables) & 3u) return ODTK_ERR_INVALID;
+  if (3ull * height * width >= (1ull << 31) || (height + odtk::kPreTileH - 1) / odtk::kPreTileH > 65535) return ODTK_ERR_INVALID;
+  if (preprocess_images_ok(batch_size, images, src_bytes, tables, tables_len, height, width, true) != ODTK_OK) return ODTK_ERR_INVALID;
+  static_assert(sizeof(odtk::PreArgs) <= 4096, "kernel arguments travel by value");
+  odtk::PreArgs args;
+  args.bytes = nullptr;
+  args.sums = nullptr;
+  args.slot = 0;
+  args.src = static_cast<const uint8_t *>(src);
+  args.tables = tables;
+  args.norm = norm_table;
+  args.out = out;
+  args.height = height;
+  args.width = width;
+  args.vector_rows = ((3ull * width * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
+  const dim3 tiles((width + odtk::kPreTileW - 1) / odtk::kPreTileW, (height + odtk::kPreTileH - 1) / odtk::kPreTileH);
+  for (int first = 0; first < batch_size; first += odtk::kPreMaxImages) {   // one launch for batches of up to 64 images
+    const int n = batch_size - first < odtk::kPreMaxImages ? batch_size - first : odtk::kPreMaxImages;
+    args.first = first;
+    std::memcpy(args.images, images + first, sizeof(odtk_image_t) * n);
+    if (n < odtk::kPreMaxImages) std::memset(args.images + n, 0, sizeof(odtk_image_t) * (odtk::kPreMaxImages - n));
+    const dim3 grid(tiles.x, tiles.y, static_cast<unsigned>(n));
+    if (es == 4)
+      hipLaunchKernelGGL(odtk::preprocess_images_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), args);
+    else
+      hipLaunchKernelGGL(odtk::preprocess_images_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), args);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
+}
+
+int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const void *src, size_t src_bytes,
+                        const int32_t *tables, size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  if (batch_size <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (3ull * height * width >= (1ull << 31) || (height + odtk::kAugRows - 1) / odtk::kAugRows > 65535) return ODTK_ERR_INVALID;
+  // workspace: one 64-bit sum per image | one slot per image for its resized bytes (as many pixels as the canvas at most)
+  const size_t slot = align_up(3ull * height * width), off_bytes = align_up(sizeof(unsigned long long) * batch_size);
+  const size_t need = off_bytes + slot * batch_size;
+  if (need > 0x7fffffffull) return ODTK_ERR_INVALID;
+  if (!workspace) return static_cast<int>(need);
+  if (!images || !augments || !src || !norm_table || !out) return ODTK_ERR_INVALID;
+  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return ODTK_ERR_INVALID;
+  const unsigned es = dtype == ODTK_F32 ? 4u : 2u;
+  if ((reinterpret_cast<uintptr_t>(norm_table) | reinterpret_cast<uintptr_t>(out)) & (es - 1u)) return ODTK_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(tables) & 3u) return ODTK_ERR_INVALID;
+  if (preprocess_images_ok(batch_size, images, src_bytes, tables, tables_len, height, width, false) != ODTK_OK) return ODTK_ERR_INVALID;
+  int32_t max_w = 0, max_h = 0;
+  for (int b = 0; b < batch_size; ++b) {
+    const odtk_image_t &im = images[b];
+    const odtk_augment_t &au = augments[b];
+    if (im.mirror != 0) return ODTK_ERR_INVALID;                  // the flip is part of the map
+    if (3ull * im.out_width * im.out_height > slot) return ODTK_ERR_INVALID;
+    if ((im.out_height + odtk::kPreTileH - 1) / odtk::kPreTileH > 65535) return ODTK_ERR_INVALID;
+    if (au.canvas_width <= 0 || au.canvas_height <= 0 || au.canvas_width > width || au.canvas_height > height) return ODTK_ERR_INVALID;
+    if (au.flags & ~(ODTK_AUGMENT_BRIGHTNESS | ODTK_AUGMENT_CONTRAST | ODTK_AUGMENT_HUE | ODTK_AUGMENT_SATURATION)) return ODTK_ERR_INVALID;
+    if (au.pad_[0] | au.pad_[1] | au.pad_[2]) return ODTK_ERR_INVALID;
+    if (((au.flags & ODTK_AUGMENT_BRIGHTNESS) && !std::isfinite(au.brightness)) || ((au.flags & ODTK_AUGMENT_CONTRAST) && !std::isfinite(au.contrast)) ||
+        ((au.flags & ODTK_AUGMENT_SATURATION) && !std::isfinite(au.saturation)))
+      return ODTK_ERR_INVALID;
+    // the map is evaluated in 32-bit integers: it is affine, so its extremes over the canvas lie at the corners
+    for (int axis = 0; axis < 2; ++axis)
+      for (int corner = 0; corner < 4; ++corner) {
+        const long long x = (corner & 1) ? au.canvas_width - 1 : 0, y = (corner & 2) ? au.canvas_height - 1 : 0;
+        const long long px = 1ll * au.map[3 * axis] * x, py = 1ll * au.map[3 * axis + 1] * y;
+        const long long limit = 0x7fffffffll;
+        if (px > limit || px < -limit || py > limit || py < -limit) return ODTK_ERR_INVALID;
+        const long long partial = au.map[3 * axis + 2] + px, v = partial + py;
+        if (partial > limit || partial < -limit || v > limit || v < -limit) return ODTK_ERR_INVALID;
+      }
+    max_w = im.out_width > max_w ? im.out_width : max_w;
+    max_h = im.out_height > max_h ? im.out_height : max_h;
+  }
+  static_assert(sizeof(odtk::PreArgs) <= 4096 && sizeof(odtk::AugArgs) <= 4096, "kernel arguments travel by value");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  odtk::PreArgs pre;
+  pre.src = static_cast<const uint8_t *>(src);
+  pre.tables = tables;
+  pre.norm = nullptr;
+  pre.out = nullptr;
+  pre.height = max_h;
+  pre.width = max_w;
+  pre.vector_rows = 0;
+  pre.bytes = static_cast<uint8_t *>(workspace) + off_bytes;
+  pre.sums = static_cast<unsigned long long *>(workspace);
+  pre.slot = slot;
+  odtk::AugArgs aug;
+  aug.bytes = pre.bytes;
+  aug.sums = pre.sums;
+  aug.norm = norm_table;
+  aug.out = out;
+  aug.slot = slot;
+  aug.height = height;
+  aug.width = width;
+  aug.vector_rows = ((3ull * width * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
+  const unsigned group = 16u * (16u / es);                        // pixels per workgroup row of pass C
+  for (int first = 0; first < batch_size; first += odtk::kPreMaxImages) {   // one chain for batches of up to 64 images
+    const int n = batch_size - first < odtk::kPreMaxImages ? batch_size - first : odtk::kPreMaxImages;
+    pre.first = aug.first = first;
+    std::memset(pre.images, 0, sizeof(pre.images));
+    std::memcpy(pre.images, images + first, sizeof(odtk_image_t) * n);
+    std::memset(aug.images, 0, sizeof(aug.images));
+    bool contrast = false;
+    for (int i = 0; i < n; ++i) {
+      const odtk_augment_t &au = augments[first + i];
+      odtk::AugImage &d = aug.images[i];
+      d.cw = au.canvas_width;
+      d.ch = au.canvas_height;
+      d.rw = images[first + i].out_width;
+      d.rh = images[first + i].out_height;
+      std::memcpy(d.map, au.map, sizeof(d.map));
+      d.flags = au.flags;
+      d.brightness = au.brightness;
+      d.contrast = au.contrast;
+      d.saturation = au.saturation;
+      d.hue = au.hue;
+      contrast = contrast || (au.flags & ODTK_AUGMENT_CONTRAST);
+    }
+    const dim3 tiles((max_w + odtk::kPreTileW - 1) / odtk::kPreTileW, (max_h + odtk::kPreTileH - 1) / odtk::kPreTileH, static_cast<unsigned>(n));
+    hipLaunchKernelGGL((odtk::preprocess_images_kernel<4, true>), tiles, dim3(256), 0, s, pre);
+    ODTK_HIP_TRY(hipGetLastError());
+    if (contrast) {
+      hipLaunchKernelGGL(odtk::augment_luma_sum_kernel, dim3(odtk::kAugSumBlocks, 1, static_cast<unsigned>(n)), dim3(256), 0, s, aug);
+      ODTK_HIP_TRY(hipGetLastError());
+    }
+    const dim3 grid((width + group - 1) / group, (height + odtk::kAugRows - 1) / odtk::kAugRows, static_cast<unsigned>(n));
+    if (es == 4)
+      hipLaunchKernelGGL(odtk::augment_images_kernel<4>, grid, dim3(256), 0, s, aug);
+    else
+      hipLaunchKernelGGL(odtk::augment_images_kernel<2>, grid, dim3(256), 0, s, aug);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
+}
+
+}  // extern "C"

@@ -23,7 +23,7 @@
 // The forward is VALU-bound (fp16 heads take the same 30 us as fp32 ones, and an atomic-free reduction -- the workspace form
 // below -- measures the same): ~27 issue slots of arithmetic + ~5 of index math per logit, three of the instructions
 // quarter-rate (exp2, rcp, log2), against 39 T lane-operations/s.  Launch shapes: odtk_debug_loss_tuning, defaults in
-// odtk_hip.hip -- the forward with atomics wants few, large workgroups (every workgroup ends in a double atomic on its
+// train.hip -- the forward with atomics wants few, large workgroups (every workgroup ends in a double atomic on its
 // level's word: 2048 workgroups per level cost +80 us of queueing).
 // Arithmetic per element: loss.py's expressions in fp32, in the symmetric form derived at focal_term below (the sums
 // are accumulated in fp32 per lane over <= 32 elements, then in fp64): forward values agree with the torch expression

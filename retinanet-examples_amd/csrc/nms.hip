@@ -1,0 +1,252 @@
+// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "internal.hpp"
+#include "iou.hpp"
+#include "nms.hpp"
+#include "soft_nms.hpp"
+
+namespace {
+
+// axis-aligned NMS rounds: batched push (round 6, csrc/nms.hpp) or, ODTK_NMS_CHUNKS=1, the chunk loop of rounds 3-5 (A/B; same result)
+bool nms_chunk_mode() {
+  static const bool v = [] { const char *e = std::getenv("ODTK_NMS_CHUNKS"); return e && e[0] == '1'; }();
+  return v;
+}
+
+template <int NB, bool kGlobalKeys, int kStage = 0>
+int nms_launch(const odtk::NmsArgs &na, int batch, size_t lds, hipStream_t stream) {
+  // opt this kernel in to the full 160 KiB of LDS (once per device)
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(&odtk::nms_kernel<NB, kGlobalKeys, kStage>), 160 * 1024,
+                                   "hipFuncSetAttribute(nms_kernel)");
+  if (rc != ODTK_OK) return rc;
+  timed_launch(kStage == 1 ? ODTK_KERNEL_NMS_ORDER : ODTK_KERNEL_NMS, odtk::nms_kernel<NB, kGlobalKeys, kStage>, dim3(batch),
+               dim3(odtk::kNmsThreads), lds, stream, na);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+// rotated boxes: first round in order -> pairwise suppression matrix on the whole chip -> resolve (csrc/nms.hpp)
+template <bool kGlobalKeys>
+int nms_rotated_staged(odtk::NmsArgs na, int batch, size_t lds, hipStream_t stream) {
+  int rc = nms_launch<6, kGlobalKeys, 1>(na, batch, lds, stream);
+  if (rc != ODTK_OK) return rc;
+  odtk::SupArgs sa;
+  sa.first_box = na.first_box; sa.first_cls = na.first_cls; sa.first_n = na.first_n; sa.sup = na.sup;
+  sa.m_max = na.m_max; sa.thresh = na.thresh; sa.flags = na.flags;
+  auto matrix = [&](uint32_t m_launch, uint32_t m_done, const uint32_t *done) {
+    sa.m_launch = m_launch; sa.m_done = m_done; sa.done = done;
+    const unsigned nblk = m_launch / 64;
+    timed_launch(ODTK_KERNEL_NMS_MATRIX, odtk::rotated_sup_matrix_kernel, dim3(nblk * (nblk + 1) / 2 * (64 / odtk::kSupRows), batch),
+                 dim3(odtk::kSupThreads), 0, stream, sa);
+  };
+  if (na.m_first >= na.m_max) {                              // the matrix is small: one step
+    na.step = 0;
+    matrix(na.m_max, 0, nullptr);
+    ODTK_HIP_TRY(hipGetLastError());
+    return nms_launch<6, kGlobalKeys, 2>(na, batch, lds, stream);
+  }
+  // two-step speculation: the pairs of the first m_first candidates, a resolve that stops there; only the images it did not
+  // finish pay for the rest of the matrix and a second resolve (the other workgroups of those two launches leave at once)
+  matrix(na.m_first, 0, nullptr);
+  ODTK_HIP_TRY(hipGetLastError());
+  na.step = 1;
+  rc = nms_launch<6, kGlobalKeys, 2>(na, batch, lds, stream);
+  if (rc != ODTK_OK) return rc;
+  matrix(na.m_max, na.m_first, na.done);
+  ODTK_HIP_TRY(hipGetLastError());
+  na.step = 2;
+  return nms_launch<6, kGlobalKeys, 2>(na, batch, lds, stream);
+}
+
+// ... and what the first of two matrix launches covers: 2.5 x detections_per_im (a detector whose boxes are well separated
+// examines 1.5 .. 2.5 x as many candidates as it keeps), at least four chunks
+uint32_t rotated_matrix_first(uint32_t m_max, int ndet) {
+  size_t m = static_cast<size_t>(ndet) * 5 / 2;
+  if (m < 256) m = 256;
+  m = (m + 63) / 64 * 64;
+  return m > m_max ? m_max : static_cast<uint32_t>(m);
+}
+
+// candidates of the first round the rotated suppression matrix covers: 8 x detections_per_im (the lazy pull of a typical
+// image examines 1.5 .. 7 x as many candidates as it keeps), whole 64-candidate chunks, at most one round
+// ... and as many as the resolve kernel can hold in LDS: it keeps the matrix (m x m / 64 words) where the polygon clip's
+// columns will be once the first pair beyond the matrix is clipped (`ways` x 4 KiB: 704 candidates at 16 ways)
+uint32_t rotated_matrix_rows(size_t count, int ndet, int ways) {
+  size_t m = static_cast<size_t>(ndet) * 8;
+  if (m > count) m = count;
+  if (m > static_cast<size_t>(odtk::kNmsRound)) m = odtk::kNmsRound;
+  m = (m + 63) / 64 * 64;
+  const size_t room = static_cast<size_t>(ways) * odtk::kClipSlotsPerWave * sizeof(float2);
+  while (m > 64 && m * (m / 64) * sizeof(uint64_t) > room) m -= 64;
+  return static_cast<uint32_t>(m);
+}
+
+// Soft-NMS (csrc/soft_nms.hpp): one workgroup per image, boxes and classes in count x 20 bytes of dynamic LDS
+template <bool kGaussian>
+int soft_nms_launch(const odtk::SoftNmsArgs &sa, int batch, hipStream_t stream) {
+  const size_t lds = odtk::soft_nms_lds_bytes(sa.count);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(&odtk::soft_nms_kernel<kGaussian>), odtk::soft_nms_lds_bytes(ODTK_MAX_NMS_COUNT),
+                                   "hipFuncSetAttribute(soft_nms_kernel)");
+  if (rc != ODTK_OK) return rc;
+  timed_launch(ODTK_KERNEL_NMS, odtk::soft_nms_kernel<kGaussian>, dim3(batch), dim3(odtk::kSoftThreads), lds, stream, sa);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+}  // namespace
+
+int nms_impl(int batch, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+             int ndet, float thresh, uint32_t flags, void *workspace, size_t workspace_size, hipStream_t stream,
+             uint32_t sorted_run_len, const uint32_t *run_valid) {
+  if (batch <= 0 || count == 0 || count > ODTK_MAX_NMS_COUNT_SCRATCH || ndet <= 0 || ndet > ODTK_MAX_NMS_DETECTIONS)
+    return ODTK_ERR_INVALID;
+  // up to ODTK_MAX_NMS_COUNT candidates per image everything is LDS-resident and the kernel needs no global scratch
+  // (a token size keeps the reference's two-phase calling convention working unchanged); beyond that the key list
+  // of every image lives in the workspace
+  const int nb = (flags & ODTK_FLAG_ROTATED) ? 6 : 4;
+  // ... or when the LDS-resident form does not fit next to a long kept list (detections_per_im in the thousands), or -- rotated
+  // -- would leave fewer than 8 of the 16 waves a polygon-clip column (they are what evaluates box pairs)
+  const odtk::NmsLds local(static_cast<uint32_t>(count > ODTK_MAX_NMS_COUNT ? 1 : count), ndet, nb, false);
+  const bool global_keys = count > ODTK_MAX_NMS_COUNT || local.total > odtk::NmsLds::kLdsBudget || (nb == 6 && local.ways < 8);
+  const size_t keys_bytes = global_keys ? align_up(sizeof(uint64_t) * static_cast<size_t>(batch) * count) : kAlign;
+  // rotated: [first-round boxes | classes | counts | suppression matrix] behind the keys
+  const uint32_t m_max = nb == 6 ? rotated_matrix_rows(count, ndet, odtk::NmsLds(static_cast<uint32_t>(global_keys ? 1 : count), ndet, nb, global_keys).ways) : 0u;
+  const size_t off_fb = keys_bytes;
+  const size_t off_fc = off_fb + (nb == 6 ? align_up(sizeof(float) * 6 * batch * m_max) : 0);
+  const size_t off_fn = off_fc + (nb == 6 ? align_up(sizeof(float) * batch * m_max) : 0);
+  const size_t off_fk = off_fn + (nb == 6 ? align_up(sizeof(uint32_t) * batch) : 0);
+  const size_t off_fs = off_fk + (nb == 6 ? align_up(sizeof(uint64_t) * batch * odtk::kNmsRound) : 0);
+  const size_t off_sup = off_fs + (nb == 6 ? align_up(sizeof(uint32_t) * 16 * batch) : 0);
+  const size_t off_done = off_sup + (nb == 6 ? align_up(sizeof(uint64_t) * batch * m_max * (m_max / 64)) : 0);
+  const size_t need = off_done + (nb == 6 ? align_up(sizeof(uint32_t) * batch) : 0);
+  if (need > 0x7fffffffull) return ODTK_ERR_INVALID;
+  if (!workspace || !workspace_size) return static_cast<int>(need);
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!inputs || !outputs || n_outputs < 3) return ODTK_ERR_INVALID;
+  for (int i = 0; i < 3; ++i)
+    if (!inputs[i] || !outputs[i]) return ODTK_ERR_INVALID;
+  odtk::NmsArgs na;
+  std::memset(&na, 0, sizeof na);
+  na.scores = static_cast<const float *>(inputs[0]);
+  na.boxes = static_cast<const float *>(inputs[1]);
+  na.classes = static_cast<const float *>(inputs[2]);
+  na.out_scores = static_cast<float *>(outputs[0]);
+  na.out_boxes = static_cast<float *>(outputs[1]);
+  na.out_classes = static_cast<float *>(outputs[2]);
+  na.out_indices = n_outputs > 3 ? static_cast<int32_t *>(outputs[3]) : nullptr;
+  na.count = static_cast<uint32_t>(count);
+  na.run_len = sorted_run_len;
+  na.run_valid = run_valid;
+  na.ndet = ndet;
+  na.thresh = thresh;
+  na.flags = flags | (nms_chunk_mode() ? odtk::kNmsFlagChunks : 0u);
+  na.trace = g_trace ? g_trace + 8 * 64 : nullptr;          // after the select_decode slots
+  na.key_scratch = global_keys ? static_cast<uint64_t *>(workspace) : nullptr;
+  const size_t lds = odtk::NmsLds(na.count, ndet, nb, global_keys).total;   // same carve-up the kernel computes
+  if (lds > 160 * 1024) return ODTK_ERR_INVALID;
+  if (nb == 6) {
+    char *ws = static_cast<char *>(workspace);
+    na.first_box = reinterpret_cast<float *>(ws + off_fb);
+    na.first_cls = reinterpret_cast<float *>(ws + off_fc);
+    na.first_n = reinterpret_cast<uint32_t *>(ws + off_fn);
+    na.first_keys = reinterpret_cast<unsigned long long *>(ws + off_fk);
+    na.first_state = reinterpret_cast<uint32_t *>(ws + off_fs);
+    na.sup = reinterpret_cast<unsigned long long *>(ws + off_sup);
+    na.m_max = m_max;
+    na.m_first = rotated_matrix_first(m_max, ndet);
+    na.done = reinterpret_cast<uint32_t *>(ws + off_done);
+    return global_keys ? nms_rotated_staged<true>(na, batch, lds, stream) : nms_rotated_staged<false>(na, batch, lds, stream);
+  }
+  return global_keys ? nms_launch<4, true>(na, batch, lds, stream) : nms_launch<4, false>(na, batch, lds, stream);
+}
+
+extern "C" {
+
+int odtk_nms(int batch_size, const void *const *inputs, void *const *outputs, size_t count,
+             int detections_per_im, float nms_thresh, void *workspace, size_t workspace_size, void *stream) {
+  return nms_impl(batch_size, inputs, outputs, 3, count, detections_per_im, nms_thresh, 0u, workspace,
+                  workspace_size, static_cast<hipStream_t>(stream));
+}
+
+int odtk_nms_rotate(int batch_size, const void *const *inputs, void *const *outputs, size_t count,
+                    int detections_per_im, float nms_thresh, void *workspace, size_t workspace_size,
+                    void *stream) {
+  return nms_impl(batch_size, inputs, outputs, 3, count, detections_per_im, nms_thresh, ODTK_FLAG_ROTATED,
+                  workspace, workspace_size, static_cast<hipStream_t>(stream));
+}
+
+int odtk_nms_ex(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                int detections_per_im, float nms_thresh, uint32_t flags, void *workspace,
+                size_t workspace_size, void *stream) {
+  return nms_impl(batch_size, inputs, outputs, n_outputs, count, detections_per_im, nms_thresh, flags,
+                  workspace, workspace_size, static_cast<hipStream_t>(stream));
+}
+
+int odtk_nms_sorted_runs(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                         int run_len, const uint32_t *run_valid, int detections_per_im, float nms_thresh, uint32_t flags,
+                         void *workspace, size_t workspace_size, void *stream) {
+  if (run_len <= 0 || count % static_cast<size_t>(run_len) != 0 || count / run_len > 8) return ODTK_ERR_INVALID;
+  if (workspace && workspace_size && !run_valid) return ODTK_ERR_INVALID;
+  return nms_impl(batch_size, inputs, outputs, n_outputs, count, detections_per_im, nms_thresh, flags, workspace, workspace_size,
+                  static_cast<hipStream_t>(stream), static_cast<uint32_t>(run_len), run_valid);
+}
+
+// everything is validated here, on the host, before anything touches the device
+int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                  int detections_per_im, float nms_thresh, int method, float sigma, float min_score, uint32_t flags,
+                  void *workspace, size_t workspace_size, void *stream) {
+  if (batch_size <= 0 || count == 0 || detections_per_im <= 0 || detections_per_im > ODTK_MAX_NMS_DETECTIONS) return ODTK_ERR_INVALID;
+  if (method != ODTK_SOFT_NMS_LINEAR && method != ODTK_SOFT_NMS_GAUSSIAN) return ODTK_ERR_INVALID;
+  if (!std::isfinite(sigma) || !(sigma > 0.0f) || !std::isfinite(min_score) || !(min_score > 0.0f)) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  if (count > ODTK_MAX_NMS_COUNT) return ODTK_ERR_UNSUPPORTED;
+  // nothing lives in global scratch: a token size keeps the two-phase calling convention
+  const size_t need = kAlign;
+  if (!workspace || !workspace_size) return static_cast<int>(need);
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!inputs || !outputs || n_outputs < 3) return ODTK_ERR_INVALID;
+  for (int i = 0; i < 3; ++i)
+    if (!inputs[i] || !outputs[i]) return ODTK_ERR_INVALID;
+  odtk::SoftNmsArgs sa;
+  std::memset(&sa, 0, sizeof sa);
+  sa.scores = static_cast<const float *>(inputs[0]);
+  sa.boxes = static_cast<const float *>(inputs[1]);
+  sa.classes = static_cast<const float *>(inputs[2]);
+  sa.out_scores = static_cast<float *>(outputs[0]);
+  sa.out_boxes = static_cast<float *>(outputs[1]);
+  sa.out_classes = static_cast<float *>(outputs[2]);
+  sa.out_indices = n_outputs > 3 ? static_cast<int32_t *>(outputs[3]) : nullptr;
+  sa.count = static_cast<uint32_t>(count);
+  sa.ndet = detections_per_im;
+  sa.thresh = nms_thresh;
+  sa.sigma = sigma;
+  sa.min_score = min_score;
+  return method == ODTK_SOFT_NMS_GAUSSIAN ? soft_nms_launch<true>(sa, batch_size, static_cast<hipStream_t>(stream))
+                                          : soft_nms_launch<false>(sa, batch_size, static_cast<hipStream_t>(stream));
+}
+
+int odtk_iou(const void *const *inputs, void *const *outputs, int num_boxes, int num_anchors, void *stream) {
+  if (num_boxes < 0 || num_anchors < 0) return ODTK_ERR_INVALID;
+  const long long pairs = 1ll * num_boxes * num_anchors;
+  if (pairs == 0) return ODTK_OK;                            // empty side: nothing to write
+  if (!inputs || !outputs || !inputs[0] || !inputs[1] || !outputs[0]) return ODTK_ERR_INVALID;
+  if (pairs > 0x7fffffffll) return ODTK_ERR_INVALID;
+  const int threads = 256;
+  long long blocks = (pairs + threads - 1) / threads;
+  if (blocks > 256 * 16) blocks = 256 * 16;                  // grid-stride beyond 16 workgroups per CU
+  {
+    KernelTimer t(ODTK_KERNEL_IOU, static_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(odtk::iou_pairs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(threads), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const float *>(inputs[0]),
+                       static_cast<const float *>(inputs[1]), static_cast<float *>(outputs[0]), num_boxes,
+                       num_anchors);
+  }
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+}  // extern "C"

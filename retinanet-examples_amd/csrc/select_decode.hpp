@@ -395,6 +395,11 @@ __device__ void bitonic_sort_desc_regs(uint64_t *s_keys) {
   __syncthreads();
 }
 
+// The 4096-key network is the one piece of device code that stays out of line (a call from every select_decode and nms
+// kernel, ~3 700 instructions each copy).  __noinline__ keeps it a call whichever kernels a source instantiates: the inliner
+// absorbs it where only the six nms kernels call it.
+__device__ __noinline__ void bitonic_sort_desc_4096(uint64_t *s_keys) { bitonic_sort_desc_regs<4>(s_keys); }
+
 // Sorts s_keys[0..n_valid) descending; entries up to the padded size are zeroed (sort last).
 // The buffer must hold max(1024, pow2(n_valid)) <= kSortCapBig keys.
 template <int kMaxKeys = 4096>
@@ -405,7 +410,7 @@ __device__ __forceinline__ void sort_keys_desc(uint64_t *s_keys, uint32_t n_vali
   __syncthreads();
   if (n_pad == kSelThreads) bitonic_sort_desc_regs<1>(s_keys);
   else if (n_pad == 2 * kSelThreads) bitonic_sort_desc_regs<2>(s_keys);
-  else if (n_pad == 4 * kSelThreads || kMaxKeys <= 4 * kSelThreads) bitonic_sort_desc_regs<4>(s_keys);
+  else if (n_pad == 4 * kSelThreads || kMaxKeys <= 4 * kSelThreads) bitonic_sort_desc_4096(s_keys);
   else if constexpr (kMaxKeys > 4 * kSelThreads) {           // only the top_n > 4096 variant carries the big networks
     if (n_pad == 8 * kSelThreads) bitonic_sort_desc_regs<8>(s_keys);
     else bitonic_sort_desc_regs<16>(s_keys);

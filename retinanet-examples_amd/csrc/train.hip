@@ -1,0 +1,390 @@
+// train.hip -- target assignment (odtk_snap_to_anchors*) and the focal + smooth-L1 loss: launch shapes, odtk_debug_loss_*,
+// odtk_retina_loss_*.
+#include <cstring>
+#include <mutex>
+
+#include "runtime.hpp"
+#include "targets.hpp"
+#include "loss.hpp"
+
+namespace {
+
+// Launch shape of the loss kernels (odtk_debug_loss_tuning; defaults = the measured best):
+// workgroup size, resident workgroups per CU the logit walk is capped at, 16-byte vectors a lane loads per trip.
+struct LossTuning {
+  int threads, per_cu, unroll, box_blocks;
+  int per_wave, window, box_rows;   // odtk_debug_loss_layout: per-wave sums (workspace form only), contiguous trips, the backward's
+                                    // box-delta walk in memory order (csrc/loss.hpp LossArgs)
+  int form;   // filled by loss_tuning_snapshot from g_loss_form (odtk_debug_loss_form): 1 = vectors of negatives take focal_plain
+};
+// [16-bit heads, fp32 heads][forward with atomics, backward, forward through a workspace] = threads, logit workgroups per
+// CU and level, vectors per trip, box workgroups per level; measured with tools/loss_probe.py (profiles/r03_loss_probe.txt)
+enum { kLossFwd = 0, kLossBwd = 1, kLossFwdWs = 2 };
+std::mutex g_loss_tuning_mu;
+// Round 6 (profiles/r06_loss_layout_probe.txt): the backward walks contiguous trips (window 1) with 256-thread workgroups and
+// writes d(deltas) in memory order -- fp32 50.6 -> 42.6-43.1 us, bf16 34.3 -> 27.4 us.
+// The forward through the workspace walks contiguous trips too (fp32: two vectors per trip); per-wave sums stay off (walk -1.3 us,
+// reduce launch +0.8 us: nothing).
+LossTuning g_loss_tuning[2][3] = {{{512, 1, 2, 64, 0, 0, 1, 0}, {256, 4, 1, 256, 0, 1, 1, 0}, {256, 4, 1, 256, 0, 1, 1, 0}},
+                                  {{512, 1, 4, 64, 0, 0, 1, 0}, {256, 8, 2, 1024, 0, 1, 1, 0}, {256, 4, 2, 256, 0, 1, 1, 0}}};
+
+// Arithmetic form of the classification walk with gamma = 2 (csrc/loss.hpp focal_plain): 0 = every element through the
+// symmetric focal_term (rounds 3-4), 1 = vectors that hold no positive element and no logit beyond kPlainMax through
+// focal_plain.  Same sums to ~1e-8, same gradients to ~1e-6 of the largest (both well inside the tested bars).
+int g_loss_form = ODTK_LOSS_FORM_DEFAULT;
+
+LossTuning loss_tuning_snapshot(int dtype, int which) {
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  LossTuning t = g_loss_tuning[dtype == ODTK_F32][which];
+  t.form = g_loss_form;
+  return t;
+}
+
+// fills the kernel arguments of one level; returns the number of workgroups it wants (0 on error, *rc set)
+unsigned retina_loss_fill(odtk::LossArgs &la, int which, const void *cls, const void *box, const float *depth,
+                          const float *box_target, int batch, int A, int C, int height, int width, int nb, int dtype,
+                          int channels_last, float alpha, float gamma, float beta, double *sums, const float *g_cls,
+                          const float *g_box, void *dcls, void *dbox, const LossTuning &t, int *rc) {
+  const bool backward = which == kLossBwd;
+  *rc = ODTK_ERR_INVALID;
+  if (!cls || !box || !depth || !box_target || batch <= 0 || A <= 0 || C <= 0 || height <= 0 || width <= 0 || nb <= 0) return 0;
+  if (channels_last != 0 && channels_last != 1) return 0;
+  if ((reinterpret_cast<uintptr_t>(cls) | reinterpret_cast<uintptr_t>(box)) & 15u) return 0;   // 16-B vector loads
+  if (backward && (!dcls || !dbox || ((reinterpret_cast<uintptr_t>(dcls) | reinterpret_cast<uintptr_t>(dbox)) & 15u))) return 0;
+  const unsigned long long n = 1ull * batch * A * C * height * width;
+  if (n >= (1ull << 32)) return 0;
+  if (1ull * batch * A * nb * height * width >= (1ull << 32)) return 0;
+  std::memset(&la, 0, sizeof la);
+  la.cls = cls; la.box = box; la.depth = depth; la.box_target = box_target;
+  la.acc = sums; la.g_cls = g_cls; la.g_box = g_box; la.dcls = dcls; la.dbox = dbox;
+  la.batch = batch; la.num_anchors = A; la.num_classes = C; la.hw = static_cast<uint32_t>(height) * width; la.nb = nb;
+  la.channels_last = channels_last;
+  la.alpha = alpha; la.gamma = gamma; la.beta = beta;
+  la.by_channels = odtk::fastdiv_make(static_cast<uint32_t>(A) * C);
+  la.by_hw = odtk::fastdiv_make(la.hw);
+  la.by_classes = odtk::fastdiv_make(C);
+  la.by_anchors = odtk::fastdiv_make(A);
+  const unsigned threads = t.threads, unroll = t.unroll;
+  const unsigned per = dtype == ODTK_F32 ? 4u : 8u;
+  // at least two trips of `unroll` vectors per lane where the level is large enough
+  unsigned long long cls_blocks = (n / per + threads * unroll * 2ull - 1) / (threads * unroll * 2ull);
+  if (cls_blocks < 1) cls_blocks = 1;
+  // forward: every block ends in (up to) three double atomics on the SAME three words of its level, ~11 ns each when
+  // they queue up (MI355X_MICROARCH.md "fanin") -- 4096 blocks cost 40 us of pure queueing per launch, and the ~2 800
+  // box-delta blocks of round 2 (one cell per lane, two atomics each) cost ~30 us on their own: the forward launch
+  // keeps both kinds of workgroup few (a lane walks several vectors / cells); backward has no such tail.
+  // The cap is PER LEVEL: dealing one budget to the levels in proportion to their size (P3 = 3/4 of the logits) was
+  // measured slower -- 768 atomics on P3's word instead of 256 (profiles/r03_loss_probe_proportional_dealing.txt).
+  const unsigned long long block_cap = 256ull * t.per_cu;
+  if (cls_blocks > block_cap) cls_blocks = block_cap;
+  unsigned long long box_blocks = (1ull * batch * A * height * width + threads - 1) / threads;
+  if (box_blocks > static_cast<unsigned>(t.box_blocks)) box_blocks = t.box_blocks;
+  la.cls_blocks = static_cast<uint32_t>(cls_blocks);
+  la.per_wave = (which == kLossFwdWs && t.per_wave) ? 1u : 0u;
+  la.window = t.window ? 1u : 0u;
+  la.box_rows = t.box_rows ? 1u : 0u;
+  *rc = ODTK_OK;
+  return static_cast<unsigned>(cls_blocks + box_blocks);
+}
+
+template <typename T, bool kBackward>
+void retina_loss_dispatch(const odtk::LossLevelsArgs &la, unsigned total, const LossTuning &t, hipStream_t stream) {
+  const dim3 grid(total), block(t.threads);
+#ifdef ODTK_LOSS_ABLATIONS   // build flag of tools/loss_form_probe.py only (make ablations): never in the shipped library
+  if constexpr (std::is_same_v<T, odtk::F32> && !kBackward) {
+    // timing ablations of form 1 (wrong results on purpose; tools/loss_form_probe.py): fp32 forward, four vectors per trip
+    if (t.form == 2) { timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, false, 4, 2>, grid, block, 0, stream, la); return; }
+    if (t.form == 3) { timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, false, 4, 3>, grid, block, 0, stream, la); return; }
+    if (t.form == 4) { timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, false, 4, 4>, grid, block, 0, stream, la); return; }
+    if (t.form == 6) { timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, false, 4, 6>, grid, block, 0, stream, la); return; }
+    if (t.form == 7) { timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, false, 4, 7>, grid, block, 0, stream, la); return; }
+  }
+#endif
+  if (t.form) {
+    switch (t.unroll) {
+      case 1: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 1, 1>, grid, block, 0, stream, la); break;
+      case 2: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 2, 1>, grid, block, 0, stream, la); break;
+      default: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 4, 1>, grid, block, 0, stream, la); break;
+    }
+    return;
+  }
+  switch (t.unroll) {
+    case 1: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 1, 0>, grid, block, 0, stream, la); break;
+    case 2: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 2, 0>, grid, block, 0, stream, la); break;
+    default: timed_launch(ODTK_KERNEL_LOSS, odtk::retina_loss_kernel<T, kBackward, 4, 0>, grid, block, 0, stream, la); break;
+  }
+}
+
+// which: kLossFwd (atomics into `sums`, pre-zeroed), kLossBwd, kLossFwdWs (per-workgroup sums into `partial`, then the
+// reduce launch writes `sums`).  With partial == nullptr and kLossFwdWs: returns the number of workgroups (size query).
+int retina_loss_levels_launch(int which, int n_levels, const odtk_loss_level_t *levels, int batch, int A, int C, int nb,
+                              int dtype, float alpha, float gamma, float beta, double *sums, const float *g_cls,
+                              const float *g_box, double *partial, bool query, hipStream_t stream,
+                              const LossTuning *tuning = nullptr) {
+  if (n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || !levels) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const bool backward = which == kLossBwd;
+  // ONE snapshot of the launch shape per call: the size query and the launch of the workspace form must agree even if
+  // odtk_debug_loss_tuning runs on another thread in between
+  const LossTuning t = tuning ? *tuning : loss_tuning_snapshot(dtype, which);
+  odtk::LossLevelsArgs la;
+  std::memset(&la, 0, sizeof la);
+  la.n_levels = n_levels;
+  unsigned total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    int rc;
+    const unsigned blocks = retina_loss_fill(la.lv[l], which, levels[l].cls, levels[l].box, levels[l].depth, levels[l].box_target,
+                                             batch, A, C, levels[l].height, levels[l].width, nb, dtype, levels[l].channels_last,
+                                             alpha, gamma, beta, sums ? sums + 3 * l : nullptr, g_cls ? g_cls + l : nullptr,
+                                             g_box ? g_box + l : nullptr, levels[l].dcls, levels[l].dbox, t, &rc);
+    if (rc != ODTK_OK) return rc;
+    la.lv[l].partial = which == kLossFwdWs ? partial : nullptr;
+    la.block_begin[l] = total;
+    total += blocks;
+  }
+  for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) la.block_begin[l] = total;
+  if (query) return static_cast<int>(total);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    backward ? retina_loss_dispatch<T, true>(la, total, t, stream) : retina_loss_dispatch<T, false>(la, total, t, stream);
+  });
+  ODTK_HIP_TRY(hipGetLastError());
+  if (which == kLossFwdWs) {
+    odtk::LossReduceArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.partial = partial;
+    ra.per = t.per_wave ? static_cast<uint32_t>(t.threads) / 64u : 1u;
+    ra.sums = sums;
+    for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = la.block_begin[l];
+    timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::loss_reduce_kernel, dim3(n_levels), dim3(odtk::kLossReduceThreads), 0, stream, ra);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
+}
+
+// one level = a one-entry level table through the same kernel
+int retina_loss_launch(bool backward, const void *cls, const void *box, const float *depth, const float *box_target,
+                       int batch, int A, int C, int height, int width, int nb, int dtype, int channels_last, float alpha,
+                       float gamma, float beta, double *sums, const float *g_cls, const float *g_box, void *dcls,
+                       void *dbox, hipStream_t stream) {
+  odtk_loss_level_t lv;
+  std::memset(&lv, 0, sizeof lv);
+  lv.cls = cls; lv.box = box; lv.depth = depth; lv.box_target = box_target;
+  lv.dcls = dcls; lv.dbox = dbox;
+  lv.height = height; lv.width = width; lv.channels_last = channels_last;
+  return retina_loss_levels_launch(backward ? kLossBwd : kLossFwd, 1, &lv, batch, A, C, nb, dtype, alpha, gamma, beta, sums, g_cls, g_box,
+                                   nullptr, false, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int odtk_debug_loss_tuning(int which, int fp32_heads, int threads, int blocks_per_cu, int unroll, int box_blocks) {
+  if (which < 0 || which > 2 || threads < 64 || threads > odtk::kLossMaxThreads || threads % 64 || blocks_per_cu < 1 ||
+      blocks_per_cu > 64 || (unroll != 1 && unroll != 2 && unroll != 4) || box_blocks < 1 || box_blocks > 16384)
+    return ODTK_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  LossTuning &t = g_loss_tuning[fp32_heads != 0][which];
+  t.threads = threads; t.per_cu = blocks_per_cu; t.unroll = unroll; t.box_blocks = box_blocks;   // (the layout switches stay)
+  return ODTK_OK;
+}
+
+int odtk_debug_loss_layout(int which, int fp32_heads, int per_wave, int window, int box_rows) {
+  if (which < 0 || which > 2 || (per_wave != 0 && per_wave != 1) || (window != 0 && window != 1) || (box_rows != 0 && box_rows != 1))
+    return ODTK_ERR_INVALID;
+  if (per_wave && which != kLossFwdWs) return ODTK_ERR_INVALID;   // per-wave sums exist in the workspace form only
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  LossTuning &t = g_loss_tuning[fp32_heads != 0][which];
+  t.per_wave = per_wave; t.window = window; t.box_rows = box_rows;
+  return ODTK_OK;
+}
+
+int odtk_debug_loss_tuning_get(int which, int fp32_heads, int out[7]) {
+  if (which < 0 || which > 2 || !out) return ODTK_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  const LossTuning &t = g_loss_tuning[fp32_heads != 0][which];
+  out[0] = t.threads; out[1] = t.per_cu; out[2] = t.unroll; out[3] = t.box_blocks;
+  out[4] = t.per_wave; out[5] = t.window; out[6] = t.box_rows;
+  return ODTK_OK;
+}
+
+int odtk_debug_loss_form_get(void) {
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  return g_loss_form;
+}
+
+int odtk_debug_loss_form(int form) {
+#ifdef ODTK_LOSS_ABLATIONS
+  if (form < 0 || form > 7 || form == 5) return ODTK_ERR_INVALID;
+#else
+  if (form != 0 && form != 1) return ODTK_ERR_INVALID;   // the ablation forms (wrong sums on purpose) are not compiled in
+#endif
+  std::lock_guard<std::mutex> lock(g_loss_tuning_mu);
+  g_loss_form = form;
+  return ODTK_OK;
+}
+
+int odtk_snap_to_anchors(int batch_size, const float *targets, int n_max, const float *anchors, int num_anchors,
+                         int num_classes, int height, int width, int stride, float iou_background,
+                         float iou_foreground, float *cls_target, float *box_target, float *depth, void *stream) {
+  if (batch_size <= 0 || n_max < 0 || num_anchors <= 0 || num_anchors > ODTK_MAX_ANCHORS || num_classes <= 0 ||
+      height <= 0 || width <= 0)
+    return ODTK_ERR_INVALID;
+  if (!anchors || !box_target || !depth || (n_max > 0 && !targets)) return ODTK_ERR_INVALID;   // cls_target may be null
+  odtk::SnapArgs sa;
+  std::memset(&sa, 0, sizeof sa);
+  sa.targets = targets;
+  sa.cls_target = cls_target;
+  sa.box_target = box_target;
+  sa.depth = depth;
+  sa.n_max = n_max;
+  sa.num_anchors = num_anchors;
+  sa.num_classes = num_classes;
+  sa.height = height;
+  sa.width = width;
+  sa.stride = static_cast<float>(stride);
+  sa.iou_bg = iou_background;
+  sa.iou_fg = iou_foreground;
+  std::memcpy(sa.anchors, anchors, sizeof(float) * 4 * num_anchors);
+  const long long cells = 1ll * num_anchors * height * width;
+  const unsigned blocks = static_cast<unsigned>((cells + odtk::kSnapThreads - 1) / odtk::kSnapThreads);
+  {
+    KernelTimer t(ODTK_KERNEL_TARGETS, static_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(odtk::snap_to_anchors_kernel, dim3(blocks, batch_size), dim3(odtk::kSnapThreads), 0,
+                       static_cast<hipStream_t>(stream), sa);
+  }
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_snap_to_anchors_levels(int batch_size, const float *targets, int n_max, int n_levels,
+                                const odtk_snap_level_t *levels, int num_anchors, int num_classes,
+                                float iou_background, float iou_foreground, void *stream) {
+  if (batch_size <= 0 || n_max < 0 || n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || !levels || num_anchors <= 0 ||
+      num_anchors > ODTK_MAX_ANCHORS || num_classes <= 0 || (n_max > 0 && !targets))
+    return ODTK_ERR_INVALID;
+  odtk::SnapLevelsArgs la;
+  std::memset(&la, 0, sizeof la);
+  la.n_levels = n_levels;
+  unsigned total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const odtk_snap_level_t &lv = levels[l];
+    if (!lv.anchors || !lv.box_target || !lv.depth || lv.height <= 0 || lv.width <= 0) return ODTK_ERR_INVALID;
+    odtk::SnapArgs &sa = la.lv[l];
+    sa.targets = targets;
+    sa.cls_target = lv.cls_target;
+    sa.box_target = lv.box_target;
+    sa.depth = lv.depth;
+    sa.n_max = n_max;
+    sa.num_anchors = num_anchors;
+    sa.num_classes = num_classes;
+    sa.height = lv.height;
+    sa.width = lv.width;
+    sa.stride = static_cast<float>(lv.stride);
+    sa.iou_bg = iou_background;
+    sa.iou_fg = iou_foreground;
+    std::memcpy(sa.anchors, lv.anchors, sizeof(float) * 4 * num_anchors);
+    la.block_begin[l] = total;
+    const long long cells = 1ll * num_anchors * lv.height * lv.width;
+    total += static_cast<unsigned>((cells + odtk::kSnapThreads - 1) / odtk::kSnapThreads);
+  }
+  for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) la.block_begin[l] = total;
+  timed_launch(ODTK_KERNEL_TARGETS, odtk::snap_to_anchors_levels_kernel, dim3(total, batch_size), dim3(odtk::kSnapThreads), 0,
+               static_cast<hipStream_t>(stream), la);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_snap_to_anchors_rotated_levels(int batch_size, const float *gt_axis, const float *gt_quads, const float *gt_class,
+                                        int n_max, int n_levels, const odtk_snap_rot_level_t *levels, int num_anchors,
+                                        int num_classes, float iou_background, float iou_foreground, void *stream) {
+  if (batch_size <= 0 || n_max < 0 || n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || !levels || num_anchors <= 0 ||
+      num_classes <= 0 || (n_max > 0 && (!gt_axis || !gt_quads || !gt_class)))
+    return ODTK_ERR_INVALID;
+  odtk::SnapRotLevelsArgs la;
+  std::memset(&la, 0, sizeof la);
+  la.n_levels = n_levels;
+  unsigned total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const odtk_snap_rot_level_t &lv = levels[l];
+    if (!lv.anchors_axis || !lv.anchors_quads || !lv.box_target || !lv.depth || lv.height <= 0 || lv.width <= 0) return ODTK_ERR_INVALID;
+    odtk::SnapRotArgs &sa = la.lv[l];
+    sa.gt_axis = gt_axis; sa.gt_quads = gt_quads; sa.gt_class = gt_class;
+    sa.anchors_axis = lv.anchors_axis; sa.anchors_rot = lv.anchors_quads;
+    sa.cls_target = lv.cls_target; sa.box_target = lv.box_target; sa.depth = lv.depth;
+    sa.n_max = n_max; sa.num_anchors = num_anchors; sa.num_classes = num_classes;
+    sa.height = lv.height; sa.width = lv.width;
+    sa.stride = static_cast<float>(lv.stride);
+    sa.iou_bg = iou_background; sa.iou_fg = iou_foreground;
+    la.block_begin[l] = total;
+    const long long cells = 1ll * num_anchors * lv.height * lv.width;
+    if (cells > 0x7fffffffll) return ODTK_ERR_INVALID;
+    total += static_cast<unsigned>((cells + odtk::kSnapThreads - 1) / odtk::kSnapThreads);
+  }
+  for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) la.block_begin[l] = total;
+  timed_launch(ODTK_KERNEL_TARGETS, odtk::snap_to_anchors_rotated_levels_kernel, dim3(total, batch_size), dim3(odtk::kSnapThreads), 0,
+               static_cast<hipStream_t>(stream), la);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_retina_loss_forward(const void *cls, const void *box, const float *depth, const float *box_target,
+                             int batch_size, int num_anchors, int num_classes, int height, int width, int box_params,
+                             int dtype, int channels_last, float alpha, float gamma, float beta, double *sums,
+                             void *stream) {
+  if (!sums) return ODTK_ERR_INVALID;
+  ODTK_HIP_TRY(hipMemsetAsync(sums, 0, 3 * sizeof(double), static_cast<hipStream_t>(stream)));
+  return retina_loss_launch(false, cls, box, depth, box_target, batch_size, num_anchors, num_classes, height, width,
+                            box_params, dtype, channels_last, alpha, gamma, beta, sums, nullptr, nullptr, nullptr, nullptr,
+                            static_cast<hipStream_t>(stream));
+}
+
+int odtk_retina_loss_backward(const void *cls, const void *box, const float *depth, const float *box_target,
+                              int batch_size, int num_anchors, int num_classes, int height, int width, int box_params,
+                              int dtype, int channels_last, float alpha, float gamma, float beta,
+                              const float *grad_cls_sum, const float *grad_box_sum, void *dcls, void *dbox,
+                              void *stream) {
+  if (!dcls || !dbox) return ODTK_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(dcls) | reinterpret_cast<uintptr_t>(dbox)) & 15u) return ODTK_ERR_INVALID;
+  return retina_loss_launch(true, cls, box, depth, box_target, batch_size, num_anchors, num_classes, height, width,
+                            box_params, dtype, channels_last, alpha, gamma, beta, nullptr, grad_cls_sum, grad_box_sum, dcls,
+                            dbox, static_cast<hipStream_t>(stream));
+}
+
+int odtk_retina_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, int batch_size, int num_anchors,
+                                    int num_classes, int box_params, int dtype, float alpha, float gamma, float beta,
+                                    double *sums, void *stream) {
+  if (!sums || n_levels <= 0 || n_levels > ODTK_MAX_LEVELS) return ODTK_ERR_INVALID;
+  ODTK_HIP_TRY(hipMemsetAsync(sums, 0, 3 * sizeof(double) * n_levels, static_cast<hipStream_t>(stream)));
+  return retina_loss_levels_launch(kLossFwd, n_levels, levels, batch_size, num_anchors, num_classes, box_params, dtype, alpha,
+                                   gamma, beta, sums, nullptr, nullptr, nullptr, false, static_cast<hipStream_t>(stream));
+}
+
+int odtk_retina_loss_levels_forward_ws(int n_levels, const odtk_loss_level_t *levels, int batch_size, int num_anchors,
+                                       int num_classes, int box_params, int dtype, float alpha, float gamma, float beta,
+                                       double *sums, void *workspace, size_t workspace_size, void *stream) {
+  if (n_levels <= 0 || n_levels > ODTK_MAX_LEVELS) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const LossTuning t = loss_tuning_snapshot(dtype, kLossFwdWs);
+  const int blocks = retina_loss_levels_launch(kLossFwdWs, n_levels, levels, batch_size, num_anchors, num_classes, box_params,
+                                               dtype, alpha, gamma, beta, nullptr, nullptr, nullptr, nullptr, true, nullptr, &t);
+  if (blocks < 0) return blocks;
+  const size_t need = (static_cast<size_t>(blocks) * (t.per_wave ? t.threads / 64 : 1) * 3 * sizeof(double) + 255) & ~static_cast<size_t>(255);
+  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
+  if (!sums) return ODTK_ERR_INVALID;
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7u) return ODTK_ERR_INVALID;
+  return retina_loss_levels_launch(kLossFwdWs, n_levels, levels, batch_size, num_anchors, num_classes, box_params, dtype, alpha,
+                                   gamma, beta, sums, nullptr, nullptr, static_cast<double *>(workspace), false,
+                                   static_cast<hipStream_t>(stream), &t);
+}
+
+int odtk_retina_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, int batch_size, int num_anchors,
+                                     int num_classes, int box_params, int dtype, float alpha, float gamma, float beta,
+                                     const float *grad_cls_sums, const float *grad_box_sums, void *stream) {
+  return retina_loss_levels_launch(kLossBwd, n_levels, levels, batch_size, num_anchors, num_classes, box_params, dtype, alpha,
+                                   gamma, beta, nullptr, grad_cls_sums, grad_box_sums, nullptr, false, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

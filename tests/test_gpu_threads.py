@@ -41,6 +41,49 @@ def _work(inp, ext):
     return list(det) + [sums] + list(dcls) + list(dbox)
 
 
+def test_profiler_and_trace_are_one_per_library():
+    """The library is linked from one object per subsystem; the profiler and the trace pointer must be ONE state that all of
+    them see: launches of the decode, nms, loss and engine sources all arrive in the same profile_collect, and the trace
+    buffer set once is stamped by select_decode and by nms."""
+    batch, n_levels = 2, 5
+    cls, dl, strides = synthetic.pyramid(batch, 9, 20, 128, 192, 'clustered', 4242)
+    assert len(strides) == n_levels
+    anchors = {s: box.generate_anchors(s, RATIOS, SCALES) for s in strides}
+    cls, dl = [c.cuda() for c in cls], [d.cuda() for d in dl]
+    lg = [torch.logit(c.clamp(1e-6, 1 - 1e-6)).bfloat16().contiguous(memory_format=torch.channels_last) for c in cls]
+    db = [d.bfloat16().contiguous(memory_format=torch.channels_last) for d in dl]
+    g = torch.Generator().manual_seed(4242)
+    depths = [torch.randint(-1, 21, (batch, 9, 1) + tuple(c.shape[-2:]), generator=g).float().cuda() for c in cls]
+    targets = [torch.randn((batch, 9, 4) + tuple(c.shape[-2:]), generator=g).cuda() * 0.3 for c in cls]
+    y = torch.randn(batch, 64, 16, 24, device='cuda').bfloat16().contiguous(memory_format=torch.channels_last)
+    bias = torch.randn(64, device='cuda')
+    trace = torch.zeros(_C.TRACE_WORDS, dtype=torch.int64, device='cuda')
+    try:
+        _C.profile_collect()                                         # whatever earlier tests left pending
+        _C.profile_enable()
+        box.detect(cls, dl, strides, anchors, 0.05, 1000, 0.5, 100)
+        _C.retina_loss_levels_forward(lg, db, depths, targets, 0.25, 2.0, 0.11, reproducible=True)
+        _C.bias_act_(y, bias)
+        _C.upsample2x(y)
+        first = _C.profile_collect()
+        for name in ('prefilter_scan_kernel', 'select_decode_kernel', 'nms_kernel', 'retina_loss_kernel', 'loss_reduce_kernel',
+                     'bias_act_kernel', 'upsample_nearest2x_kernel'):
+            assert first[name][1] >= 1, (name, first)
+        assert all(n == 0 for _, n in _C.profile_collect().values())
+        _C.debug_set_trace(trace)
+        box.detect(cls, dl, strides, anchors, 0.05, 1000, 0.5, 100)
+        torch.cuda.synchronize()
+        words = trace.cpu()
+        assert bool((words[:8 * batch * n_levels] != 0).any()), 'select_decode: 8 words per (level, image) segment from word 0'
+        nms = words[8 * 64:]                                         # nms: behind the select_decode slots, 8 words per workgroup,
+        for b in range(batch):                                       # the first `batch` groups of 8 left free
+            assert int(nms[(batch + b) * 8]) != 0, 'nms workgroup %d left no stamp' % b
+    finally:
+        _C.debug_set_trace(None)
+        _C.profile_enable(False)
+        _C.profile_collect()
+
+
 @pytest.mark.parametrize('ext', [False, True], ids=['ctypes', 'compiled'])
 def test_concurrent_calls_on_distinct_streams_equal_serial_results(ext):
     inputs = [_inputs(1000 + t) for t in range(N_THREADS)]

@@ -3,7 +3,8 @@
 one line per kernel with VGPRs / AGPRs / SGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS.
 No GPU needed.  `--filter nms` restricts the kernels; exit code 1 when any listed kernel uses scratch.
 `--from-library` (what tests/test_kernel_resources.py runs: seconds instead of a five-minute recompile) reads the same figures
-out of the BUILT libodtk_hip.so -- the gfx950 code object's AMDGPU metadata notes (.vgpr_count, .private_segment_fixed_size ...);
+out of the BUILT libodtk_hip.so -- the AMDGPU metadata notes (.vgpr_count, .private_segment_fixed_size ...) of its gfx950 code
+objects, one per object file the library was linked from;
 it refuses a library older than its sources."""
 import argparse
 import os
@@ -23,7 +24,7 @@ LLVM = '/opt/rocm/lib/llvm/bin'
 
 
 def rows_from_library(lib):
-    """[{name, VGPRs, AGPRs, TotalSGPRs, ScratchSize, LDS Size}] of the gfx950 code object inside `lib`."""
+    """[{name, VGPRs, AGPRs, TotalSGPRs, ScratchSize, LDS Size}] of every gfx950 code object inside `lib`."""
     import glob
     import tempfile
     src = os.path.join(ROOT, 'retinanet-examples_amd', 'csrc')
@@ -33,9 +34,17 @@ def rows_from_library(lib):
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, 'fat.bin'), os.path.join(tmp, 'gfx950.co')
         subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), '-O', 'binary', '--only-section=.hip_fatbin', lib, fat], check=True)
-        subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
-                        '--input=' + fat, '--output=' + co, '--unbundle'], check=True)
-        notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', co], capture_output=True, text=True, check=True).stdout
+        # one offload bundle per object the library was linked from, back to back at 4096-aligned offsets
+        with open(fat, 'rb') as f:
+            data = f.read()
+        starts = [i for i in range(0, len(data), 4096) if data.startswith(b'__CLANG_OFFLOAD_BUNDLE__', i)]
+        notes = ''
+        for begin, end in zip(starts, starts[1:] + [len(data)]):
+            with open(fat, 'wb') as f:
+                f.write(data[begin:end])
+            subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
+                            '--input=' + fat, '--output=' + co, '--unbundle'], check=True)
+            notes += subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', co], capture_output=True, text=True, check=True).stdout
     rows, cur = [], None
     keys = {'.vgpr_count': 'VGPRs', '.agpr_count': 'AGPRs', '.sgpr_count': 'TotalSGPRs', '.private_segment_fixed_size': 'ScratchSize',
             '.group_segment_fixed_size': 'LDS Size'}
