@@ -1,4 +1,4 @@
-// decode.hip -- decode and selection: workspace layout, the ODTK_SCAN_* / ODTK_SELECT_* knobs, odtk_decode*,
+// decode.hip -- decode and selection: workspace layout, the ODTK_SELECT_* knobs, odtk_decode*,
 // odtk_prefilter_thresholds and odtk_detect (decode, then nms.hip's nms_impl over decode's own output).
 #include <cmath>
 #include <cstdlib>
@@ -20,14 +20,6 @@ static_assert(sizeof(odtk::DecodeArgs) <= 4096 && sizeof(odtk::ScanArgs) <= 4096
 // top_n <= 4096: the standard select_decode (32 KiB static sort buffer); beyond: the variant with 128 KiB of dynamic LDS
 uint32_t sort_cap_for(int top_n) { return top_n <= odtk::kSortCap ? odtk::kSortCap : odtk::kSortCapBig; }
 
-// Order of the prefilter's workgroups inside a level: consecutive workgroups take the same span of DIFFERENT images (the
-// launch sweeps `batch` fronts through memory at once; measured 41.1 vs 42.0 us back to back, 48.1 vs 49.0 us in the step),
-// ODTK_SCAN_ORDER=1: one image after the other (A/B measurements; the result does not depend on it)
-int scan_image_major() {
-  static const int v = [] { const char *e = std::getenv("ODTK_SCAN_ORDER"); return (e && e[0] == '1') ? 1 : 0; }();
-  return v;
-}
-
 // select_decode's cooperative route (csrc/select_decode.hpp): how long a workgroup waits for the partners of its segment, in ticks
 // of the 100 MHz wall clock, before the segment falls back to the tournament.  ODTK_SELECT_COOP_TICKS: 0 = route off (A/B),
 // 1 = every barrier times out at once unless the partners are already there (exercises the fall-back), default 1000 = 10 us:
@@ -35,19 +27,6 @@ int scan_image_major() {
 // (profiles/r06_select_routes_instep.txt) -- every segment went the cooperative route and workgroup 0 sat 2.1 us (p50) / 3.1 us
 // (p99) / 3.4 us (max) between "slice fetched" and "barrier passed", its own histogram atomics included; the same with a 5 us
 // bound.  10 us is three times the longest wait seen; a partner that is NOT resident costs its segment 10 us, not round 5's 30.
-// A/B knobs of select_decode's partition (defaults = the constants of csrc/select_decode.hpp): workgroups PROVIDED per segment =
-// ceil(spans / ODTK_SELECT_SPANS_PER_PART), workgroups that TAKE PART = ceil(candidates / ODTK_SELECT_KEYS_PER_PART) of them
-uint32_t select_spans_per_part() {
-  static const uint32_t v = [] { const char *e = std::getenv("ODTK_SELECT_SPANS_PER_PART"); const int x = e ? std::atoi(e) : 0;
-                                 return x >= 1 && x <= 4096 ? static_cast<uint32_t>(x) : odtk::kSpansPerPart; }();
-  return v;
-}
-uint32_t select_keys_per_part() {
-  static const uint32_t v = [] { const char *e = std::getenv("ODTK_SELECT_KEYS_PER_PART"); const int x = e ? std::atoi(e) : 0;
-                                 return x >= 64 && x <= 4096 ? static_cast<uint32_t>(x) : odtk::kKeysPerPart; }();
-  return v;
-}
-
 uint32_t select_coop_ticks() {
   static const uint32_t v = [] {
     const char *e = std::getenv("ODTK_SELECT_COOP_TICKS");
@@ -66,16 +45,6 @@ uint32_t select_rank_sort() {
   return v;
 }
 
-// Tiles per prefilter workgroup for 16-bit inputs (ODTK_SCAN_SPAN = 1, 2 or 4; A/B measurements)
-uint32_t scan_span_tiles() {
-  static const uint32_t v = [] {
-    const char *e = std::getenv("ODTK_SCAN_SPAN");
-    const int x = e ? std::atoi(e) : 2;
-    return static_cast<uint32_t>(x == 1 || x == 4 ? x : 2);
-  }();
-  return v;
-}
-
 // Workspace of a decode call: [segment state | sub-list lengths | candidate pool: kSpanCap keys per span | survivor lists].
 // A span = 1 (fp32) or 2 (16-bit) tiles of 16 384 scores of ONE image; its four prefilter waves own kWaveStage keys each, so
 // no list can overflow into another and nothing is reserved at run time.  A wave with more raw hits than that marks its
@@ -84,7 +53,7 @@ int decode_layout(int batch, int n_levels, const odtk_level_t *levels, int A, in
   size_t off = 0;
   out->sel_off = off;
   off += align_up(sizeof(odtk::SelSeg) * static_cast<size_t>(batch) * n_levels);
-  out->span_tiles = dtype == ODTK_F32 ? 1u : scan_span_tiles();
+  out->span_tiles = dtype == ODTK_F32 ? 1u : odtk::kSpanTiles16;
   out->span_elems = out->span_tiles * odtk::kTile;
   out->budget = sort_cap_for(top_n);                       // keys a workgroup of the tournament route passes on: one sort buffer
   size_t lists = 0;
@@ -95,7 +64,7 @@ int decode_layout(int batch, int n_levels, const odtk_level_t *levels, int A, in
     out->spans[l] = static_cast<uint32_t>((n + out->span_elems - 1) / out->span_elems);
     // workgroups select_decode provides per segment: one per kSpansPerPart spans (they leave at once unless the segment
     // holds more than kKeysPerPart candidates each), and enough of them for a slice's sub-list lengths to fit in LDS
-    uint32_t parts = (out->spans[l] + select_spans_per_part() - 1) / select_spans_per_part();
+    uint32_t parts = (out->spans[l] + odtk::kSpansPerPart - 1) / odtk::kSpansPerPart;
     if (parts > odtk::kMaxParts) parts = odtk::kMaxParts;
     const uint32_t fit = (out->spans[l] * odtk::kScanWaves + odtk::kCntSlots - 1) / odtk::kCntSlots;
     if (parts < fit) parts = fit;
@@ -214,7 +183,6 @@ int decode_levels_impl(int batch, int n_levels, const odtk_level_t *levels, int 
   sa.n_levels = n_levels;
   sa.batch = batch;
   sa.span = static_cast<int>(lay.span_tiles);
-  sa.image_major = scan_image_major();
   sa.thresh = thresh;
   sa.raw_lo = logit_lower_bound(thresh);
 
@@ -226,7 +194,6 @@ int decode_levels_impl(int batch, int n_levels, const odtk_level_t *levels, int 
   da.span_elems = lay.span_elems;
   da.aligned = aligned ? 1u : 0u;
   da.coop_ticks = select_coop_ticks();
-  da.keys_per_part = select_keys_per_part();
   da.rank_sort = select_rank_sort();
   da.raw_lo = sa.raw_lo;
   da.by_channels = odtk::fastdiv_make(static_cast<uint32_t>(A) * C);

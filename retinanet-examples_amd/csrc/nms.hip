@@ -1,6 +1,5 @@
 // nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 #include "internal.hpp"
@@ -9,12 +8,6 @@
 #include "soft_nms.hpp"
 
 namespace {
-
-// axis-aligned NMS rounds: batched push (round 6, csrc/nms.hpp) or, ODTK_NMS_CHUNKS=1, the chunk loop of rounds 3-5 (A/B; same result)
-bool nms_chunk_mode() {
-  static const bool v = [] { const char *e = std::getenv("ODTK_NMS_CHUNKS"); return e && e[0] == '1'; }();
-  return v;
-}
 
 template <int NB, bool kGlobalKeys, int kStage = 0>
 int nms_launch(const odtk::NmsArgs &na, int batch, size_t lds, hipStream_t stream) {
@@ -142,7 +135,8 @@ int nms_impl(int batch, const void *const *inputs, void *const *outputs, int n_o
   na.run_valid = run_valid;
   na.ndet = ndet;
   na.thresh = thresh;
-  na.flags = flags | (nms_chunk_mode() ? odtk::kNmsFlagChunks : 0u);
+  na.flags = flags;
+  na.batched_push = 1u;
   na.trace = g_trace ? g_trace + 8 * 64 : nullptr;          // after the select_decode slots
   na.key_scratch = global_keys ? static_cast<uint64_t *>(workspace) : nullptr;
   const size_t lds = odtk::NmsLds(na.count, ndet, nb, global_keys).total;   // same carve-up the kernel computes

@@ -48,7 +48,6 @@ constexpr int kNmsRound = 1024;        // keys selected + ordered per round (one
 constexpr int kNmsChunk = 64;          // candidates resolved per chunk: one wave-width
 constexpr int kPairQueue = kRadixBins; // rotated: (box, box) pairs per queue slab -- the queue lives in the histogram's 8 KiB
 constexpr int kNmsMisc = 160;          // words of s_misc
-constexpr uint32_t kNmsFlagChunks = 0x80000000u;   // internal (NmsArgs::flags): axis-aligned rounds through the chunk loop of rounds 3-5 (A/B)
 
 struct NmsArgs {
   uint64_t *key_scratch;   // [batch, count] keys in the workspace when count > ODTK_MAX_NMS_COUNT (else unused)
@@ -67,6 +66,8 @@ struct NmsArgs {
   int ndet;
   float thresh;
   uint32_t flags;
+  uint32_t batched_push;       // always 1: the rounds behind the first go through the batched push.  An argument, not a constant: with the
+                               // test compiled out the kernel ran 0.4 us slower on the bench's heads (24.7 vs 24.3 us, two alternations)
   unsigned long long *trace;   // debug (odtk_debug_set_trace): 8 timestamps per workgroup, or null
   // rotated boxes, three launches (below): the first round in order, its pairwise suppression matrix, the resolve
   float *first_box;            // [batch, m_max, 6]  boxes of the first round's candidates, in NMS order
@@ -632,7 +633,7 @@ __global__ __launch_bounds__(kNmsThreads) void nms_kernel(const NmsArgs a) {
           for (int u = 0; u < kOwn; ++u)
             if (mk[u] && mc[u] == kc && axis_suppresses(kb, mb[u], thr)) mk[u] = 0;
           ++kept;
-          if (!(a.flags & kNmsFlagChunks) && ++pushes == kMaxPushAll && kept < ndet) { bailed = true; break; }   // (block-uniform)
+          if (a.batched_push && ++pushes == kMaxPushAll && kept < ndet) { bailed = true; break; }   // (block-uniform)
         }
         if (tid == 0) { s_misc[34] = static_cast<uint32_t>(kept); s_misc[37] = 0; }
         if (bailed) {
@@ -966,9 +967,9 @@ __global__ __launch_bounds__(kNmsThreads) void nms_kernel(const NmsArgs a) {
     // batch kept -- so a kept box clears its whole cluster out of the round at once, and the next batch starts at the next
     // candidate that is really still alive.  Same verdicts in the same order as the greedy loop (a batch member has survived
     // every box kept before the batch; inside the batch the rows are resolved in rank order; everything behind is tested against
-    // what the batch kept before it is looked at).  kNmsFlagChunks (ODTK_NMS_CHUNKS=1): rounds 3-5's chunk loop, A/B.
+    // what the batch kept before it is looked at).
     if constexpr (NB == 4) {
-      if (!(a.flags & kNmsFlagChunks) && !first_round) {     // (the first round stays with the chunk loop: on a detector that keeps most of what it examines -- one round, 100 kept of ~230 -- that form is the faster one)
+      if (a.batched_push && !first_round) {     // (the first round stays with the chunk loop: on a detector that keeps most of what it examines -- one round, 100 kept of ~230 -- that form is the faster one)
         pushed = true;
         const uint32_t r = static_cast<uint32_t>(tid);
         float jb[4];

@@ -11,7 +11,7 @@
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
 // __graft_entry__.build() as retinanet-examples_amd/odtk/_C_ext*.so (plain host C++, g++; links libodtk_hip.so);
-// `ODTK_BINDING=ext` makes odtk/_C.py hand decode / nms / iou to it instead of ctypes.
+// it is imported as odtk._C_ext next to the ctypes binding odtk/_C.py, which never hands work to it.
 #include <torch/extension.h>
 // PyTorch-ROCm keeps the device type named "cuda": the guard and stream accessors that honour that are the
 // *MasqueradingAsCUDA forms (what hipify turns c10::cuda::CUDAGuard / getCurrentCUDAStream of the reference's

@@ -240,23 +240,49 @@ _workspaces = {}
 _workspaces_lock = threading.Lock()      # several host threads may enqueue on their own streams at once (include/odtk_hip.h)
 
 
-def _workspace(device, nbytes):
+def _workspace(device, nbytes, cache=_workspaces):
     """Scratch owned by the binding, cached per (device, stream): never shared between streams.
     While the stream is being captured into a hipGraph nothing is cached and nothing cached is used: the buffer of a
     captured call is allocated for that call and belongs to the graph (torch serves allocations made during a capture
     from the graph's private pool and keeps that pool alive exactly as long as the graph), so a graph never reads
     scratch that an eager call -- or another graph -- may grow, replace or overwrite, and the cache never holds
-    memory of a graph that no longer exists."""
+    memory of a graph that no longer exists.  -> (buffer, stream handle)"""
     stream = torch.cuda.current_stream(device)
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device), stream.cuda_stream
     key = (device.index, stream.cuda_stream)
     with _workspaces_lock:
-        ws = _workspaces.get(key)
+        ws = cache.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-            _workspaces[key] = ws
+            cache[key] = ws
     return ws, stream.cuda_stream
+
+
+def _enqueue(fn, what, device, *args):
+    """The two-phase call of the ABI on torch's current HIP stream of `device`: fn(*args, workspace, size, stream) with a null
+    workspace answers the size it needs (every entry point does so before it looks at a data pointer: tests/test_abi_host.py),
+    then the same call with the binding's scratch enqueues the work."""
+    with torch.cuda.device(device):
+        size = _check(fn(*args, None, 0, None), what + ' (workspace query)')
+        ws, stream = _workspace(device, size)
+        _check(fn(*args, ws.data_ptr(), ws.numel(), stream), what)
+
+
+def _launch(fn, what, device, *args):
+    """An ABI call that takes no workspace: fn(*args, stream) on torch's current HIP stream of `device`."""
+    with torch.cuda.device(device):
+        _check(fn(*args, torch.cuda.current_stream(device).cuda_stream), what)
+
+
+def _detections(batch, n, nb, device, return_indices=False):
+    """The outputs of a decode / nms call: [scores [B, n], boxes [B, n, nb], classes [B, n]] (+ int32 indices [B, n])."""
+    out = [torch.empty((batch, n), dtype=torch.float32, device=device),
+           torch.empty((batch, n, nb), dtype=torch.float32, device=device),
+           torch.empty((batch, n), dtype=torch.float32, device=device)]
+    if return_indices:
+        out.append(torch.empty((batch, n), dtype=torch.int32, device=device))
+    return out
 
 
 def _anchor_array(anchors):
@@ -279,18 +305,11 @@ def decode(cls_head, box_head, anchors, scale, score_thresh, top_n, rotated=Fals
     num_classes = channels // num_anchors
     if box_head.shape != (batch, num_anchors * nb, height, width):
         raise RuntimeError('box_head shape %s does not match cls_head %s' % (tuple(box_head.shape), tuple(cls_head.shape)))
-    fn = lib.odtk_decode_rotate if rotated else lib.odtk_decode
-    with torch.cuda.device(cls_head.device):
-        scores = torch.empty((batch, top_n), dtype=torch.float32, device=cls_head.device)
-        boxes = torch.empty((batch, top_n, nb), dtype=torch.float32, device=cls_head.device)
-        classes = torch.empty((batch, top_n), dtype=torch.float32, device=cls_head.device)
-        size = _check(fn(batch, None, None, height, width, int(scale), num_anchors, num_classes, arr, n,
-                         float(score_thresh), int(top_n), None, 0, None), 'decode (workspace query)')
-        ws, stream = _workspace(cls_head.device, size)
-        _check(fn(batch, _ptrs([cls_head, box_head]), _ptrs([scores, boxes, classes]), height, width, int(scale),
-                  num_anchors, num_classes, arr, n, float(score_thresh), int(top_n), ws.data_ptr(), ws.numel(),
-                  stream), 'decode')
-    return [scores, boxes, classes]
+    out = _detections(batch, top_n, nb, cls_head.device)
+    _enqueue(lib.odtk_decode_rotate if rotated else lib.odtk_decode, 'decode', cls_head.device, batch,
+             _ptrs([cls_head, box_head]), _ptrs(out), height, width, int(scale), num_anchors, num_classes, arr, n,
+             float(score_thresh), int(top_n))
+    return out
 
 
 def nms(scores, boxes, classes, nms_thresh, detections_per_im, rotated=False, return_indices=False):
@@ -303,20 +322,9 @@ def nms(scores, boxes, classes, nms_thresh, detections_per_im, rotated=False, re
     batch, count = scores.shape
     if boxes.shape != (batch, count, nb) or classes.shape != (batch, count):
         raise RuntimeError('nms: inconsistent shapes')
-    dev = scores.device
-    with torch.cuda.device(dev):
-        out = [torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im, nb), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev)]
-        if return_indices:
-            out.append(torch.empty((batch, detections_per_im), dtype=torch.int32, device=dev))
-        flags = FLAG_ROTATED if rotated else 0
-        size = _check(lib.odtk_nms_ex(batch, None, None, len(out), count, int(detections_per_im), float(nms_thresh),
-                                      flags, None, 0, None), 'nms (workspace query)')
-        ws, stream = _workspace(dev, size)
-        _check(lib.odtk_nms_ex(batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
-                               int(detections_per_im), float(nms_thresh), flags, ws.data_ptr(), ws.numel(), stream),
-               'nms')
+    out = _detections(batch, detections_per_im, nb, scores.device, return_indices)
+    _enqueue(lib.odtk_nms_ex, 'nms', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
+             int(detections_per_im), float(nms_thresh), FLAG_ROTATED if rotated else 0)
     return out
 
 
@@ -330,18 +338,9 @@ def soft_nms(scores, boxes, classes, nms_thresh, detections_per_im, method, sigm
     batch, count = scores.shape
     if boxes.shape != (batch, count, 4) or classes.shape != (batch, count):
         raise RuntimeError('soft_nms: inconsistent shapes')
-    dev = scores.device
-    with torch.cuda.device(dev):
-        out = [torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im, 4), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev)]
-        if return_indices:
-            out.append(torch.empty((batch, detections_per_im), dtype=torch.int32, device=dev))
-        args = (len(out), count, int(detections_per_im), float(nms_thresh), int(method), float(sigma), float(min_score), 0)
-        size = _check(lib.odtk_soft_nms(batch, None, None, *args, None, 0, None), 'soft_nms (workspace query)')
-        ws, stream = _workspace(dev, size)
-        _check(lib.odtk_soft_nms(batch, _ptrs([scores, boxes, classes]), _ptrs(out), *args, ws.data_ptr(), ws.numel(), stream),
-               'soft_nms')
+    out = _detections(batch, detections_per_im, 4, scores.device, return_indices)
+    _enqueue(lib.odtk_soft_nms, 'soft_nms', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
+             int(detections_per_im), float(nms_thresh), int(method), float(sigma), float(min_score), 0)
     return out
 
 
@@ -357,19 +356,10 @@ def nms_sorted_runs(scores, boxes, classes, run_len, nms_thresh, detections_per_
     batch, count = scores.shape
     if boxes.shape != (batch, count, nb) or classes.shape != (batch, count) or count % int(run_len):
         raise RuntimeError('nms_sorted_runs: inconsistent shapes')
-    dev = scores.device
-    with torch.cuda.device(dev):
-        run_valid = (scores.view(batch, count // int(run_len), int(run_len)) > 0).sum(2).to(torch.int32).contiguous()
-        out = [torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im, nb), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev)]
-        flags = FLAG_ROTATED if rotated else 0
-        size = _check(lib.odtk_nms_sorted_runs(batch, None, None, 3, count, int(run_len), None, int(detections_per_im),
-                                               float(nms_thresh), flags, None, 0, None), 'nms_sorted_runs (workspace query)')
-        ws, stream = _workspace(dev, size)
-        _check(lib.odtk_nms_sorted_runs(batch, _ptrs([scores, boxes, classes]), _ptrs(out), 3, count, int(run_len),
-                                        run_valid.data_ptr(), int(detections_per_im), float(nms_thresh), flags, ws.data_ptr(),
-                                        ws.numel(), stream), 'nms_sorted_runs')
+    run_valid = (scores.view(batch, count // int(run_len), int(run_len)) > 0).sum(2).to(torch.int32).contiguous()
+    out = _detections(batch, detections_per_im, nb, scores.device)
+    _enqueue(lib.odtk_nms_sorted_runs, 'nms_sorted_runs', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), 3,
+             count, int(run_len), run_valid.data_ptr(), int(detections_per_im), float(nms_thresh), FLAG_ROTATED if rotated else 0)
     return out
 
 
@@ -380,10 +370,8 @@ def iou(boxes, anchors):
     lib = library()
     num_boxes = boxes.numel() // 8
     num_anchors = anchors.numel() // 8
-    with torch.cuda.device(boxes.device):
-        out = torch.empty((num_anchors, num_boxes), dtype=torch.float32, device=boxes.device)
-        stream = torch.cuda.current_stream(boxes.device).cuda_stream
-        _check(lib.odtk_iou(_ptrs([boxes, anchors]), _ptrs([out]), num_boxes, num_anchors, stream), 'iou')
+    out = torch.empty((num_anchors, num_boxes), dtype=torch.float32, device=boxes.device)
+    _launch(lib.odtk_iou, 'iou', boxes.device, _ptrs([boxes, anchors]), _ptrs([out]), num_boxes, num_anchors)
     return [out]
 
 
@@ -425,10 +413,8 @@ def prefilter_thresholds(cls_bias, dtype, score_thresh):
     if dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError('prefilter_thresholds: 16-bit head dtypes only')
     table = torch.empty(cls_bias.numel() + 8, dtype=torch.float32, device=cls_bias.device)
-    with torch.cuda.device(cls_bias.device):
-        stream = torch.cuda.current_stream(cls_bias.device).cuda_stream
-        _check(library().odtk_prefilter_thresholds(cls_bias.data_ptr(), cls_bias.numel(), _DTYPES[dtype], float(score_thresh),
-                                                   table.data_ptr(), stream), 'prefilter_thresholds')
+    _launch(library().odtk_prefilter_thresholds, 'prefilter_thresholds', cls_bias.device, cls_bias.data_ptr(), cls_bias.numel(),
+            _DTYPES[dtype], float(score_thresh), table.data_ptr())
     return table
 
 
@@ -493,19 +479,10 @@ def decode_levels(cls_heads, box_heads, anchors_list, strides, score_thresh, top
                                                                 cls_bias, box_bias, cls_thresholds)
     dev = cls_heads[0].device
     n = len(cls_heads)
-    with torch.cuda.device(dev):
-        out = [torch.empty((batch, n * top_n), dtype=torch.float32, device=dev),
-               torch.empty((batch, n * top_n, nb), dtype=torch.float32, device=dev),
-               torch.empty((batch, n * top_n), dtype=torch.float32, device=dev)]
-        if return_indices:
-            out.append(torch.empty((batch, n * top_n), dtype=torch.int32, device=dev))
-        flags = (FLAG_ROTATED if rotated else 0) | (FLAG_LOGITS if logits else 0)
-        size = _check(lib.odtk_decode_levels(batch, n, arr, num_anchors, num_classes, dtype, flags, float(score_thresh),
-                                             int(top_n), None, 0, None, 0, None), 'decode_levels (workspace query)')
-        ws, stream = _workspace(dev, size)
-        _check(lib.odtk_decode_levels(batch, n, arr, num_anchors, num_classes, dtype, flags, float(score_thresh),
-                                      int(top_n), _ptrs(out), len(out), ws.data_ptr(), ws.numel(), stream),
-               'decode_levels')
+    out = _detections(batch, n * top_n, nb, dev, return_indices)
+    flags = (FLAG_ROTATED if rotated else 0) | (FLAG_LOGITS if logits else 0)
+    _enqueue(lib.odtk_decode_levels, 'decode_levels', dev, batch, n, arr, num_anchors, num_classes, dtype, flags,
+             float(score_thresh), int(top_n), _ptrs(out), len(out))
     return out
 
 
@@ -518,17 +495,10 @@ def detect(cls_heads, box_heads, anchors_list, strides, score_thresh, top_n, nms
     arr, keep, batch, num_anchors, num_classes, dtype = _levels(cls_heads, box_heads, anchors_list, strides, nb,
                                                                 cls_bias, box_bias, cls_thresholds)
     dev = cls_heads[0].device
-    n = len(cls_heads)
-    with torch.cuda.device(dev):
-        out = [torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im, nb), dtype=torch.float32, device=dev),
-               torch.empty((batch, detections_per_im), dtype=torch.float32, device=dev)]
-        flags = (FLAG_ROTATED if rotated else 0) | (FLAG_LOGITS if logits else 0)
-        args = (batch, n, arr, num_anchors, num_classes, dtype, flags, float(score_thresh), int(top_n),
-                float(nms_thresh), int(detections_per_im))
-        size = _check(lib.odtk_detect(*args, None, None, 0, None), 'detect (workspace query)')
-        ws, stream = _workspace(dev, size)
-        _check(lib.odtk_detect(*args, _ptrs(out), ws.data_ptr(), ws.numel(), stream), 'detect')
+    out = _detections(batch, detections_per_im, nb, dev)
+    flags = (FLAG_ROTATED if rotated else 0) | (FLAG_LOGITS if logits else 0)
+    _enqueue(lib.odtk_detect, 'detect', dev, batch, len(cls_heads), arr, num_anchors, num_classes, dtype, flags,
+             float(score_thresh), int(top_n), float(nms_thresh), int(detections_per_im), _ptrs(out))
     return out
 
 
@@ -545,17 +515,34 @@ def snap_to_anchors(targets, anchors, num_classes, height, width, stride, iou_ba
     a = n // 4
     b, n_max = targets.shape[0], targets.shape[1]
     dev = targets.device
-    with torch.cuda.device(dev):
-        cls = torch.empty((b, a, num_classes, height, width), dtype=torch.float32, device=dev) if want_cls_target else None
-        box_t = torch.empty((b, a, 4, height, width), dtype=torch.float32, device=dev)
-        depth = torch.empty((b, a, 1, height, width), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_snap_to_anchors(b, targets.data_ptr(), n_max, arr, a, int(num_classes), int(height),
-                                              int(width), int(stride), float(iou_background), float(iou_foreground),
-                                              cls.data_ptr() if cls is not None else None, box_t.data_ptr(),
-                                              depth.data_ptr(), stream),
-               'snap_to_anchors')
+    cls = torch.empty((b, a, num_classes, height, width), dtype=torch.float32, device=dev) if want_cls_target else None
+    box_t = torch.empty((b, a, 4, height, width), dtype=torch.float32, device=dev)
+    depth = torch.empty((b, a, 1, height, width), dtype=torch.float32, device=dev)
+    _launch(library().odtk_snap_to_anchors, 'snap_to_anchors', dev, b, targets.data_ptr(), n_max, arr, a, int(num_classes),
+            int(height), int(width), int(stride), float(iou_background), float(iou_foreground),
+            cls.data_ptr() if cls is not None else None, box_t.data_ptr(), depth.data_ptr())
     return cls, box_t, depth
+
+
+def _snap_level_count(what, anchors_list, sizes, strides):
+    n = len(anchors_list)
+    if not (n == len(sizes) == len(strides)) or n == 0 or n > MAX_LEVELS:
+        raise RuntimeError('%s: need 1..%d levels with matching lists' % (what, MAX_LEVELS))
+    return n
+
+
+def _snap_targets(arr, b, a, num_classes, nb, sizes, strides, dev, want_cls_target):
+    """Allocate every level's targets and enter them, with the level's geometry, into its descriptor (SnapLevel and SnapRotLevel
+    name these fields alike) -> lists (cls_targets or Nones, box_targets [B, A, nb, H, W], depths)."""
+    cls_t, box_t, depth_t = [], [], []
+    for lv, (h, w), s in zip(arr, sizes, strides):
+        cls_t.append(torch.empty((b, a, num_classes, h, w), dtype=torch.float32, device=dev) if want_cls_target else None)
+        box_t.append(torch.empty((b, a, nb, h, w), dtype=torch.float32, device=dev))
+        depth_t.append(torch.empty((b, a, 1, h, w), dtype=torch.float32, device=dev))
+        lv.cls_target = cls_t[-1].data_ptr() if want_cls_target else None
+        lv.box_target, lv.depth = box_t[-1].data_ptr(), depth_t[-1].data_ptr()
+        lv.height, lv.width, lv.stride = int(h), int(w), int(s)
+    return cls_t, box_t, depth_t
 
 
 def snap_to_anchors_rotated_levels(gt_axis, gt_quads, gt_class, anchors_list, num_classes, sizes, strides, iou_background,
@@ -569,36 +556,25 @@ def snap_to_anchors_rotated_levels(gt_axis, gt_quads, gt_class, anchors_list, nu
         if t.dim() != 3 or t.shape[2] != last:
             raise RuntimeError('%s must be [B, N, %d]' % (name, last))
     _check_input(gt_class, 'gt_class')
-    n = len(anchors_list)
-    if not (n == len(sizes) == len(strides)) or n == 0 or n > MAX_LEVELS:
-        raise RuntimeError('snap_to_anchors_rotated_levels: need 1..%d levels with matching lists' % MAX_LEVELS)
+    n = _snap_level_count('snap_to_anchors_rotated_levels', anchors_list, sizes, strides)
     b, n_max = gt_axis.shape[0], gt_axis.shape[1]
     if gt_quads.shape[:2] != (b, n_max) or tuple(gt_class.shape) != (b, n_max):
         raise RuntimeError('snap_to_anchors_rotated_levels: gt_axis / gt_quads / gt_class disagree')
     dev = gt_axis.device
     arr = (SnapRotLevel * n)()
-    cls_t, box_t, depth_t = [], [], []
     a = None
-    with torch.cuda.device(dev):
-        for i, ((axis, quads), (h, w), s) in enumerate(zip(anchors_list, sizes, strides)):
-            _check_input(axis, 'anchors (axis form)')
-            _check_input(quads, 'anchors (quads)')
-            if a is None:
-                a = axis.shape[0]
-            if tuple(axis.shape) != (a, 4) or tuple(quads.shape) != (a, 8):
-                raise RuntimeError('snap_to_anchors_rotated_levels: every level needs [A, 4] and [A, 8] anchor tables')
-            cls_t.append(torch.empty((b, a, num_classes, h, w), dtype=torch.float32, device=dev) if want_cls_target else None)
-            box_t.append(torch.empty((b, a, 6, h, w), dtype=torch.float32, device=dev))
-            depth_t.append(torch.empty((b, a, 1, h, w), dtype=torch.float32, device=dev))
-            arr[i].anchors_axis, arr[i].anchors_quads = axis.data_ptr(), quads.data_ptr()
-            arr[i].cls_target = cls_t[-1].data_ptr() if want_cls_target else None
-            arr[i].box_target, arr[i].depth = box_t[-1].data_ptr(), depth_t[-1].data_ptr()
-            arr[i].height, arr[i].width, arr[i].stride = int(h), int(w), int(s)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_snap_to_anchors_rotated_levels(b, gt_axis.data_ptr(), gt_quads.data_ptr(), gt_class.data_ptr(), n_max, n,
-                                                             arr, a, int(num_classes), float(iou_background), float(iou_foreground),
-                                                             stream), 'snap_to_anchors_rotated_levels')
-    return cls_t, box_t, depth_t
+    for lv, (axis, quads) in zip(arr, anchors_list):
+        _check_input(axis, 'anchors (axis form)')
+        _check_input(quads, 'anchors (quads)')
+        if a is None:
+            a = axis.shape[0]
+        if tuple(axis.shape) != (a, 4) or tuple(quads.shape) != (a, 8):
+            raise RuntimeError('snap_to_anchors_rotated_levels: every level needs [A, 4] and [A, 8] anchor tables')
+        lv.anchors_axis, lv.anchors_quads = axis.data_ptr(), quads.data_ptr()
+    out = _snap_targets(arr, b, a, num_classes, 6, sizes, strides, dev, want_cls_target)
+    _launch(library().odtk_snap_to_anchors_rotated_levels, 'snap_to_anchors_rotated_levels', dev, b, gt_axis.data_ptr(),
+            gt_quads.data_ptr(), gt_class.data_ptr(), n_max, n, arr, a, int(num_classes), float(iou_background), float(iou_foreground))
+    return out
 
 
 def snap_to_anchors_levels(targets, anchors_list, num_classes, sizes, strides, iou_background, iou_foreground,
@@ -608,34 +584,24 @@ def snap_to_anchors_levels(targets, anchors_list, num_classes, sizes, strides, i
     _check_input(targets, 'targets')
     if targets.dim() != 3 or targets.shape[2] != 5:
         raise RuntimeError('targets must be [B, N, 5]')
-    n = len(anchors_list)
-    if not (n == len(sizes) == len(strides)) or n == 0 or n > MAX_LEVELS:
-        raise RuntimeError('snap_to_anchors_levels: need 1..%d levels with matching lists' % MAX_LEVELS)
+    n = _snap_level_count('snap_to_anchors_levels', anchors_list, sizes, strides)
     b, n_max = targets.shape[0], targets.shape[1]
     dev = targets.device
     arr = (SnapLevel * n)()
-    keep, cls_t, box_t, depth_t = [], [], [], []
+    keep = []
     a = None
-    with torch.cuda.device(dev):
-        for i, (anchors, (h, w), s) in enumerate(zip(anchors_list, sizes, strides)):
-            carr, ln = _anchor_array(anchors.reshape(-1).tolist() if isinstance(anchors, torch.Tensor) else anchors)
-            if a is None:
-                a = ln // 4
-            if ln != 4 * a:
-                raise RuntimeError('snap_to_anchors_levels: every level needs the same number of anchors')
-            keep.append(carr)
-            cls_t.append(torch.empty((b, a, num_classes, h, w), dtype=torch.float32, device=dev) if want_cls_target else None)
-            box_t.append(torch.empty((b, a, 4, h, w), dtype=torch.float32, device=dev))
-            depth_t.append(torch.empty((b, a, 1, h, w), dtype=torch.float32, device=dev))
-            arr[i].anchors = ctypes.cast(carr, _fp)
-            arr[i].cls_target = cls_t[-1].data_ptr() if want_cls_target else None
-            arr[i].box_target, arr[i].depth = box_t[-1].data_ptr(), depth_t[-1].data_ptr()
-            arr[i].height, arr[i].width, arr[i].stride = int(h), int(w), int(s)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_snap_to_anchors_levels(b, targets.data_ptr(), n_max, n, arr, a, int(num_classes),
-                                                     float(iou_background), float(iou_foreground), stream),
-               'snap_to_anchors_levels')
-    return cls_t, box_t, depth_t
+    for lv, anchors in zip(arr, anchors_list):
+        carr, ln = _anchor_array(anchors.reshape(-1).tolist() if isinstance(anchors, torch.Tensor) else anchors)
+        if a is None:
+            a = ln // 4
+        if ln != 4 * a:
+            raise RuntimeError('snap_to_anchors_levels: every level needs the same number of anchors')
+        keep.append(carr)
+        lv.anchors = ctypes.cast(carr, _fp)
+    out = _snap_targets(arr, b, a, num_classes, 4, sizes, strides, dev, want_cls_target)
+    _launch(library().odtk_snap_to_anchors_levels, 'snap_to_anchors_levels', dev, b, targets.data_ptr(), n_max, n, arr, a,
+            int(num_classes), float(iou_background), float(iou_foreground))
+    return out
 
 
 def _loss_geometry(cls_head, box_head, depth, box_target):
@@ -684,19 +650,12 @@ def retina_loss_levels_forward(cls_heads, box_heads, depths, box_targets, alpha,
     two launches against 34.6; profiles/r06_loss_layout_probe.txt)."""
     arr, n, (b, a, c, nb, dtype) = _loss_levels(cls_heads, box_heads, depths, box_targets)
     dev = cls_heads[0].device
-    lib = library()
-    with torch.cuda.device(dev):
-        sums = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        if not reproducible:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.odtk_retina_loss_levels_forward(n, arr, b, a, c, nb, dtype, float(alpha), float(gamma), float(beta),
-                                                       sums.data_ptr(), stream), 'retina_loss_levels_forward')
-            return sums
-        need = _check(lib.odtk_retina_loss_levels_forward_ws(n, arr, b, a, c, nb, dtype, float(alpha), float(gamma), float(beta),
-                                                             None, None, 0, None), 'retina_loss_levels_forward (workspace query)')
-        ws, stream = _workspace(dev, need)
-        _check(lib.odtk_retina_loss_levels_forward_ws(n, arr, b, a, c, nb, dtype, float(alpha), float(gamma), float(beta),
-                                                      sums.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'retina_loss_levels_forward')
+    sums = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    args = (n, arr, b, a, c, nb, dtype, float(alpha), float(gamma), float(beta), sums.data_ptr())
+    if reproducible:
+        _enqueue(library().odtk_retina_loss_levels_forward_ws, 'retina_loss_levels_forward', dev, *args)
+    else:
+        _launch(library().odtk_retina_loss_levels_forward, 'retina_loss_levels_forward', dev, *args)
     return sums
 
 
@@ -704,23 +663,20 @@ def retina_loss_levels_backward(cls_heads, box_heads, depths, box_targets, alpha
     """Gradients of sum_l (g_cls[l] * cls_sum[l] + g_box[l] * box_sum[l]) w.r.t. every head, ONE launch.
     grad_*: float32 CUDA vectors [L] (or None = zeros), read on the device."""
     dev = cls_heads[0].device
-    with torch.cuda.device(dev):
-        dcls = [torch.empty_like(t) for t in cls_heads]
-        dbox = [torch.empty_like(t) for t in box_heads]
-        for g, t in zip(dcls + dbox, list(cls_heads) + list(box_heads)):
-            if g.stride() != t.stride():
-                raise RuntimeError('retina_loss_levels_backward: could not allocate gradients in the heads\' layout')
-        arr, n, (b, a, c, nb, dtype) = _loss_levels(cls_heads, box_heads, depths, box_targets, (dcls, dbox))
+    dcls = [torch.empty_like(t) for t in cls_heads]
+    dbox = [torch.empty_like(t) for t in box_heads]
+    for g, t in zip(dcls + dbox, list(cls_heads) + list(box_heads)):
+        if g.stride() != t.stride():
+            raise RuntimeError('retina_loss_levels_backward: could not allocate gradients in the heads\' layout')
+    arr, n, (b, a, c, nb, dtype) = _loss_levels(cls_heads, box_heads, depths, box_targets, (dcls, dbox))
 
-        def vec(g):
-            return None if g is None else g.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+    def vec(g):
+        return None if g is None else g.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
 
-        g_cls, g_box = vec(grad_cls_sums), vec(grad_box_sums)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_retina_loss_levels_backward(n, arr, b, a, c, nb, dtype, float(alpha), float(gamma), float(beta),
-                                                          g_cls.data_ptr() if g_cls is not None else None,
-                                                          g_box.data_ptr() if g_box is not None else None, stream),
-               'retina_loss_levels_backward')
+    g_cls, g_box = vec(grad_cls_sums), vec(grad_box_sums)
+    _launch(library().odtk_retina_loss_levels_backward, 'retina_loss_levels_backward', dev, n, arr, b, a, c, nb, dtype,
+            float(alpha), float(gamma), float(beta), g_cls.data_ptr() if g_cls is not None else None,
+            g_box.data_ptr() if g_box is not None else None)
     return dcls, dbox
 
 
@@ -728,13 +684,10 @@ def retina_loss_forward(cls_head, box_head, depth, box_target, alpha, gamma, bet
     """-> float64 CUDA tensor [3] = (sum of masked focal losses, sum of masked smooth-L1 losses, #foreground anchors)
     of one level (reference model.py:193-209 + loss.py:13-31 in one pass; csrc/loss.hpp)."""
     b, a, c, h, w, nb, dtype, lay = _loss_geometry(cls_head, box_head, depth, box_target)
-    dev = cls_head.device
-    with torch.cuda.device(dev):
-        sums = torch.empty(3, dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_retina_loss_forward(cls_head.data_ptr(), box_head.data_ptr(), depth.data_ptr(),
-                                                  box_target.data_ptr(), b, a, c, h, w, nb, dtype, lay, float(alpha),
-                                                  float(gamma), float(beta), sums.data_ptr(), stream), 'retina_loss_forward')
+    sums = torch.empty(3, dtype=torch.float64, device=cls_head.device)
+    _launch(library().odtk_retina_loss_forward, 'retina_loss_forward', cls_head.device, cls_head.data_ptr(), box_head.data_ptr(),
+            depth.data_ptr(), box_target.data_ptr(), b, a, c, h, w, nb, dtype, lay, float(alpha), float(gamma), float(beta),
+            sums.data_ptr())
     return sums
 
 
@@ -751,19 +704,24 @@ def retina_loss_backward(cls_head, box_head, depth, box_target, alpha, gamma, be
         return g
 
     g_cls, g_box = scalar(grad_cls_sum), scalar(grad_box_sum)
-    with torch.cuda.device(dev):
-        dcls = torch.empty_like(cls_head)                   # preserves the (dense) memory format
-        dbox = torch.empty_like(box_head)
-        if dcls.stride() != cls_head.stride() or dbox.stride() != box_head.stride():
-            raise RuntimeError('retina_loss_backward: could not allocate gradients in the heads\' layout')
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(library().odtk_retina_loss_backward(cls_head.data_ptr(), box_head.data_ptr(), depth.data_ptr(),
-                                                   box_target.data_ptr(), b, a, c, h, w, nb, dtype, lay, float(alpha),
-                                                   float(gamma), float(beta),
-                                                   g_cls.data_ptr() if g_cls is not None else None,
-                                                   g_box.data_ptr() if g_box is not None else None,
-                                                   dcls.data_ptr(), dbox.data_ptr(), stream), 'retina_loss_backward')
+    dcls = torch.empty_like(cls_head)                   # preserves the (dense) memory format
+    dbox = torch.empty_like(box_head)
+    if dcls.stride() != cls_head.stride() or dbox.stride() != box_head.stride():
+        raise RuntimeError('retina_loss_backward: could not allocate gradients in the heads\' layout')
+    _launch(library().odtk_retina_loss_backward, 'retina_loss_backward', dev, cls_head.data_ptr(), box_head.data_ptr(),
+            depth.data_ptr(), box_target.data_ptr(), b, a, c, h, w, nb, dtype, lay, float(alpha), float(gamma), float(beta),
+            g_cls.data_ptr() if g_cls is not None else None, g_box.data_ptr() if g_box is not None else None,
+            dcls.data_ptr(), dbox.data_ptr())
     return dcls, dbox
+
+
+def _channels_last(t, or_one_pixel=False):
+    """channels_last -- or, where the caller allows it, a 1 x 1 map (whose strides torch reports either way)."""
+    return t.is_contiguous(memory_format=torch.channels_last) or (or_one_pixel and t.shape[2] * t.shape[3] == 1)
+
+
+def _bias_vector(bias, c):
+    return bias.dtype == torch.float32 and bias.numel() == c and bias.is_cuda
 
 
 def bias_act_(y, bias, residual=None, relu=True):
@@ -772,17 +730,14 @@ def bias_act_(y, bias, residual=None, relu=True):
     if not y.is_cuda or y.dim() != 4 or y.dtype not in _DTYPES:
         raise RuntimeError('bias_act_: y must be a 4-d CUDA tensor of float32/bfloat16/float16')
     n, c, h, w = y.shape
-    if not (y.is_contiguous(memory_format=torch.channels_last) or h * w == 1):
+    if not _channels_last(y, True):
         raise RuntimeError('bias_act_: y must be channels_last')
-    if bias.dtype != torch.float32 or bias.numel() != c or not bias.is_cuda:
+    if not _bias_vector(bias, c):
         raise RuntimeError('bias_act_: bias must be a float32 CUDA vector of length C')
-    if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or not (
-            residual.is_contiguous(memory_format=torch.channels_last) or h * w == 1)):
+    if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or not _channels_last(residual, True)):
         raise RuntimeError('bias_act_: residual must match y (shape, dtype, channels_last)')
-    with torch.cuda.device(y.device):
-        stream = torch.cuda.current_stream(y.device).cuda_stream
-        _check(library().odtk_bias_act(y.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                       n * h * w, c, _DTYPES[y.dtype], 1 if relu else 0, stream), 'bias_act')
+    _launch(library().odtk_bias_act, 'bias_act', y.device, y.data_ptr(), bias.data_ptr(),
+            residual.data_ptr() if residual is not None else None, n * h * w, c, _DTYPES[y.dtype], 1 if relu else 0)
     _count('bias_act_kernel', y.numel() * y.element_size() * (3 if residual is not None else 2))
     return y
 
@@ -793,15 +748,13 @@ def bias_act_maxpool(y, bias, relu=True):
     if not y.is_cuda or y.dim() != 4 or y.dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError('bias_act_maxpool: y must be a 4-d CUDA tensor of bfloat16/float16')
     n, c, h, w = y.shape
-    if not y.is_contiguous(memory_format=torch.channels_last) or c % 8:
+    if not _channels_last(y) or c % 8:
         raise RuntimeError('bias_act_maxpool: y must be channels_last with channels % 8 == 0')
-    if bias.dtype != torch.float32 or bias.numel() != c or not bias.is_cuda:
+    if not _bias_vector(bias, c):
         raise RuntimeError('bias_act_maxpool: bias must be a float32 CUDA vector of length C')
     out = torch.empty((n, c, (h + 1) // 2, (w + 1) // 2), dtype=y.dtype, device=y.device, memory_format=torch.channels_last)
-    with torch.cuda.device(y.device):
-        stream = torch.cuda.current_stream(y.device).cuda_stream
-        _check(library().odtk_bias_act_maxpool(y.data_ptr(), bias.data_ptr(), out.data_ptr(), n, h, w, c, _DTYPES[y.dtype],
-                                               1 if relu else 0, stream), 'bias_act_maxpool')
+    _launch(library().odtk_bias_act_maxpool, 'bias_act_maxpool', y.device, y.data_ptr(), bias.data_ptr(), out.data_ptr(), n, h, w, c,
+            _DTYPES[y.dtype], 1 if relu else 0)
     _count('bias_act_maxpool_kernel', (y.numel() + out.numel()) * y.element_size())
     return out
 
@@ -812,12 +765,10 @@ def upsample2x(x):
     if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES:
         raise RuntimeError('upsample2x: x must be a 4-d CUDA tensor of float32/bfloat16/float16')
     n, c, h, w = x.shape
-    if not x.is_contiguous(memory_format=torch.channels_last) or (c * x.element_size()) % 16:
+    if not _channels_last(x) or (c * x.element_size()) % 16:
         raise RuntimeError('upsample2x: x must be channels_last with channels * element size a multiple of 16 bytes')
     out = torch.empty((n, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _check(library().odtk_upsample_nearest2x(x.data_ptr(), out.data_ptr(), n, h, w, c, _DTYPES[x.dtype], stream), 'upsample2x')
+    _launch(library().odtk_upsample_nearest2x, 'upsample2x', x.device, x.data_ptr(), out.data_ptr(), n, h, w, c, _DTYPES[x.dtype])
     _count('upsample_nearest2x_kernel', (x.numel() + out.numel()) * x.element_size())
     return out
 
@@ -826,7 +777,7 @@ def _canvas_args(canvas, rects, what):
     if not canvas.is_cuda or canvas.dim() != 4 or canvas.dtype not in _DTYPES:
         raise RuntimeError('%s: canvas must be a 4-d CUDA tensor of float32/bfloat16/float16' % what)
     n, c, h, w = canvas.shape
-    if not canvas.is_contiguous(memory_format=torch.channels_last) or (c * canvas.element_size()) % 16:
+    if not _channels_last(canvas) or (c * canvas.element_size()) % 16:
         raise RuntimeError('%s: canvas must be channels_last with channels * element size a multiple of 16 bytes' % what)
     if len(rects) > MAX_LEVELS:
         raise RuntimeError('%s: at most %d rectangles' % (what, MAX_LEVELS))
@@ -840,9 +791,8 @@ def canvas_clear_(canvas, rects):
     """In place: zero every pixel of the channels_last `canvas` outside `rects` = [(y0, x0, height, width), ...] (the gutters of the
     engine's pyramid canvas; include/odtk_hip.h: odtk_canvas_clear).  One launch; pixels inside the rectangles are not touched."""
     n, c, h, w, arr = _canvas_args(canvas, rects, 'canvas_clear_')
-    with torch.cuda.device(canvas.device):
-        stream = torch.cuda.current_stream(canvas.device).cuda_stream
-        _check(library().odtk_canvas_clear(canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr, len(rects), stream), 'canvas_clear')
+    _launch(library().odtk_canvas_clear, 'canvas_clear', canvas.device, canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr,
+            len(rects))
     return canvas
 
 
@@ -855,14 +805,12 @@ def canvas_pack(levels, rects, height, width):
         raise RuntimeError('canvas_pack: one rectangle per level')
     for t, r in zip(levels, rects):
         if (not t.is_cuda or t.dim() != 4 or t.dtype != first.dtype or t.device != first.device or tuple(t.shape) != (n, c, r[2], r[3])
-                or not (t.is_contiguous(memory_format=torch.channels_last))):
+                or not _channels_last(t)):
             raise RuntimeError('canvas_pack: every level must be a channels_last [B, C, h, w] CUDA tensor of one dtype filling its rectangle')
     canvas = torch.empty((n, c, height, width), dtype=first.dtype, device=first.device, memory_format=torch.channels_last)
     n, c, h, w, arr = _canvas_args(canvas, rects, 'canvas_pack')
-    with torch.cuda.device(canvas.device):
-        stream = torch.cuda.current_stream(canvas.device).cuda_stream
-        _check(library().odtk_canvas_pack(canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr, _ptrs(list(levels)), len(rects), stream),
-               'canvas_pack')
+    _launch(library().odtk_canvas_pack, 'canvas_pack', canvas.device, canvas.data_ptr(), n, h, w, c, _DTYPES[canvas.dtype], arr,
+            _ptrs(list(levels)), len(rects))
     return canvas
 
 
@@ -882,10 +830,24 @@ def stem_pack(x, dtype):
     else:
         raise RuntimeError('stem_pack: x must be contiguous (NCHW or channels_last)')
     out = torch.empty((n, 16, h // 2, w // 2), dtype=dtype, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _check(library().odtk_stem_pack(x.data_ptr(), out.data_ptr(), n, h, w, _DTYPES[x.dtype], cl, _DTYPES[dtype], stream), 'stem_pack')
+    _launch(library().odtk_stem_pack, 'stem_pack', x.device, x.data_ptr(), out.data_ptr(), n, h, w, _DTYPES[x.dtype], cl, _DTYPES[dtype])
     return out
+
+
+def _image_args(what, src, images, tables, table, height, width):
+    """Shared by preprocess_images / augment_images: checks src, tables and table, coerces `images` to a ctypes array and allocates
+    the output -> (images, out, the arguments both entry points take from src on)."""
+    if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise RuntimeError('%s: src must be a contiguous uint8 CUDA tensor' % what)
+    if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
+        raise RuntimeError('%s: tables must be a contiguous int32 tensor on the device of src' % what)
+    if table.device != src.device or table.dtype not in _DTYPES or tuple(table.shape) != (3, 256) or not table.is_contiguous():
+        raise RuntimeError('%s: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src' % what)
+    if not isinstance(images, ctypes.Array):
+        images = (Image * len(images))(*images)
+    out = torch.empty((len(images), 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
+    return images, out, (src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None, tables.numel(),
+                         table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype])
 
 
 def preprocess_images(src, images, tables, table, height, width):
@@ -895,21 +857,8 @@ def preprocess_images(src, images, tables, table, height, width):
     memory; tables: int32 CUDA tensor of the resampling tables (odtk/data.py: resample_weights; may be empty when no image is
     resized); table: [3, 256] CUDA tensor of float32 / bfloat16 / float16, whose dtype is the output's.
     -> [len(images), 3, height, width] with channels_last strides."""
-    if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
-        raise RuntimeError('preprocess_images: src must be a contiguous uint8 CUDA tensor')
-    if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
-        raise RuntimeError('preprocess_images: tables must be a contiguous int32 tensor on the device of src')
-    if table.device != src.device or table.dtype not in _DTYPES or tuple(table.shape) != (3, 256) or not table.is_contiguous():
-        raise RuntimeError('preprocess_images: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src')
-    if not isinstance(images, ctypes.Array):
-        images = (Image * len(images))(*images)
-    batch = len(images)
-    out = torch.empty((batch, 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
-    with torch.cuda.device(src.device):
-        stream = torch.cuda.current_stream(src.device).cuda_stream
-        _check(library().odtk_preprocess_images(batch, images, src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None,
-                                                tables.numel(), table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype],
-                                                stream), 'preprocess_images')
+    images, out, args = _image_args('preprocess_images', src, images, tables, table, height, width)
+    _launch(library().odtk_preprocess_images, 'preprocess_images', src.device, len(images), images, *args)
     return out
 
 
@@ -918,46 +867,26 @@ def augment_images(src, images, augments, tables, table, height, width):
     odtk_augment_images): quarter turn and flip as an index map, brightness, contrast, hue, saturation, Pillow-exact.
     augments: a ctypes array (or sequence) of `Augment`, one per image, HOST memory; the rest as `preprocess_images`.
     -> [len(images), 3, height, width] with channels_last strides."""
-    if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
-        raise RuntimeError('augment_images: src must be a contiguous uint8 CUDA tensor')
-    if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
-        raise RuntimeError('augment_images: tables must be a contiguous int32 tensor on the device of src')
-    if table.device != src.device or table.dtype not in _DTYPES or tuple(table.shape) != (3, 256) or not table.is_contiguous():
-        raise RuntimeError('augment_images: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src')
-    if not isinstance(images, ctypes.Array):
-        images = (Image * len(images))(*images)
+    images, out, args = _image_args('augment_images', src, images, tables, table, height, width)
     if not isinstance(augments, ctypes.Array):
         augments = (Augment * len(augments))(*augments)
-    batch = len(images)
-    if len(augments) != batch:
-        raise RuntimeError('augment_images: %d images but %d augment descriptors' % (batch, len(augments)))
-    out = torch.empty((batch, 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
-    lib = library()
-    with torch.cuda.device(src.device):
-        args = (batch, images, augments, src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None, tables.numel(),
-                table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype])
-        size = _check(lib.odtk_augment_images(*args, None, 0, None), 'augment_images (workspace query)')
-        ws, stream = _workspace(src.device, size)
-        _check(lib.odtk_augment_images(*args, ws.data_ptr(), ws.numel(), stream), 'augment_images')
+    if len(augments) != len(images):
+        raise RuntimeError('augment_images: %d images but %d augment descriptors' % (len(images), len(augments)))
+    _enqueue(library().odtk_augment_images, 'augment_images', src.device, len(images), images, augments, *args)
     return out
 
 
-_GEMM_WORKSPACE = {}
+_GEMM_WORKSPACE = {}     # a dictionary of its own: the 32 MiB GEMM buffer and the decode scratch never replace each other
 _GEMM_READY = []
 
 
 def _gemm_setup(device):
     """Bind hipBLASLt (the copy PyTorch ships, so that one copy of the soname serves the process) and keep one 32 MiB
-    scratch buffer per (device, stream) -- GEMMs on different streams may run at the same time.  Inside a hipGraph
-    capture the buffer is allocated for the call and belongs to the graph (see `_workspace`)."""
+    scratch buffer per (device, stream) -- GEMMs on different streams may run at the same time; `_workspace`'s rules
+    (its lock; a captured call gets a buffer of its own).  -> (buffer, stream handle)"""
     if not gemm_available():
         raise RuntimeError('gemm_bias_act: hipBLASLt could not be bound (odtk_gemm_init failed)')
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(32 << 20, dtype=torch.uint8, device=device)
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    if key not in _GEMM_WORKSPACE:
-        _GEMM_WORKSPACE[key] = torch.empty(32 << 20, dtype=torch.uint8, device=device)
-    return _GEMM_WORKSPACE[key]
+    return _workspace(device, 32 << 20, _GEMM_WORKSPACE)
 
 
 def gemm_available():
@@ -982,17 +911,15 @@ def gemm_bias_act(x, weight, bias, residual=None, relu=True):
     if weight.numel() != n * k or weight.dtype != x.dtype or not weight.is_contiguous() and not weight.is_contiguous(
             memory_format=torch.channels_last):
         raise RuntimeError('gemm_bias_act: weight must be a dense [Cout, Cin(, 1, 1)] tensor of x.dtype')
-    if not (x.is_contiguous(memory_format=torch.channels_last) or h * w == 1):
+    if not _channels_last(x, True):
         raise RuntimeError('gemm_bias_act: x must be channels_last')
-    if bias.dtype != torch.float32 or bias.numel() != n or not bias.is_cuda:
+    if not _bias_vector(bias, n):
         raise RuntimeError('gemm_bias_act: bias must be a float32 CUDA vector of length Cout')
     y = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or not (
-            residual.is_contiguous(memory_format=torch.channels_last) or h * w == 1)):
+    if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or not _channels_last(residual, True)):
         raise RuntimeError('gemm_bias_act: residual must match the output (shape, dtype, channels_last)')
     with torch.cuda.device(x.device):
-        ws = _gemm_setup(x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ws, stream = _gemm_setup(x.device)
         _check(library().odtk_gemm_bias_act(y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
                                             residual.data_ptr() if residual is not None else None,
                                             b * h * w, n, k, _DTYPES[x.dtype], 1 if relu else 0,
@@ -1059,7 +986,7 @@ def conv_bias_act(x, weight, bias, stride=(1, 1), padding=(1, 1), relu=True, out
     ho, wo = (h + ph0 + ph1 - kh) // sh + 1, (w + pw0 + pw1 - kw) // sw + 1
     if out is None:
         y = torch.empty((b, k, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    else:                                                    # caller-owned output (the engine's head-tensor arena)
+    else:                                                    # caller-owned output
         if tuple(out.shape) != (b, k, ho, wo) or out.dtype != x.dtype or out.device != x.device:
             raise RuntimeError('conv_bias_act: out must be a channels_last %s tensor of shape %s' % (x.dtype, (b, k, ho, wo)))
         y = out
@@ -1076,11 +1003,8 @@ def conv_bias_act(x, weight, bias, stride=(1, 1), padding=(1, 1), relu=True, out
         srow = srow if hh > 1 else ww * spix
         sn = sn if t.shape[0] > 1 else hh * srow
         views += [sn, srow, spix]
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _check(lib.odtk_conv_bias_act_strided(y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), b, c, h, w, k, kh, kw,
-                                              sh, sw, ph0, pw0, ph1, pw1, *views, _DTYPES[x.dtype], 1 if relu else 0, stream),
-               'conv_bias_act')
+    _launch(lib.odtk_conv_bias_act_strided, 'conv_bias_act', x.device, y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+            b, c, h, w, k, kh, kw, sh, sw, ph0, pw0, ph1, pw1, *views, _DTYPES[x.dtype], 1 if relu else 0)
     return y
 
 

@@ -161,7 +161,7 @@ class _Conv(nn.Module):
         self.learned = {}                                               # kind ('act' | 'only') -> the last measured decision: unplanned geometries follow it
         self.route = {}                                                 # input shape -> (use the library, us library, us miopen + epilogue)
 
-    def conv_only(self, x, out=None):
+    def conv_only(self, x):
         """The convolution without its epilogue (the caller owns the bias: the heads' last convolutions, whose bias the
         post-processing kernels add).  Routed like `forward`: the library's instance list is a second find space for the same
         contraction (a zero bias, no clamp), taken where the plan pass measured it faster than MIOpen's pick."""
@@ -172,18 +172,17 @@ class _Conv(nn.Module):
                 self.zero_bias = torch.zeros_like(self.bias_lp)
             if self._routed(key, 'only', x, self._miopen_only, self._library_only):
                 try:
-                    return self._library_only(x, out)
+                    return self._library_only(x)
                 except RuntimeError:
                     self.route[key] = (False, float('inf'), 0.0)
-        y = self._miopen_only(x)
-        return y if out is None else out.copy_(y)                       # (MIOpen owns its output: an arena then costs a copy)
+        return self._miopen_only(x)
 
-    def on_view(self, x, only=False, out=None):
+    def on_view(self, x, only=False):
         """`forward` (or `conv_only`) on a spatial window of a larger channels_last tensor -- a level's rectangle of the pyramid
         canvas.  Where this geometry is routed to the convolution library the window is read in place; otherwise, and where the
         library refuses the view, it is copied out first.  (The route of the packed geometry is left alone either way.)"""
         if x.is_contiguous(memory_format=torch.channels_last):
-            return self.conv_only(x, out) if only else self(x)
+            return self.conv_only(x) if only else self(x)
         if self.library_ok and _Conv.use_conv_library and x.is_cuda and _window(x) and _C.conv_available():
             if only and self.zero_bias is None:
                 self.zero_bias = torch.zeros_like(self.bias_lp)
@@ -191,11 +190,11 @@ class _Conv(nn.Module):
             two, one = (self._miopen_only, self._library_only) if only else (self._two_pass, self._one_pass)
             if self._routed(key, 'only' if only else 'act', x, two, one):
                 try:
-                    return self._library_only(x, out) if only else self._one_pass(x)
+                    return self._library_only(x) if only else self._one_pass(x)
                 except RuntimeError:
                     pass
         x = x.contiguous(memory_format=torch.channels_last)
-        return self.conv_only(x, out) if only else self(x)
+        return self.conv_only(x) if only else self(x)
 
     def _torch(self, x, residual=None):
         """Plain torch (CPU tensors: the engine's logic without a GPU; no hot path)."""
@@ -208,8 +207,8 @@ class _Conv(nn.Module):
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, groups=self.groups)
         return y if y.is_contiguous(memory_format=torch.channels_last) else y.contiguous(memory_format=torch.channels_last)
 
-    def _library_only(self, x, out=None):
-        return _C.conv_bias_act(x, self.weight, self.zero_bias, self.stride, self.padding, False, out=out)
+    def _library_only(self, x):
+        return _C.conv_bias_act(x, self.weight, self.zero_bias, self.stride, self.padding, False)
 
     def _two_pass(self, x, residual=None):
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, groups=self.groups)
@@ -375,8 +374,6 @@ class FusedRetinaNet(nn.Module):
         self._streams = None
         self.tower_plan = 0
         self._planned = set()                                           # input geometries whose k x k convolutions were routed (plan pass)
-        self.cls_arena = bool(os.environ.get('ODTK_CLS_ARENA'))           # experiment: cls head tensors in one 2 MiB-aligned buffer (_cls_arena)
-        self._arenas = {}
         self._loaded_geometries = set()                                 # input shapes routed by a loaded plan (load_plan): never measured
         self._plan_file_seen = False                                    # ODTK_CONV_PLAN was looked at
         self.libraries_taken = None                                     # (gemm, conv) lines the libraries took from the last loaded plan
@@ -466,7 +463,7 @@ class FusedRetinaNet(nn.Module):
             return None
         return gutter
 
-    def _canvas_towers(self, feats, gutter, last_bias, arena=None):
+    def _canvas_towers(self, feats, gutter, last_bias):
         """Both head towers on the levels below P3 -- a quarter of the pyramid's pixels, but four launches per layer of which the
         smallest are pure latency (a P7 layer: 24 us for 1 us of arithmetic) -- as ONE convolution per layer.  The levels lie side
         by side in one channels_last canvas per image (pyramid_canvas_layout) with `gutter` zero pixels between them: the tower
@@ -489,7 +486,7 @@ class FusedRetinaNet(nn.Module):
                 canvas[:, :, y:y + h, x:x + w] = t
                 mask[:, :, y:y + h, x:x + w] = False
         out = []
-        for which, head in enumerate((self.cls_head, self.box_head)):
+        for head in (self.cls_head, self.box_head):
             t = canvas
             for j, c in enumerate(head[:-1]):
                 t = c(t)
@@ -497,10 +494,7 @@ class FusedRetinaNet(nn.Module):
                     t = _C.canvas_clear_(t, rects) if t.is_cuda else t.masked_fill_(mask, 0)
             last = head[-1]
             views = [t[:, :, y:y + h, x:x + w] for y, x, h, w in rects]
-            if last_bias:
-                out.append([last.on_view(v) for v in views])
-            else:
-                out.append([last.on_view(v, True, None if (arena is None or which) else arena[i]) for i, v in enumerate(views)])
+            out.append([last.on_view(v, not last_bias) for v in views])
         return list(zip(*out))
 
     def _towers(self, feats, last_bias, level_streams=None):
@@ -508,21 +502,20 @@ class FusedRetinaNet(nn.Module):
         8000 / 2080 / 560 pixels at bs 8) cannot fill 256 CUs on their own, so they run on side HIP streams
         next to P3's convolutions: [P3] on the caller's stream and the pyramid canvas of P4..P7 (`_canvas_towers`) on another --
         or, without the canvas, [P4] and [P5, P6, P7] on two others."""
-        arena = self._cls_arena(feats) if (self.cls_arena and not last_bias and feats[0].is_cuda and not _planning()) else None
         out = [None] * len(feats)
 
-        def level(t, i):
+        def level(t):
             if last_bias:
                 return self._run(self.cls_head, t), self._run(self.box_head, t)
-            return (self.cls_head[-1].conv_only(self._run(self.cls_head[:-1], t), None if arena is None else arena[i]),
+            return (self.cls_head[-1].conv_only(self._run(self.cls_head[:-1], t)),
                     self.box_head[-1].conv_only(self._run(self.box_head[:-1], t)))
 
         def unit(i):
             """One pyramid level -- or, for i == 'canvas', all the levels below P3 at once."""
             if i == 'canvas':
-                out[1:] = self._canvas_towers(feats[1:], gutter, last_bias, None if arena is None else arena[1:])
+                out[1:] = self._canvas_towers(feats[1:], gutter, last_bias)
                 return out[1:]
-            out[i] = level(feats[i], i)
+            out[i] = level(feats[i])
             return [out[i]]
 
         gutter = self._canvas_gutter(feats)
@@ -562,30 +555,6 @@ class FusedRetinaNet(nn.Module):
         for e in done:
             main.wait_event(e)
         return [o[0] for o in out], [o[1] for o in out]
-
-    def _cls_arena(self, feats):
-        """Experiment (ODTK_CLS_ARENA=1): the five cls head tensors -- the 245 MB the prefilter streams -- in ONE
-        engine-owned buffer, every level on a 2 MiB boundary, allocated once per geometry and kept (the same virtual pages every
-        step, aligned to the largest page-table fragment).  Views in channels_last layout; the convolution library writes into
-        them (`conv_only(x, out)`), MIOpen-routed levels are copied.  Measured: profiles/r06_prefilter_tlb.txt."""
-        channels = self.cls_head[-1].weight.shape[0]
-        key = tuple((t.shape[0], t.shape[2], t.shape[3]) for t in feats) + (feats[0].device,)
-        hit = self._arenas.get(key)
-        if hit is None:
-            step = 2 << 20
-            elt = torch.empty(0, dtype=self.dtype).element_size()
-            sizes = [t.shape[0] * t.shape[2] * t.shape[3] * channels * elt for t in feats]
-            total = sum((n + step - 1) // step * step for n in sizes) + step
-            buf = torch.empty(total, dtype=torch.uint8, device=feats[0].device)
-            off = (-buf.data_ptr()) % step
-            views = []
-            for t, n in zip(feats, sizes):
-                v = buf[off:off + n].view(self.dtype).view(t.shape[0], t.shape[2], t.shape[3], channels).permute(0, 3, 1, 2)
-                views.append(v)
-                off += (n + step - 1) // step * step
-            self._arenas.clear()
-            hit = self._arenas[key] = (buf, views)
-        return hit[1]
 
     # The engine owns its dtypes (weights are stored in `self.dtype`, every op runs in it): an enclosing
     # torch.autocast region -- which is how Model.forward picks the engine's dtype -- must not re-cast anything.
@@ -750,7 +719,7 @@ class FusedRetinaNet(nn.Module):
         for s in strides:
             m.level_anchors(s)
         table = None
-        if fold and cls_bias.is_cuda and not os.environ.get('ODTK_NO_THRESHOLD_TABLE'):
+        if fold and cls_bias.is_cuda:
             # the prefilter's per-channel threshold table: made once per (threshold, state of the bias vector); a capture
             # finds the one its eager warm-up passes made (without: the kernels derive the thresholds themselves)
             key = (float(m.threshold), cls_bias.data_ptr(), cls_bias._version)

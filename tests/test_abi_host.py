@@ -293,6 +293,62 @@ def test_loss_forward_workspace_query_without_a_gpu():
                                                   None, None, 0, None) == _C.ERR_INVALID
 
 
+def _query_cases():
+    """name -> (entry point, function of a dummy pointer or None -> the arguments in front of (workspace, size, stream)).
+    Small arguments: batch 2, levels 13 x 17 and 7 x 9, A = 9, C = 5, top_n 100, 500 candidates, 100 detections."""
+    anchors = (ctypes.c_float * 36)(*[1.0] * 36)
+
+    def ptrs(p, n=4):
+        return None if p is None else (ctypes.c_void_p * n)(*[p] * n)
+
+    def levels(p):
+        lv = (_C.Level * 2)()
+        for l, (h, w) in zip(lv, ((13, 17), (7, 9))):
+            l.cls = l.box = p
+            l.height, l.width, l.stride = h, w, 8
+            l.anchors = ctypes.cast(anchors, ctypes.POINTER(ctypes.c_float))
+        return lv
+
+    def loss_levels():
+        lv = (_C.LossLevel * 2)()
+        for l, (h, w) in zip(lv, ((13, 17), (7, 9))):
+            l.cls = l.box = l.depth = l.box_target = 1 << 20                   # (this query refuses null LEVEL pointers)
+            l.height, l.width, l.channels_last = h, w, 1
+        return lv
+
+    def images(p):
+        return None if p is None else (_C.Image * 2)()
+
+    single = lambda p: (2, ptrs(p), ptrs(p), 13, 17, 8, 9, 5, anchors, 36, 0.05, 100)
+    return {
+        'odtk_decode': single,
+        'odtk_decode_rotate': single,
+        'odtk_nms_ex': lambda p: (2, ptrs(p), ptrs(p), 3, 500, 100, 0.5, 0),
+        'odtk_nms_ex-indices': lambda p: (2, ptrs(p), ptrs(p), 4, 500, 100, 0.5, 0),
+        'odtk_nms_ex-rotated': lambda p: (2, ptrs(p), ptrs(p), 3, 500, 100, 0.5, _C.FLAG_ROTATED),
+        'odtk_soft_nms': lambda p: (2, ptrs(p), ptrs(p), 3, 500, 100, 0.5, _C.SOFT_NMS_GAUSSIAN, 0.5, 0.05, 0),
+        'odtk_nms_sorted_runs': lambda p: (2, ptrs(p), ptrs(p), 3, 500, 100, p, 100, 0.5, 0),
+        'odtk_decode_levels': lambda p: (2, 2, levels(p), 9, 5, _C.F32, 0, 0.05, 100, ptrs(p), 0 if p is None else 4),
+        'odtk_detect': lambda p: (2, 2, levels(p), 9, 5, _C.F32, 0, 0.05, 100, 0.5, 100, ptrs(p)),
+        'odtk_detect-rotated': lambda p: (2, 2, levels(p), 9, 5, _C.F32, _C.FLAG_ROTATED, 0.05, 100, 0.5, 100, ptrs(p)),
+        'odtk_retina_loss_levels_forward_ws': lambda p: (2, loss_levels(), 2, 9, 5, 4, _C.F32, 0.25, 2.0, 0.11, p),
+        'odtk_augment_images': lambda p: (2, images(p), None if p is None else (_C.Augment * 2)(), p, 0 if p is None else 4096, p,
+                                          0 if p is None else 64, p, p, 32, 48, _C.BF16),
+    }
+
+
+@pytest.mark.parametrize('case', sorted(_query_cases()))
+def test_workspace_query_does_not_depend_on_the_data_pointers(case):
+    """What `_C._enqueue` rests on: it queries with the real input and output pointers already in place, so every two-phase
+    entry point must answer the same positive size with null and with non-null pointers -- and must answer before it looks
+    at one (the pointers here are dummies: 1 MiB into nowhere)."""
+    fn = getattr(_C.library(), case.split('-')[0])
+    make = _query_cases()[case]
+    null = fn(*make(None), None, 0, None)
+    real = fn(*make(1 << 20), None, 0, None)
+    assert null > 0 and real == null, (case, null, real)
+
+
 def test_fastdiv_is_exact(tmp_path):
     """csrc/fastdiv.hpp (division by a launch-constant divisor: multiply-high + shifts, Granlund & Montgomery fig. 4.1)
     against `/` and `%`: every divisor the kernels can see at the edges, random pairs over the whole 32-bit range."""

@@ -5,7 +5,7 @@ segment to the tournament -- so the result must not depend on it.  The library r
 the selection suites run again in child processes with
     1  every barrier times out unless the partners are already there: segments of ONE launch take different routes
     0  the cooperative route off: every shared segment through the tournament (rounds 3-4)
-(the default, 3000 ticks = 30 us, is what every other GPU test runs under; the full-size, rotated, corner and thread suites were run
+(the default, 1000 ticks = 10 us, is what every other GPU test runs under; the full-size, rotated, corner and thread suites were run
 the same way by hand: profiles/r05_pytest_gpu_final_tail.txt)."""
 import os
 import subprocess
