@@ -178,30 +178,14 @@ def box2delta(boxes, anchors):
     return torch.cat([(b_ctr - a_ctr) / a_wh, torch.log(b_wh / a_wh)], 1)
 
 
-def snap_to_anchors(boxes, size, stride, anchors, num_classes, anchor_ious):
-    """box.py:134-189 restated in the anchor order [A, H, W] directly (the reference builds
-    [A, W, H] and transposes; every per-anchor value is independent of that order).
-    boxes [N, 5] = (x, y, w, h, class); size = [W*stride, H*stride] in pixels.
-    -> cls_target [A, C, H, W], box_target [A, 4, H, W], depth [A, 1, H, W]."""
-    A = anchors.shape[0]
-    W, H = int(size[0] / stride), int(size[1] / stride)
-    if boxes.nelement() == 0:
-        return torch.zeros(A, num_classes, H, W), torch.zeros(A, 4, H, W), torch.zeros(A, 1, H, W)
-    boxes, classes = boxes.split(4, dim=1)
-    xs = torch.arange(0, size[0], stride, dtype=classes.dtype)
-    ys = torch.arange(0, size[1], stride, dtype=classes.dtype)
-    gy, gx = torch.meshgrid(ys, xs, indexing='ij')                       # [H, W]
-    grid = torch.stack((gx, gy, gx, gy), 2).unsqueeze(0)                 # [1, H, W, 4]
-    anc = (grid + anchors.view(-1, 1, 1, 4).to(classes.dtype)).contiguous().view(-1, 4)   # (a, y, x)
-    boxes = torch.cat([boxes[:, :2], boxes[:, :2] + boxes[:, 2:] - 1], 1)
-    xy1 = torch.max(anc[:, None, :2], boxes[:, :2])
-    xy2 = torch.min(anc[:, None, 2:], boxes[:, 2:])
-    inter = torch.prod((xy2 - xy1 + 1).clamp(0), 2)
-    boxes_area = torch.prod(boxes[:, 2:] - boxes[:, :2] + 1, 1)
-    anc_area = torch.prod(anc[:, 2:] - anc[:, :2] + 1, 1)
-    overlap = inter / (anc_area[:, None] + boxes_area - inter)
+def snap_tail(overlap, boxes, classes, anc, A, H, W, num_classes, anchor_ious, to_delta=box2delta):
+    """box.py:165-189 (and :228-252 with to_delta = the rotated deltas): first maximum per anchor -> deltas, depth, class map.
+    overlap [A*H*W, N], boxes [N, 4+] corner form, classes [N, 1], anc [A*H*W, 4] in (a, y, x) order.
+    -> cls_target, box_target, depth, winner index [A, H, W] (int64), overlap of the winner [A, H, W]."""
     overlap, indices = overlap.max(1)
-    box_target = box2delta(boxes[indices], anc).view(A, H, W, 4).permute(0, 3, 1, 2).contiguous()
+    box_target = to_delta(boxes[indices], anc)
+    nb = box_target.shape[1]
+    box_target = box_target.view(A, H, W, nb).permute(0, 3, 1, 2).contiguous()
     depth = torch.ones_like(overlap) * -1
     depth[overlap < anchor_ious[0]] = 0
     fg = overlap >= anchor_ious[1]
@@ -211,4 +195,38 @@ def snap_to_anchors(boxes, size, stride, anchors, num_classes, anchor_ious):
     cls_target = torch.zeros(anc.shape[0], num_classes + 1, dtype=boxes.dtype)
     cls_target.scatter_(1, cls_idx.view(-1, 1), 1)
     cls_target = cls_target[:, :num_classes].view(A, H, W, num_classes).permute(0, 3, 1, 2).contiguous()
-    return cls_target, box_target, depth.view(A, 1, H, W)
+    return cls_target, box_target, depth.view(A, 1, H, W), indices.view(A, H, W), overlap.view(A, H, W)
+
+
+def cell_anchors(anchors, size, stride, dtype=torch.float32):
+    """box.py:143-149: grid + anchors, [A*H*W, K] in (a, y, x) order (K = 4 corners, or 8 quad coordinates)."""
+    xs = torch.arange(0, size[0], stride, dtype=dtype)
+    ys = torch.arange(0, size[1], stride, dtype=dtype)
+    gy, gx = torch.meshgrid(ys, xs, indexing='ij')                       # [H, W]
+    k = anchors.shape[1]
+    grid = torch.stack((gx, gy) * (k // 2), 2).unsqueeze(0)              # [1, H, W, K]
+    return (grid + anchors.view(-1, 1, 1, k).to(dtype)).contiguous().view(-1, k)
+
+
+def snap_to_anchors(boxes, size, stride, anchors, num_classes, anchor_ious, return_winner=False):
+    """box.py:134-189 restated in the anchor order [A, H, W] directly (the reference builds
+    [A, W, H] and transposes; every per-anchor value is independent of that order).
+    boxes [N, 5] = (x, y, w, h, class); size = [W*stride, H*stride] in pixels.
+    -> cls_target [A, C, H, W], box_target [A, 4, H, W], depth [A, 1, H, W]; with return_winner also the index of the
+    winning box per anchor [A, H, W] (int64, -1 without boxes) and its overlap [A, H, W]."""
+    A = anchors.shape[0]
+    W, H = int(size[0] / stride), int(size[1] / stride)
+    if boxes.nelement() == 0:
+        out = torch.zeros(A, num_classes, H, W), torch.zeros(A, 4, H, W), torch.zeros(A, 1, H, W)
+        return out + (torch.full((A, H, W), -1, dtype=torch.int64), torch.zeros(A, H, W)) if return_winner else out
+    boxes, classes = boxes.split(4, dim=1)
+    anc = cell_anchors(anchors, size, stride, classes.dtype)
+    boxes = torch.cat([boxes[:, :2], boxes[:, :2] + boxes[:, 2:] - 1], 1)
+    xy1 = torch.max(anc[:, None, :2], boxes[:, :2])
+    xy2 = torch.min(anc[:, None, 2:], boxes[:, 2:])
+    inter = torch.prod((xy2 - xy1 + 1).clamp(0), 2)
+    boxes_area = torch.prod(boxes[:, 2:] - boxes[:, :2] + 1, 1)
+    anc_area = torch.prod(anc[:, 2:] - anc[:, :2] + 1, 1)
+    overlap = inter / (anc_area[:, None] + boxes_area - inter)
+    out = snap_tail(overlap, boxes, classes, anc, A, H, W, num_classes, anchor_ious)
+    return out if return_winner else out[:3]

@@ -125,6 +125,18 @@ def snap_case(name, seed, stride, size, n_boxes, classes=10, ious=(0.4, 0.5)):
     print('%-28s fg %d ignore %d' % (name, int((out[2] > 0).sum()), int((out[2] < 0).sum())))
 
 
+# (name, seed, stride, size, boxes, classes); the last has more rows than the fused kernel stages at a time (1024)
+SNAP_CASES = (('snap_s16_256x160', 41, 16, (256, 160), 7, 10), ('snap_s8_128x128', 42, 8, (128, 128), 20, 10),
+              ('snap_s64_one_box', 43, 64, (256, 192), 1, 10), ('snap_s32_none', 44, 32, (128, 96), 0, 10),
+              ('snap_s32_1100_boxes', 45, 32, (256, 192), 1100, 8))
+
+
+def snap_cases(only=None):
+    for name, seed, stride, size, n_boxes, classes in SNAP_CASES:
+        if not only or name in only:
+            snap_case(name, seed, stride, size, n_boxes, classes)
+
+
 def main():
     assert ref_loader.available(), 'needs /root/reference'
     os.makedirs(GOLDEN, exist_ok=True)
@@ -160,11 +172,12 @@ def main():
     nms_case('nms_thr03_det10', 3, 500, 32, 0.3, 10)
     nms_case('nms_few', 2, 40, 33, 0.5, 100, zero_frac=0.8)
 
-    snap_case('snap_s16_256x160', 41, 16, (256, 160), 7)
-    snap_case('snap_s8_128x128', 42, 8, (128, 128), 20)
-    snap_case('snap_s64_one_box', 43, 64, (256, 192), 1)
-    snap_case('snap_s32_none', 44, 32, (128, 96), 0)
+    snap_cases()
 
 
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 1:                     # python oracle/gen_golden.py snap_s32_1100_boxes : only the named snap_* files
+        assert ref_loader.available(), 'needs /root/reference'
+        snap_cases(sys.argv[1:])
+    else:
+        main()

@@ -4,7 +4,9 @@
 Run in the build container (needs /root/reference to build the library); the fixtures travel instead of it.
 
     python oracle/gen_golden_native.py
+    python oracle/gen_golden_native.py snaprot d      # only tests/golden/snaprot_ref_d.npz
 """
+import math
 import os
 import sys
 
@@ -16,6 +18,9 @@ from oracle import ref_native                                   # noqa: E402
 from oracle.ref_build import build_ref                           # noqa: E402
 
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+# the anchor parameters of every recipe below (decode and target assignment alike)
+RATIOS, SCALES = [1.0, 2.0, 0.5], [4 * 2 ** (i / 3) for i in range(3)]
+ANGLES = [-math.pi / 6, 0, math.pi / 6]
 
 
 def quads(r, n, lo, hi, size):
@@ -37,6 +42,37 @@ def boxes6(r, k, span, size, unit=True):
     scale = 1.0 if unit else r.uniform(0.6, 1.4, k)               # the network does not normalise (sin, cos)
     return np.concatenate([ctr - wh / 2, ctr + wh / 2, (np.sin(th) * scale)[:, None], (np.cos(th) * scale)[:, None]],
                           1).astype(np.float32)
+
+
+# rotated target assignment: (name, seed, stride, size, boxes, classes).  'd' has 300 boxes on a 8 x 6 level: the fused kernel
+# stages 128 boxes at a time, so the winners of its cells come from three staging rounds
+SNAPROT_CASES = (('a', 61, 16, (160, 128), 6, 7), ('b', 62, 32, (256, 192), 12, 80), ('c', 63, 8, (64, 48), 0, 5),
+                 ('d', 64, 16, (128, 96), 300, 8))
+
+
+def snaprot_cases(only=None):
+    """The reference's own snap_to_anchors_rotated (odtk/box.py:192-252) run on the CPU with its `iou_cuda` bound to its
+    own iou kernel (oracle/ref_loader.py:ref_snap_to_anchors_rotated) -> tests/golden/snaprot_ref_*.npz (every case draws
+    from a generator of its own: `only` = names writes just those files)."""
+    import warnings
+    import torch
+    from oracle import ref_loader
+    warnings.filterwarnings('ignore')
+    for name, seed, stride, size, n, n_cls in SNAPROT_CASES:
+        if only and name not in only:
+            continue
+        g = torch.Generator().manual_seed(seed)
+        anchors = ref_loader.ref_generate_anchors_rotated(stride, RATIOS, SCALES, ANGLES)
+        xy = torch.rand(n, 2, generator=g) * torch.tensor([size[0] * 0.7, size[1] * 0.7])
+        wh = torch.rand(n, 2, generator=g) * torch.tensor([size[0] * 0.4, size[1] * 0.4]) + 12
+        th = (torch.rand(n, 1, generator=g) - 0.5) * 1.4
+        boxes = torch.cat([xy, wh, th, torch.randint(0, n_cls, (n, 1), generator=g).float()], 1)
+        cls_t, box_t, depth = ref_loader.ref_snap_to_anchors_rotated(boxes, list(size), stride, anchors, n_cls, [0.4, 0.5])
+        np.savez_compressed(os.path.join(GOLDEN, 'snaprot_ref_%s.npz' % name), boxes=boxes.numpy(), size=np.array(size),
+                            stride=np.int32(stride), classes=np.int32(n_cls), ious=np.array([0.4, 0.5], np.float32),
+                            cls_target=cls_t.numpy(), box_target=box_t.numpy(), depth=depth.numpy())
+        print('snaprot_ref_%s: fg %d ignore %d background %d' % (name, int((depth > 0).sum()), int((depth < 0).sum()),
+                                                                 int((depth == 0).sum())))
 
 
 def main():
@@ -81,16 +117,14 @@ def main():
     # indices the CPU-convention selection keeps.  Index decomposition, gather layout and sin/cos passthrough must be
     # exact; the box differs from the CPU path only by documented conventions (one- vs two-sided clamp, the order of
     # the centre sum, float exp) -- tests apply the two-sided clamp and a 1e-4 tolerance.
-    import math
     sys.path.insert(0, os.path.join(ROOT, 'retinanet-examples_amd'))
     from odtk import box as box_ops
     from oracle import c_oracle
-    ratios, scales = [1.0, 2.0, 0.5], [4 * 2 ** (i / 3) for i in range(3)]
     for name, rotated, n_cls, h, w, stride, thr, top_n in (('axis', False, 7, 19, 23, 16, 0.4, 500), ('rotated', True, 5, 11, 14, 32, 0.5, 300)):
         if rotated:
-            anchors = box_ops.generate_anchors_rotated(stride, ratios, scales, [-math.pi / 6, 0, math.pi / 6])[0].numpy()
+            anchors = box_ops.generate_anchors_rotated(stride, RATIOS, SCALES, ANGLES)[0].numpy()
         else:
-            anchors = box_ops.generate_anchors(stride, ratios, scales).numpy()
+            anchors = box_ops.generate_anchors(stride, RATIOS, SCALES).numpy()
         a, nb = anchors.shape[0], 6 if rotated else 4
         cls = r.random((a * n_cls, h, w)).astype(np.float32)
         dl = (r.standard_normal((a * nb, h, w)) * 0.3).astype(np.float32)
@@ -100,26 +134,14 @@ def main():
         np.savez_compressed(os.path.join(GOLDEN, 'decode_ref_%s.npz' % name), cls=cls, deltas=dl, anchors=anchors,
                             stride=np.int32(stride), thresh=np.float32(thr), top_n=np.int32(top_n), num_classes=np.int32(n_cls),
                             indices=idx, out_scores=s, out_boxes=b, out_classes=c)
-    # rotated target assignment: the reference's own snap_to_anchors_rotated (odtk/box.py:192-252) run on the CPU
-    # with its `iou_cuda` bound to its own iou kernel (oracle/ref_loader.py:ref_snap_to_anchors_rotated)
-    import warnings
-    import torch
-    from oracle import ref_loader
-    warnings.filterwarnings('ignore')
-    angles = [-math.pi / 6, 0, math.pi / 6]
-    for name, seed, stride, size, n, n_cls in (('a', 61, 16, (160, 128), 6, 7), ('b', 62, 32, (256, 192), 12, 80), ('c', 63, 8, (64, 48), 0, 5)):
-        g = torch.Generator().manual_seed(seed)
-        anchors = ref_loader.ref_generate_anchors_rotated(stride, ratios, scales, angles)
-        xy = torch.rand(n, 2, generator=g) * torch.tensor([size[0] * 0.7, size[1] * 0.7])
-        wh = torch.rand(n, 2, generator=g) * torch.tensor([size[0] * 0.4, size[1] * 0.4]) + 12
-        th = (torch.rand(n, 1, generator=g) - 0.5) * 1.4
-        boxes = torch.cat([xy, wh, th, torch.randint(0, n_cls, (n, 1), generator=g).float()], 1)
-        cls_t, box_t, depth = ref_loader.ref_snap_to_anchors_rotated(boxes, list(size), stride, anchors, n_cls, [0.4, 0.5])
-        np.savez_compressed(os.path.join(GOLDEN, 'snaprot_ref_%s.npz' % name), boxes=boxes.numpy(), size=np.array(size),
-                            stride=np.int32(stride), classes=np.int32(n_cls), ious=np.array([0.4, 0.5], np.float32),
-                            cls_target=cls_t.numpy(), box_target=box_t.numpy(), depth=depth.numpy())
+    snaprot_cases()
     print('wrote', sorted(f for f in os.listdir(GOLDEN) if '_ref_' in f))
 
 
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 1:                                        # python oracle/gen_golden_native.py snaprot d
+        assert sys.argv[1] == 'snaprot', sys.argv
+        build_ref.build()
+        snaprot_cases(sys.argv[2:])
+    else:
+        main()

@@ -232,6 +232,8 @@ int odtk_snap_to_anchors(int batch_size, const float *targets, int n_max, const 
       height <= 0 || width <= 0)
     return ODTK_ERR_INVALID;
   if (!anchors || !box_target || !depth || (n_max > 0 && !targets)) return ODTK_ERR_INVALID;   // cls_target may be null
+  const long long cells = 1ll * num_anchors * height * width;
+  if (cells > 0x7fffffffll) return ODTK_ERR_INVALID;        // the kernel indexes cells with int
   odtk::SnapArgs sa;
   std::memset(&sa, 0, sizeof sa);
   sa.targets = targets;
@@ -247,7 +249,6 @@ int odtk_snap_to_anchors(int batch_size, const float *targets, int n_max, const 
   sa.iou_bg = iou_background;
   sa.iou_fg = iou_foreground;
   std::memcpy(sa.anchors, anchors, sizeof(float) * 4 * num_anchors);
-  const long long cells = 1ll * num_anchors * height * width;
   const unsigned blocks = static_cast<unsigned>((cells + odtk::kSnapThreads - 1) / odtk::kSnapThreads);
   {
     KernelTimer t(ODTK_KERNEL_TARGETS, static_cast<hipStream_t>(stream));
@@ -287,6 +288,7 @@ int odtk_snap_to_anchors_levels(int batch_size, const float *targets, int n_max,
     std::memcpy(sa.anchors, lv.anchors, sizeof(float) * 4 * num_anchors);
     la.block_begin[l] = total;
     const long long cells = 1ll * num_anchors * lv.height * lv.width;
+    if (cells > 0x7fffffffll) return ODTK_ERR_INVALID;
     total += static_cast<unsigned>((cells + odtk::kSnapThreads - 1) / odtk::kSnapThreads);
   }
   for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) la.block_begin[l] = total;

@@ -167,6 +167,66 @@ def test_new_entry_points_validate_before_touching_the_device():
     assert lib.odtk_prefilter_thresholds(4096, 720, _C.F32, 0.05, 8192, None) == _C.ERR_UNSUPPORTED
 
 
+def test_target_assignment_entry_points_validate_before_touching_the_device():
+    """odtk_snap_to_anchors / _levels / _rotated_levels refuse on the host what their kernels cannot index or were never given:
+    a level of more than 2^31 - 1 anchor cells (the kernels hold the cell index in an int), 0 or more than ODTK_MAX_LEVELS levels,
+    0 or more than ODTK_MAX_ANCHORS anchors (the axis-aligned table travels in the kernel arguments), null output pointers.
+    Every call here returns before any launch: the pointers are never dereferenced."""
+    lib = _C.library()
+    fp = ctypes.POINTER(ctypes.c_float)
+    table = (ctypes.c_float * (4 * (_C.MAX_ANCHORS + 1)))()
+    p = 1 << 20                                               # stands for a device pointer
+
+    def single(a=9, h=5, w=7, cls=p, box_t=p, depth=p, anchors=table, targets=p, batch=2, n_max=3, classes=80):
+        return lib.odtk_snap_to_anchors(batch, targets, n_max, anchors, a, classes, h, w, 8, 0.4, 0.5, cls, box_t, depth, None)
+
+    def levels(rotated, n_levels=1, a=9, h=5, w=7, box_t=p, depth=p, anchors=True, n_given=None, batch=2, n_max=3, classes=80):
+        arr = ((_C.SnapRotLevel if rotated else _C.SnapLevel) * max(n_given or n_levels, 1))()
+        for lv in arr:
+            lv.height, lv.width, lv.stride, lv.cls_target, lv.box_target, lv.depth = h, w, 8, p, box_t, depth
+            if rotated:
+                lv.anchors_axis, lv.anchors_quads = (p, p) if anchors else (None, None)
+            elif anchors:
+                lv.anchors = ctypes.cast(table, fp)
+        if rotated:
+            return lib.odtk_snap_to_anchors_rotated_levels(batch, p, p, p, n_max, n_levels, arr, a, classes, 0.4, 0.5, None)
+        return lib.odtk_snap_to_anchors_levels(batch, p, n_max, n_levels, arr, a, classes, 0.4, 0.5, None)
+
+    # oversized geometry: 9 * 16384 * 16384 = 2^31 + 2^28 cells; 32 * 8192 * 8192 = 2^31 exactly, one past the largest int
+    for a, h, w in ((9, 16384, 16384), (_C.MAX_ANCHORS, 8192, 8192), (1, 65536, 32768)):
+        assert single(a=a, h=h, w=w) == _C.ERR_INVALID, (a, h, w)
+        assert levels(False, a=a, h=h, w=w) == _C.ERR_INVALID, (a, h, w)
+        assert levels(True, a=a, h=h, w=w) == _C.ERR_INVALID, (a, h, w)
+    for rotated in (False, True):
+        assert levels(rotated, n_levels=3, a=9, h=16384, w=16384) == _C.ERR_INVALID              # in every level of several
+        # level counts
+        assert levels(rotated, n_levels=0) == _C.ERR_INVALID
+        assert levels(rotated, n_levels=_C.MAX_LEVELS + 1) == _C.ERR_INVALID
+        assert levels(rotated, n_levels=-1, n_given=1) == _C.ERR_INVALID
+        # null outputs, null anchor tables, empty geometry
+        assert levels(rotated, box_t=None) == _C.ERR_INVALID
+        assert levels(rotated, depth=None) == _C.ERR_INVALID
+        assert levels(rotated, anchors=False) == _C.ERR_INVALID
+        assert levels(rotated, h=0) == _C.ERR_INVALID and levels(rotated, w=0) == _C.ERR_INVALID
+        assert levels(rotated, a=0) == _C.ERR_INVALID
+        assert levels(rotated, batch=0) == _C.ERR_INVALID and levels(rotated, n_max=-1) == _C.ERR_INVALID
+        assert levels(rotated, classes=0) == _C.ERR_INVALID
+    assert lib.odtk_snap_to_anchors_levels(2, p, 3, 1, None, 9, 80, 0.4, 0.5, None) == _C.ERR_INVALID
+    assert lib.odtk_snap_to_anchors_rotated_levels(2, p, p, p, 3, 1, None, 9, 80, 0.4, 0.5, None) == _C.ERR_INVALID
+    assert lib.odtk_snap_to_anchors_levels(2, None, 3, 1, (_C.SnapLevel * 1)(), 9, 80, 0.4, 0.5, None) == _C.ERR_INVALID   # rows, no table
+    for missing in range(3):
+        ptrs = [p, p, p]
+        ptrs[missing] = None
+        assert lib.odtk_snap_to_anchors_rotated_levels(2, *ptrs, 3, 1, (_C.SnapRotLevel * 1)(), 9, 80, 0.4, 0.5, None) == _C.ERR_INVALID
+    # anchor counts of the two axis-aligned entry points
+    for a in (0, -1, _C.MAX_ANCHORS + 1):
+        assert single(a=a) == _C.ERR_INVALID and levels(False, a=a) == _C.ERR_INVALID, a
+    assert single(box_t=None) == _C.ERR_INVALID and single(depth=None) == _C.ERR_INVALID
+    assert single(anchors=None) == _C.ERR_INVALID and single(targets=None) == _C.ERR_INVALID
+    assert single(h=0) == _C.ERR_INVALID and single(w=0) == _C.ERR_INVALID and single(batch=0) == _C.ERR_INVALID
+    assert single(n_max=-1) == _C.ERR_INVALID and single(classes=0) == _C.ERR_INVALID
+
+
 def test_loss_tuning_hook_validates_without_a_gpu():
     """odtk_debug_loss_tuning (launch shape of the loss kernels) never touches HIP: bad shapes are refused, good ones stick
     until set back.  The built-in defaults are the ones tools/loss_probe.py measured (profiles/r03_loss_probe.txt)."""

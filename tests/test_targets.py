@@ -240,13 +240,54 @@ def _rotated_case(path):
 def test_snap_to_anchors_rotated_matches_reference_fixture(path, monkeypatch):
     """The torch logic of the product function (rotate_boxes, cell anchors, arg-max, deltas, depth, class map) with
     the HIP iou op stood in by the oracle: equal to the reference's function bit for bit."""
-    assert len(SNAPROT) == 3
+    assert len(SNAPROT) == 4
     g, boxes, size, stride, anchors, classes, ious = _rotated_case(path)
     monkeypatch.setattr(box, '_require_gpu', lambda *a: None)
     monkeypatch.setattr(box._C, 'iou', _oracle_iou)
     out = box.snap_to_anchors_rotated(boxes, size, stride, anchors, classes, 'cpu', ious)
     for o, k in zip(out, ('cls_target', 'box_target', 'depth')):
         assert o.shape == tuple(g[k].shape) and np.array_equal(_bits(o.numpy()), _bits(g[k])), k
+
+
+@pytest.mark.parametrize('path', SNAPROT, ids=os.path.basename)
+def test_rotated_oracle_matches_reference_fixture(path):
+    """oracle/targets_oracle.py (what tests/test_gpu_target_shapes.py measures the fused kernel against) == the reference's
+    function bit for bit; the returned winners reproduce the overlap decisions, and in fixture d (300 boxes) they come from
+    all three groups of 128 rows the fused kernel stages."""
+    from oracle import targets_oracle
+    g, boxes, size, stride, anchors, classes, ious = _rotated_case(path)
+    out = targets_oracle.snap_to_anchors_rotated(boxes, size, stride, anchors, classes, ious)
+    for o, k in zip(out, ('cls_target', 'box_target', 'depth')):
+        assert o.shape == tuple(g[k].shape) and np.array_equal(_bits(o.numpy()), _bits(g[k])), k
+    winner, overlap = out[3], out[4]
+    assert winner.shape == overlap.shape == out[2][:, 0].shape
+    if boxes.shape[0] == 0:
+        assert (winner == -1).all() and not overlap.any()
+        return
+    fg = overlap >= ious[1]
+    assert torch.equal(out[2][:, 0][fg], boxes[winner[fg], 5] + 1) and torch.equal(out[2][:, 0] == 0, overlap < ious[0])
+    if boxes.shape[0] > 256:
+        assert {int(v) for v in (winner[fg] // 128).unique()} == {0, 1, 2}
+
+
+def test_axis_oracle_returns_the_winner():
+    """box_oracle.snap_to_anchors(return_winner=True): the same three tensors, plus the arg-max the depth map was made from."""
+    path = os.path.join(GOLDEN, 'snap_s32_1100_boxes.npz')
+    with np.load(path) as z:
+        g = {k: z[k] for k in z.files}
+    boxes, anchors = torch.from_numpy(g['boxes']).view(-1, 5), torch.from_numpy(g['anchors'])
+    assert boxes.shape[0] > 1024
+    size, stride, classes, ious = [int(v) for v in g['size']], int(g['stride']), int(g['classes']), list(g['ious'])
+    plain = box_oracle.snap_to_anchors(boxes, size, stride, anchors, classes, ious)
+    full = box_oracle.snap_to_anchors(boxes, size, stride, anchors, classes, ious, return_winner=True)
+    assert len(plain) == 3 and len(full) == 5 and all(torch.equal(a, b) for a, b in zip(plain, full))
+    winner, overlap = full[3], full[4]
+    fg = overlap >= ious[1]
+    assert fg.any() and torch.equal(full[2][:, 0][fg], boxes[winner[fg], 4] + 1)
+    assert torch.equal(full[2][:, 0] == 0, overlap < ious[0]) and (overlap < ious[0]).any()
+    assert int(winner.max()) >= 1024                                      # a winner from the second staging round
+    empty = box_oracle.snap_to_anchors(boxes[:0], size, stride, anchors, classes, ious, return_winner=True)
+    assert (empty[3] == -1).all() and not empty[4].any() and not empty[2].any()
 
 
 @pytest.mark.skipif(not ref_loader.available() or torch.cuda.is_available(), reason='reference tree only in the build container')
