@@ -65,7 +65,7 @@ extern "C" {
 
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
- * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t; -1 for any other value
+ * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t; -1 for any other value
  * (4 stays unassigned: tests/test_abi_host.py probes it as the first unknown id).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
@@ -360,6 +360,38 @@ typedef struct odtk_augment {
 int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const void *src, size_t src_bytes,
                         const int32_t *tables, size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype,
                         void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * odtk_augment_images_ex -- odtk_augment_images plus a free rotation per image: `Image.rotate(angle, resample=Image.BILINEAR)` of
+ * the turned image about its centre on its own canvas (no expand, black fill), bit-identical to Pillow on the host.  No reference
+ * equivalent: the reference parses --augment-free-rotate and ignores it.
+ *   rotations   HOST odtk_rotation_t[batch_size], like augments; NULL: exactly odtk_augment_images (same checks, same workspace).
+ * For an image with enabled != 0, in this order:
+ *   resize -> the index map of augments[i], which holds the quarter turn ONLY, onto the canvas (w x h = canvas_width x canvas_height)
+ *   -> rotation on that canvas, which keeps its size.  `matrix` takes the centre of an output pixel to a point of the turned image
+ *      (odtk/data.py: free_rotation_matrix computes it on the host, in double, as Image.rotate does); per output pixel (x, y), every
+ *      step one IEEE double operation, never fused:
+ *        xin = (m0 (x + 0.5) + m1 (y + 0.5)) + m2,  yin = (m3 (x + 0.5) + m4 (y + 0.5)) + m5;  black unless 0 <= xin < w, 0 <= yin < h
+ *        xin -= 0.5, yin -= 0.5, X = floor(xin), Y = floor(yin), dx = xin - X, dy = yin - Y
+ *        v1 = p[Y'][X0] + (p[Y'][X1] - p[Y'][X0]) dx   with X0, X1 = X, X + 1 clamped to [0, w - 1], Y' = Y clamped to [0, h - 1]
+ *        v2 = the same on row Y + 1 if Y + 1 < h, else v1;   byte = (uint8)(v1 + (v2 - v1) dy), truncated, per channel
+ *   -> flip left-right if `flip`
+ *   -> the colour chain of odtk_augment_images on those bytes (the black corners are image pixels: they count in the contrast's
+ *      grey level and are normalised as byte 0), table, pad.
+ * An image with enabled == 0 (then flip must be 0) comes out exactly as odtk_augment_images writes it.
+ *   workspace   as odtk_augment_images, and a second slot per image for the finished canvas bytes: two-phase with this entry point's
+ *               own query (workspace == NULL), which may answer more than odtk_augment_images does.
+ * One more launch in the chain, between the resize and the sum of L (two for more than 32 images): the finished canvas bytes of
+ * every image go to its second slot, and the sum and the colour pass read them through the identity map.
+ * Everything is checked on the host before anything touches HIP: the matrix of an enabled image is finite, the flags are 0 or 1.
+ */
+typedef struct odtk_rotation {
+  double matrix[6];                         /* m0 .. m5, see above; read only if enabled                */
+  int32_t enabled;                          /* 0 | 1                                                    */
+  int32_t flip;                             /* 0 | 1: flip left-right AFTER the rotation                */
+} odtk_rotation_t;
+int odtk_augment_images_ex(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const odtk_rotation_t *rotations,
+                           const void *src, size_t src_bytes, const int32_t *tables, size_t tables_len, const void *norm_table, void *out,
+                           int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream);
 /*
  * odtk_gemm_bias_act -- 1x1 (pointwise) convolution of a channels_last activation as ONE GEMM with
  * the whole epilogue fused:

@@ -17,6 +17,16 @@
 //      (profiles/r08_device_augment_kernel.txt), so it is not here.  Pass B avoids the question: a sum does not care for the
 //      order, so under such a map its lanes walk the canvas by columns = along the byte image's rows.
 //
+// With a free rotation (odtk_augment_images_ex) one more pass runs between A and B:
+//   R. augment_rotate_kernel: the finished canvas BYTES of every image of the launch -- the turn through the index map, then
+//      `Image.rotate(angle, resample=BILINEAR)` on the turned canvas, then the flip -- go to a second slot of the workspace, and B
+//      and C read that slot through the identity map: their code, and so the colour chain's bits, are the ones above.  An image
+//      without a rotation is copied through its map (a gather of bytes: the same bytes B and C would have gathered themselves).
+//      Pillow's bilinear affine transform is double arithmetic (odtk/data.py: rotate_bilinear is this pass in numpy): the centre
+//      of an output pixel goes through the host-computed matrix, a point outside the image is black, otherwise two taps on each
+//      of two rows (clamped to the image; the lower row only if it exists) are blended by the fractions and TRUNCATED to a byte.
+//      A thread owns four consecutive pixels of the canvas (rows are contiguous) = 12 bytes = three aligned 32-bit stores.
+//
 // The index map is Pillow's affine_fixed: xin = (a2 + a0 x + a1 y) >> 16, yin = (a5 + a3 x + a4 y) >> 16 in 16.16 fixed point, black
 // where (xin, yin) lies outside the resized image.  The host computes the six integers (also for the transposes and with the flip
 // composed in), so there is one gather path.  Black pixels of the turn are image pixels: they are normalised like any byte 0 and
@@ -138,6 +148,119 @@ __device__ __forceinline__ void aug_hue(int32_t *pr, int32_t *pg, int32_t *pb, i
     case 3: *pr = p, *pg = q, *pb = maxc; break;
     case 4: *pr = t, *pg = p, *pb = maxc; break;
     default: *pr = maxc, *pg = p, *pb = q; break;
+  }
+}
+
+constexpr int kRotMaxImages = 32;                // descriptors per launch of pass R (96 bytes each, by value in the kernel arguments)
+constexpr int kRotPixels = 4;                    // consecutive pixels per thread of pass R
+
+struct RotImage {
+  double m[6];             // odtk_rotation_t.matrix
+  int32_t cw, ch;          // canvas after the turn = what the rotation works on and what is written
+  int32_t rw, rh;          // the resized image = what the source slot holds
+  int32_t map[6];          // the turn (enabled) or the turn and the flip (not enabled)
+  int32_t enabled, flip;
+};
+
+struct RotArgs {
+  const uint8_t *bytes;    // resized bytes of image b = bytes + b * slot
+  uint8_t *canvas;         // finished canvas bytes of image b = canvas + b * slot, rows 3 * cw bytes apart
+  uint64_t slot;
+  int32_t first;           // batch index of images[0]
+  int32_t pad_;
+  RotImage images[kRotMaxImages];
+};
+
+// pixel (x, y) of the TURNED canvas, 0 <= x < cw, 0 <= y < ch: the byte image through the index map, black outside it.
+__device__ __forceinline__ void rot_tap(const uint8_t *image, const RotImage &im, int32_t x, int32_t y, double *r, double *g, double *b) {
+  const int32_t xin = (im.map[2] + im.map[0] * x + im.map[1] * y) >> 16, yin = (im.map[5] + im.map[3] * x + im.map[4] * y) >> 16;
+  *r = *g = *b = 0.0;
+  if (xin >= 0 && xin < im.rw && yin >= 0 && yin < im.rh) {
+    const uint8_t *p = image + (static_cast<uint32_t>(yin) * static_cast<uint32_t>(im.rw) + static_cast<uint32_t>(xin)) * 3u;
+    *r = static_cast<double>(p[0]);
+    *g = static_cast<double>(p[1]);
+    *b = static_cast<double>(p[2]);
+  }
+}
+
+// Pillow's BILINEAR(v, a, b, d): v = a + (b - a) * d, three roundings.
+__device__ __forceinline__ double rot_lerp(double a, double b, double d) {
+#pragma clang fp contract(off)
+  const double diff = b - a;
+  const double product = diff * d;
+  return a + product;
+}
+
+// Pixel (x, y) of the rotated canvas -> 0x00BBGGRR.  Pillow's affine_transform + bilinear_filter32RGB, in double, never fused.
+__device__ __forceinline__ uint32_t rot_pixel(const uint8_t *image, const RotImage &im, int32_t x, int32_t y) {
+#pragma clang fp contract(off)
+  const double xc = static_cast<double>(x) + 0.5, yc = static_cast<double>(y) + 0.5;
+  const double ax = im.m[0] * xc, bx = im.m[1] * yc, ay = im.m[3] * xc, by = im.m[4] * yc;
+  const double sx = ax + bx, sy = ay + by;
+  double xin = sx + im.m[2], yin = sy + im.m[5];
+  if (!(xin >= 0.0 && xin < static_cast<double>(im.cw) && yin >= 0.0 && yin < static_cast<double>(im.ch))) return 0u;
+  xin = xin - 0.5;
+  yin = yin - 0.5;
+  const double fx = floor(xin), fy = floor(yin);
+  const double dx = xin - fx, dy = yin - fy;
+  const int32_t col = static_cast<int32_t>(fx), row = static_cast<int32_t>(fy);          // -1 <= col < cw, -1 <= row < ch
+  const int32_t x0 = col < 0 ? 0 : col, x1 = col + 1 > im.cw - 1 ? im.cw - 1 : col + 1, y0 = row < 0 ? 0 : row;
+  double r0, g0, b0, r1, g1, b1;
+  rot_tap(image, im, x0, y0, &r0, &g0, &b0);
+  rot_tap(image, im, x1, y0, &r1, &g1, &b1);
+  const double vr = rot_lerp(r0, r1, dx), vg = rot_lerp(g0, g1, dx), vb = rot_lerp(b0, b1, dx);
+  double wr = vr, wg = vg, wb = vb;
+  if (row + 1 < im.ch) {                                          // (row + 1 >= 0 always)
+    rot_tap(image, im, x0, row + 1, &r0, &g0, &b0);
+    rot_tap(image, im, x1, row + 1, &r1, &g1, &b1);
+    wr = rot_lerp(r0, r1, dx);
+    wg = rot_lerp(g0, g1, dx);
+    wb = rot_lerp(b0, b1, dx);
+  }
+  const uint32_t r = static_cast<uint32_t>(static_cast<int32_t>(rot_lerp(vr, wr, dy))) & 255u;
+  const uint32_t g = static_cast<uint32_t>(static_cast<int32_t>(rot_lerp(vg, wg, dy))) & 255u;
+  const uint32_t b = static_cast<uint32_t>(static_cast<int32_t>(rot_lerp(vb, wb, dy))) & 255u;
+  return r | (g << 8) | (b << 16);
+}
+
+// Pass R.  grid = (ceil(largest canvas of the launch in pixels / (256 * kRotPixels)), 1, images of the launch).
+__global__ __launch_bounds__(256) void augment_rotate_kernel(const RotArgs a) {
+  const RotImage &im = a.images[blockIdx.z];
+  const uint32_t pixels = static_cast<uint32_t>(im.cw) * static_cast<uint32_t>(im.ch);
+  const uint32_t p0 = (blockIdx.x * 256u + threadIdx.x) * kRotPixels;
+  if (p0 >= pixels) return;
+  const uint8_t *image = a.bytes + static_cast<size_t>(a.first + blockIdx.z) * a.slot;
+  uint8_t *dst = a.canvas + static_cast<size_t>(a.first + blockIdx.z) * a.slot + static_cast<size_t>(p0) * 3u;
+  int32_t y = static_cast<int32_t>(p0 / static_cast<uint32_t>(im.cw)), x = static_cast<int32_t>(p0 - static_cast<uint32_t>(y) * static_cast<uint32_t>(im.cw));
+  uint32_t v[kRotPixels];
+#pragma unroll
+  for (int p = 0; p < kRotPixels; ++p) {
+    v[p] = 0u;
+    if (p0 + p < pixels) {
+      if (im.enabled) {
+        v[p] = rot_pixel(image, im, im.flip ? im.cw - 1 - x : x, y);
+      } else {
+        double r, g, b;
+        rot_tap(image, im, x, y, &r, &g, &b);
+        v[p] = static_cast<uint32_t>(r) | (static_cast<uint32_t>(g) << 8) | (static_cast<uint32_t>(b) << 16);
+      }
+    }
+    if (++x == im.cw) x = 0, ++y;
+  }
+  static_assert(kRotPixels == 4, "12 bytes = three words");
+  if (p0 + kRotPixels <= pixels) {                                // slots are 16-byte aligned and p0 * 3 is a multiple of 12
+    uint32_t *w = reinterpret_cast<uint32_t *>(dst);
+    w[0] = v[0] | (v[1] << 24);
+    w[1] = (v[1] >> 8) | (v[2] << 16);
+    w[2] = (v[2] >> 16) | (v[3] << 8);
+  } else {
+#pragma unroll
+    for (int p = 0; p < kRotPixels; ++p)
+      if (p0 + p < pixels) {
+        dst[3 * p] = static_cast<uint8_t>(v[p]);
+        dst[3 * p + 1] = static_cast<uint8_t>(v[p] >> 8);
+        dst[3 * p + 2] = static_cast<uint8_t>(v[p] >> 16);
+      }
   }
 }
 

@@ -1,4 +1,5 @@
-// input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise) and odtk_augment_images.
+// input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise), odtk_augment_images and
+// odtk_augment_images_ex (the same with a free rotation).
 #include <cmath>
 #include <cstring>
 
@@ -72,15 +73,17 @@ int odtk_preprocess_images(int batch_size, const odtk_image_t *images, const voi
   return ODTK_OK;
 }
 
-int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const void *src, size_t src_bytes,
-                        const int32_t *tables, size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype,
-                        void *workspace, size_t workspace_bytes, void *stream) {
+// odtk_augment_images (rotations == nullptr) and odtk_augment_images_ex.
+static int augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const odtk_rotation_t *rotations,
+                          const void *src, size_t src_bytes, const int32_t *tables, size_t tables_len, const void *norm_table, void *out,
+                          int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
   if (batch_size <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
   if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
   if (3ull * height * width >= (1ull << 31) || (height + odtk::kAugRows - 1) / odtk::kAugRows > 65535) return ODTK_ERR_INVALID;
   // workspace: one 64-bit sum per image | one slot per image for its resized bytes (as many pixels as the canvas at most)
+  // | with rotations: one more slot per image for its finished canvas bytes
   const size_t slot = align_up(3ull * height * width), off_bytes = align_up(sizeof(unsigned long long) * batch_size);
-  const size_t need = off_bytes + slot * batch_size;
+  const size_t need = off_bytes + slot * batch_size * (rotations ? 2u : 1u);
   if (need > 0x7fffffffull) return ODTK_ERR_INVALID;
   if (!workspace) return static_cast<int>(need);
   if (!images || !augments || !src || !norm_table || !out) return ODTK_ERR_INVALID;
@@ -114,8 +117,15 @@ int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_a
       }
     max_w = im.out_width > max_w ? im.out_width : max_w;
     max_h = im.out_height > max_h ? im.out_height : max_h;
+    if (rotations) {
+      const odtk_rotation_t &ro = rotations[b];
+      if ((ro.enabled != 0 && ro.enabled != 1) || (ro.flip != 0 && ro.flip != 1) || (!ro.enabled && ro.flip)) return ODTK_ERR_INVALID;
+      for (int k = 0; ro.enabled && k < 6; ++k)
+        if (!std::isfinite(ro.matrix[k])) return ODTK_ERR_INVALID;
+    }
   }
-  static_assert(sizeof(odtk::PreArgs) <= 4096 && sizeof(odtk::AugArgs) <= 4096, "kernel arguments travel by value");
+  static_assert(sizeof(odtk::PreArgs) <= 4096 && sizeof(odtk::AugArgs) <= 4096 && sizeof(odtk::RotArgs) <= 4096,
+                "kernel arguments travel by value");
   hipStream_t s = static_cast<hipStream_t>(stream);
   odtk::PreArgs pre;
   pre.src = static_cast<const uint8_t *>(src);
@@ -128,8 +138,13 @@ int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_a
   pre.bytes = static_cast<uint8_t *>(workspace) + off_bytes;
   pre.sums = static_cast<unsigned long long *>(workspace);
   pre.slot = slot;
+  odtk::RotArgs rot;
+  rot.bytes = pre.bytes;
+  rot.canvas = pre.bytes + slot * batch_size;
+  rot.slot = slot;
+  rot.pad_ = 0;
   odtk::AugArgs aug;
-  aug.bytes = pre.bytes;
+  aug.bytes = rotations ? rot.canvas : pre.bytes;                 // passes B and C read the finished canvas, through the identity map
   aug.sums = pre.sums;
   aug.norm = norm_table;
   aug.out = out;
@@ -153,6 +168,12 @@ int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_a
       d.rw = images[first + i].out_width;
       d.rh = images[first + i].out_height;
       std::memcpy(d.map, au.map, sizeof(d.map));
+      if (rotations) {
+        const int32_t identity[6] = {65536, 0, 0, 0, 65536, 0};
+        d.rw = au.canvas_width;
+        d.rh = au.canvas_height;
+        std::memcpy(d.map, identity, sizeof(d.map));
+      }
       d.flags = au.flags;
       d.brightness = au.brightness;
       d.contrast = au.contrast;
@@ -163,6 +184,31 @@ int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_a
     const dim3 tiles((max_w + odtk::kPreTileW - 1) / odtk::kPreTileW, (max_h + odtk::kPreTileH - 1) / odtk::kPreTileH, static_cast<unsigned>(n));
     hipLaunchKernelGGL((odtk::preprocess_images_kernel<4, true>), tiles, dim3(256), 0, s, pre);
     ODTK_HIP_TRY(hipGetLastError());
+    for (int at = 0; rotations && at < n; at += odtk::kRotMaxImages) {   // its descriptors are larger: up to two launches
+      const int m = n - at < odtk::kRotMaxImages ? n - at : odtk::kRotMaxImages;
+      rot.first = first + at;
+      std::memset(rot.images, 0, sizeof(rot.images));
+      unsigned long long pixels = 0;
+      for (int i = 0; i < m; ++i) {
+        const odtk_augment_t &au = augments[first + at + i];
+        const odtk_rotation_t &ro = rotations[first + at + i];
+        odtk::RotImage &d = rot.images[i];
+        std::memcpy(d.m, ro.matrix, sizeof(d.m));
+        d.cw = au.canvas_width;
+        d.ch = au.canvas_height;
+        d.rw = images[first + at + i].out_width;
+        d.rh = images[first + at + i].out_height;
+        std::memcpy(d.map, au.map, sizeof(d.map));
+        d.enabled = ro.enabled;
+        d.flip = ro.flip;
+        const unsigned long long count = 1ull * au.canvas_width * au.canvas_height;
+        pixels = count > pixels ? count : pixels;
+      }
+      const unsigned per_group = 256u * odtk::kRotPixels;
+      hipLaunchKernelGGL(odtk::augment_rotate_kernel, dim3(static_cast<unsigned>((pixels + per_group - 1) / per_group), 1, static_cast<unsigned>(m)),
+                         dim3(256), 0, s, rot);
+      ODTK_HIP_TRY(hipGetLastError());
+    }
     if (contrast) {
       hipLaunchKernelGGL(odtk::augment_luma_sum_kernel, dim3(odtk::kAugSumBlocks, 1, static_cast<unsigned>(n)), dim3(256), 0, s, aug);
       ODTK_HIP_TRY(hipGetLastError());
@@ -175,6 +221,20 @@ int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_a
     ODTK_HIP_TRY(hipGetLastError());
   }
   return ODTK_OK;
+}
+
+int odtk_augment_images(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const void *src, size_t src_bytes,
+                        const int32_t *tables, size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  return augment_images(batch_size, images, augments, nullptr, src, src_bytes, tables, tables_len, norm_table, out, height, width, dtype,
+                        workspace, workspace_bytes, stream);
+}
+
+int odtk_augment_images_ex(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const odtk_rotation_t *rotations,
+                           const void *src, size_t src_bytes, const int32_t *tables, size_t tables_len, const void *norm_table, void *out,
+                           int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
+  return augment_images(batch_size, images, augments, rotations, src, src_bytes, tables, tables_len, norm_table, out, height, width, dtype,
+                        workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

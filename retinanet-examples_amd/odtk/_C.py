@@ -80,6 +80,11 @@ class Augment(ctypes.Structure):
                 ('saturation', ctypes.c_float), ('hue', ctypes.c_uint8), ('pad_', ctypes.c_uint8 * 3)]
 
 
+class Rotation(ctypes.Structure):
+    """odtk_rotation_t"""
+    _fields_ = [('matrix', ctypes.c_double * 6), ('enabled', ctypes.c_int32), ('flip', ctypes.c_int32)]
+
+
 _SIGNATURES = {
     'odtk_version': (ctypes.c_char_p, []),
     'odtk_abi_struct_size': (ctypes.c_int, [ctypes.c_int]),
@@ -138,6 +143,8 @@ _SIGNATURES = {
                                               ctypes.c_int, _vp]),
     'odtk_augment_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), ctypes.POINTER(Augment), _vp, _sz, _vp, _sz, _vp, _vp,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
+    'odtk_augment_images_ex': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), ctypes.POINTER(Augment), ctypes.POINTER(Rotation), _vp, _sz,
+                                              _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_nms_sorted_runs': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_soft_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_int,
@@ -184,7 +191,7 @@ def library():
             fn.restype = res
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
-        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment)):
+        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -862,17 +869,26 @@ def preprocess_images(src, images, tables, table, height, width):
     return out
 
 
-def augment_images(src, images, augments, tables, table, height, width):
+def augment_images(src, images, augments, tables, table, height, width, rotations=None):
     """`preprocess_images` with the training augmentations between the resize and the normalisation (include/odtk_hip.h:
     odtk_augment_images): quarter turn and flip as an index map, brightness, contrast, hue, saturation, Pillow-exact.
     augments: a ctypes array (or sequence) of `Augment`, one per image, HOST memory; the rest as `preprocess_images`.
+    rotations: None, or a ctypes array (or sequence) of `Rotation`, one per image, HOST memory: the free rotation between the turn
+    and the flip (odtk_augment_images_ex).
     -> [len(images), 3, height, width] with channels_last strides."""
     images, out, args = _image_args('augment_images', src, images, tables, table, height, width)
     if not isinstance(augments, ctypes.Array):
         augments = (Augment * len(augments))(*augments)
     if len(augments) != len(images):
         raise RuntimeError('augment_images: %d images but %d augment descriptors' % (len(images), len(augments)))
-    _enqueue(library().odtk_augment_images, 'augment_images', src.device, len(images), images, augments, *args)
+    if rotations is None:
+        _enqueue(library().odtk_augment_images, 'augment_images', src.device, len(images), images, augments, *args)
+        return out
+    if not isinstance(rotations, ctypes.Array):
+        rotations = (Rotation * len(rotations))(*rotations)
+    if len(rotations) != len(images):
+        raise RuntimeError('augment_images: %d images but %d rotation descriptors' % (len(images), len(rotations)))
+    _enqueue(library().odtk_augment_images_ex, 'augment_images', src.device, len(images), images, augments, rotations, *args)
     return out
 
 

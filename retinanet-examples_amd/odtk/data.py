@@ -23,6 +23,9 @@ bytes per pixel) with the tables of Pillow's fixed-point bilinear resampling (`r
 `device_augment=True` is that hand-over plus the training augmentations: the workers draw the quarter turn, the flip and the
 colour factors and ship them as descriptors; the turn (Pillow's fixed-point index map), brightness, contrast, hue and saturation
 run on the device between the resize and the normalisation (`odtk_augment_images`), bit-identical to Pillow on the host.
+`augment_free_rotate=(lo, hi)` adds a rotation by a free angle between the quarter turn and the flip: Pillow's bilinear
+`Image.rotate` on the host, or, with `device_augment`, six doubles per image and one more pass on the device
+(`odtk_augment_images_ex`), the same bytes (`free_rotation_matrix`, `rotate_bilinear`).
 
 `CocoIndex` is the part of `pycocotools.coco.COCO` (nvidia/cocoapi master, un-pinned and absent from this
 image) that the reference touches: `dataset`, `imgs`, `getCatIds`, `getAnnIds`, `loadAnns`, `loadImgs`,
@@ -257,6 +260,59 @@ def index_map(pixels, canvas_width, canvas_height, coefficients):
     return np.ascontiguousarray(out)
 
 
+def free_rotation_matrix(width, height, angle):
+    """The matrix `Image.rotate(angle)` builds for a `width` x `height` image turned about its centre on its own canvas, in double
+    and in Pillow's operation order (the entries rounded to 15 places, as there): six coefficients (m0 .. m5) that take the centre
+    of an OUTPUT pixel to a point of the input,  xin = m0 (x + 0.5) + m1 (y + 0.5) + m2,  yin = m3 (x + 0.5) + m4 (y + 0.5) + m5.
+    `angle` in degrees, any real: positive is counter-clockwise on screen.  The device receives these six doubles."""
+    angle = float(angle) % 360.0
+    radians = -math.radians(angle)
+    m = [round(math.cos(radians), 15), round(math.sin(radians), 15), 0.0,
+         round(-math.sin(radians), 15), round(math.cos(radians), 15), 0.0]
+    cx, cy = int(width) / 2, int(height) / 2
+    m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
+    m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+    return tuple(m)
+
+
+def rotate_bilinear(pixels, matrix):
+    """`np.array(Image.fromarray(pixels).rotate(angle, resample=Image.BILINEAR))` for uint8 `[h, w, c]` and `matrix` =
+    `free_rotation_matrix(w, h, angle)`, without Pillow: its affine transform with the bilinear filter, every step one IEEE double
+    operation in its order.  A pixel whose source point lies outside the image is black; inside, the two taps of a row are clamped
+    to the row, the row below is used only if it exists, and the result is truncated to a byte."""
+    pixels = np.asarray(pixels)
+    h, w = pixels.shape[:2]
+    m0, m1, m2, m3, m4, m5 = (float(v) for v in matrix)
+    x = np.arange(w, dtype=np.float64)[None, :] + 0.5
+    y = np.arange(h, dtype=np.float64)[:, None] + 0.5
+    xin, yin = (m0 * x + m1 * y) + m2, (m3 * x + m4 * y) + m5
+    inside = (xin >= 0.0) & (xin < w) & (yin >= 0.0) & (yin < h)
+    xin, yin = xin - 0.5, yin - 0.5
+    fx, fy = np.floor(xin), np.floor(yin)
+    dx, dy = (xin - fx)[..., None], (yin - fy)[..., None]
+    col, row = np.clip(fx, -1, w).astype(np.int64), np.clip(fy, -1, h).astype(np.int64)     # (inside: -1 <= floor < size)
+    x0, x1 = np.clip(col, 0, w - 1), np.clip(col + 1, 0, w - 1)
+    p = pixels.astype(np.float64)
+    first, second = p[np.clip(row, 0, h - 1), x0], p[np.clip(row, 0, h - 1), x1]
+    v1 = first + (second - first) * dx
+    first, second = p[np.clip(row + 1, 0, h - 1), x0], p[np.clip(row + 1, 0, h - 1), x1]
+    below = ((row + 1 >= 0) & (row + 1 < h))[..., None]
+    v2 = np.where(below, first + (second - first) * dx, v1)
+    out = (v1 + (v2 - v1) * dy).astype(np.int64).astype(np.uint8)
+    out[~inside] = 0
+    return np.ascontiguousarray(out)
+
+
+def rotate_points(x, y, width, height, angle):
+    """Where `rotate_bilinear` (= `Image.rotate(angle)`) moves the points (x, y) of a `width` x `height` image: the inverse of the
+    pixel map, out - c = [[cos a, sin a], [-sin a, cos a]] (in - c) about c = (width / 2, height / 2), with the matrix' rounded
+    entries; float64 tensors in, float64 tensors out."""
+    m = free_rotation_matrix(width, height, angle)
+    cos, sin = m[0], m[3]
+    cx, cy = int(width) / 2, int(height) / 2
+    return cx + (cos * (x - cx) + sin * (y - cy)), cy + (cos * (y - cy) - sin * (x - cx))
+
+
 def luma(pixels):
     """`convert('L')` of uint8 RGB `[..., 3]`: (19595 R + 38470 G + 7471 B + 0x8000) >> 16."""
     p = np.asarray(pixels).astype(np.int64)
@@ -348,10 +404,15 @@ def adjust_hue(pixels, shift):
     return hsv_to_rgb(hsv)
 
 
-def augment_pixels(pixels, aug):
+def augment_pixels(pixels, aug, rotation=None):
     """Resized uint8 RGB `[h, w, 3]` and one AUGMENT_DTYPE record -> the augmented canvas: turn and flip (the index map), then
-    brightness, contrast, hue, saturation, in `__getitem__`'s order."""
+    brightness, contrast, hue, saturation, in `__getitem__`'s order.  With an enabled ROTATION_DTYPE record the map holds the turn
+    alone, and the free rotation (on the turned canvas) and the record's flip follow it, before the colours."""
     pixels = index_map(pixels, int(aug['canvas_width']), int(aug['canvas_height']), aug['map'])
+    if rotation is not None and int(rotation['enabled']):
+        pixels = rotate_bilinear(pixels, rotation['matrix'])
+        if int(rotation['flip']):
+            pixels = np.ascontiguousarray(pixels[:, ::-1])
     flags = int(aug['flags'])
     if flags & AUGMENT_BRIGHTNESS:
         pixels = adjust_brightness(pixels, aug['brightness'])
@@ -368,10 +429,11 @@ def augment_pixels(pixels, aug):
 AUGMENT_DTYPE = np.dtype([('canvas_width', '<i4'), ('canvas_height', '<i4'), ('map', '<i4', (6,)), ('flags', '<u4'),
                           ('brightness', '<f4'), ('contrast', '<f4'), ('saturation', '<f4'), ('hue', 'u1'), ('pad_', 'u1', (3,))])
                                                                     # odtk_augment_t (include/odtk_hip.h)
+ROTATION_DTYPE = np.dtype([('matrix', '<f8', (6,)), ('enabled', '<i4'), ('flip', '<i4')])     # odtk_rotation_t (include/odtk_hip.h)
 IMAGE_DTYPE =np.dtype([('src_offset', '<u8'), ('src_width', '<i4'), ('src_height', '<i4'), ('src_pitch', '<i4'),
                         ('out_width', '<i4'), ('out_height', '<i4'), ('mirror', '<i4'), ('x_table', '<i4'), ('y_table', '<i4'),
                         ('x_taps', '<i4'), ('y_taps', '<i4')])      # odtk_image_t (include/odtk_hip.h)
-_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, augments at byte (0: none), 0, 0
+_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, augments at byte (0: none), rotations at byte (0: none), 0
 _up16 = lambda n: (n + 15) // 16 * 16
 
 
@@ -385,12 +447,18 @@ class SourceBatch:
     With `device_augment=True` the geometry tuples are longer (`CocoDataset._augment_item`) and the buffer carries one
     odtk_augment_t per image between the image descriptors and the tables (the header's sixth word says where): the index map of
     the quarter turn and the flip, and the colour operations.  The batch is then padded to the canvases AFTER the turn, and
-    `apply_cpu` is the CPU implementation of `odtk_augment_images`."""
+    `apply_cpu` is the CPU implementation of `odtk_augment_images`.
+
+    With `augment_free_rotate` the tuples of the rotated images carry two more entries, the matrix of `free_rotation_matrix` and the
+    flip, and the buffer one odtk_rotation_t per image after the augment records (the header's seventh word says where; it is 0,
+    and the buffer is what it was, when no image of the batch is rotated).  The map of such an image is the quarter turn alone:
+    the free rotation and then the flip follow it on the turned canvas (`odtk_augment_images_ex`)."""
 
     @staticmethod
     def pack(sources, geometry, stride):
         """sources: uint8 `[h, w, 3]` tensors; geometry: `(out_width, out_height, mirror)` per image, or (device_augment)
-        `(out_width, out_height, 0, canvas_width, canvas_height, map, flags, brightness, contrast, saturation, hue)`."""
+        `(out_width, out_height, 0, canvas_width, canvas_height, map, flags, brightness, contrast, saturation, hue)`, or (free
+        rotation) that with `(matrix, flip)` appended."""
         up = lambda d: d + (stride - d % stride) % stride
         augmented = any(len(g) > 3 for g in geometry)
         if augmented:                                               # plain images of such a batch get the identity map
@@ -420,18 +488,26 @@ class SourceBatch:
         for aug, g in zip(augments, geometry):
             aug['canvas_width'], aug['canvas_height'], aug['map'], aug['flags'] = g[3], g[4], g[5], g[6]
             aug['brightness'], aug['contrast'], aug['saturation'], aug['hue'] = g[7], g[8], g[9], g[10]
+        rotated = any(len(g) > 11 for g in geometry)
+        rotations = np.zeros(len(sources) if rotated else 0, dtype=ROTATION_DTYPE)
+        for rot, g in zip(rotations, geometry):
+            if len(g) > 11:
+                rot['matrix'], rot['enabled'], rot['flip'] = g[11], 1, int(bool(g[12]))
         augments_at = _up16(4 * _HEADER_WORDS + images.nbytes) if augmented else 0
-        tables_at = _up16(max(augments_at, 4 * _HEADER_WORDS + images.nbytes) + augments.nbytes)
+        rotations_at = _up16(augments_at + augments.nbytes) if rotated else 0
+        tables_at = _up16(max(augments_at, rotations_at, 4 * _HEADER_WORDS + images.nbytes) + (rotations.nbytes if rotated else augments.nbytes))
         at = _up16(tables_at + 4 * length)
         for im in images:
             im['src_offset'] = at
             at = _up16(at + int(im['src_pitch']) * int(im['src_height']))
         buffer = _batch_buffer((at,))
         view = buffer.numpy()
-        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, augments_at, 0, 0)
+        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, augments_at, rotations_at, 0)
         view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + images.nbytes] = images.view(np.uint8)
         if augmented:
             view[augments_at:augments_at + augments.nbytes] = augments.view(np.uint8)
+        if rotated:
+            view[rotations_at:rotations_at + rotations.nbytes] = rotations.view(np.uint8)
         if tables:
             view[tables_at:tables_at + 4 * length].view(np.int32)[:] = np.concatenate(tables)
         for im, p in zip(images, sources):
@@ -444,11 +520,14 @@ class SourceBatch:
         self.buffer = buffer
         self.view = buffer.numpy()
         header = self.view[:4 * _HEADER_WORDS].view(np.int32)
-        self.batch, self.height, self.width, self.tables_at, self.tables_len, augments_at = (int(v) for v in header[:6])
+        self.batch, self.height, self.width, self.tables_at, self.tables_len, augments_at, rotations_at = (int(v) for v in header[:7])
         self.images = self.view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + self.batch * IMAGE_DTYPE.itemsize].view(IMAGE_DTYPE)
         self.augments = None                                        # one AUGMENT_DTYPE record per image with `device_augment`
         if augments_at:
             self.augments = self.view[augments_at:augments_at + self.batch * AUGMENT_DTYPE.itemsize].view(AUGMENT_DTYPE)
+        self.rotations = None                                       # one ROTATION_DTYPE record per image when one of them is rotated
+        if rotations_at:
+            self.rotations = self.view[rotations_at:rotations_at + self.batch * ROTATION_DTYPE.itemsize].view(ROTATION_DTYPE)
 
     def tables(self, buffer=None):
         """The int32 tables as a view of `buffer` (default: the host copy; pass the uploaded one for the device's view)."""
@@ -462,7 +541,7 @@ class SourceBatch:
 
     def apply_cpu(self, table, dtype=torch.float32):
         """-> `[B, 3, H, W]` `dtype`, channels_last storage: what `odtk_preprocess_images` (with augment descriptors:
-        `odtk_augment_images`) writes, computed on the host."""
+        `odtk_augment_images`, with rotation records `odtk_augment_images_ex`) writes, computed on the host."""
         table = table.to(device='cpu', dtype=dtype).reshape(-1)
         out = torch.zeros((self.batch, self.height, self.width, 3), dtype=dtype)
         channel = torch.tensor([0, 256, 512])
@@ -471,7 +550,7 @@ class SourceBatch:
             if im['mirror']:
                 pixels = pixels[:, ::-1].copy()
             if self.augments is not None:
-                pixels = augment_pixels(pixels, self.augments[k])
+                pixels = augment_pixels(pixels, self.augments[k], None if self.rotations is None else self.rotations[k])
             out[k, :pixels.shape[0], :pixels.shape[1]] = table[torch.from_numpy(pixels).long() + channel]
         return out.permute(0, 3, 1, 2)
 
@@ -496,20 +575,29 @@ class CocoDataset(data.dataset.Dataset):
     The random decisions of training are drawn from `random` in the reference's order (resize jitter,
     quarter-turn, flip, brightness, contrast, hue, saturation), so a seeded run makes the same choices.
 
+    `augment_free_rotate=(lo, hi)`, in degrees: every training item is rotated about its centre, on its own canvas, by an angle drawn
+    uniformly from the range, between the quarter turn and the flip (`Image.rotate(angle, resample=Image.BILINEAR)`; the corners it
+    leaves empty are black image pixels) and its boxes move with it (`_rotate_boxes`).  (0, 0), the default, is off: no draw is taken.
+
     `device_resize=True`: items are source pixels and the target geometry (`_source_item`); it refuses the quarter turns and the
-    colour options.  `device_augment=True`: the same hand-over, and those five travel as descriptors (`_augment_item`)."""
+    colour options and the free rotation.  `device_augment=True`: the same hand-over, and those travel as descriptors
+    (`_augment_item`)."""
 
     box_fields = 4
 
     def __init__(self, path, resize, max_size, stride, annotations=None, training=False, rotate_augment=False,
                  augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, device_resize=False,
-                 device_augment=False):
+                 device_augment=False, augment_free_rotate=(0, 0)):
         super().__init__()
+        augment_free_rotate = tuple(float(v) for v in augment_free_rotate)
+        if len(augment_free_rotate) != 2 or not all(math.isfinite(v) for v in augment_free_rotate) or augment_free_rotate[0] > augment_free_rotate[1]:
+            raise ValueError('augment_free_rotate must be a finite range (lo, hi) in degrees with lo <= hi, got %r' % (augment_free_rotate,))
         if device_resize and not device_augment:
             # quarter turns and the colour augmentations act on the RESIZED PIL image in the reference: they stay on the host path
             for name, value in (('rotate_augment', rotate_augment), ('augment_brightness', augment_brightness),
                                 ('augment_contrast', augment_contrast), ('augment_hue', augment_hue),
-                                ('augment_saturation', augment_saturation)):
+                                ('augment_saturation', augment_saturation),
+                                ('augment_free_rotate', augment_free_rotate if any(augment_free_rotate) else ())):
                 if value:
                     raise ValueError('device_resize=True cannot be combined with %s=%r: that augmentation works on the resized '
                                      'image on the host (use the default loader)' % (name, value))
@@ -522,6 +610,7 @@ class CocoDataset(data.dataset.Dataset):
         self.rotate_augment = rotate_augment
         self.augment_brightness, self.augment_contrast = augment_brightness, augment_contrast
         self.augment_hue, self.augment_saturation = augment_hue, augment_saturation
+        self.augment_free_rotate = augment_free_rotate if any(augment_free_rotate) else None       # None: off, no draw
         self.coco = CocoIndex(dataset=annotations) if isinstance(annotations, dict) else CocoIndex(annotations)
         self.ids = list(self.coco.imgs.keys())
         if 'categories' in self.coco.dataset:
@@ -570,6 +659,27 @@ class CocoDataset(data.dataset.Dataset):
             boxes[:, 2], boxes[:, 3] = h, w
         return boxes
 
+    def _free_rotate(self, im, boxes, categories, angle):
+        """Rotate the image by `angle` degrees (any real) about its centre on its own canvas, bilinear, black corners, and move
+        the boxes with it; boxes the rotation pushes out of the image are dropped with their categories."""
+        return (im.rotate(angle, resample=Image.BILINEAR),) + self._rotate_boxes(boxes, categories, angle, *im.size)
+
+    def _rotate_boxes(self, boxes, categories, angle, width, height):
+        """The boxes' half of `_free_rotate` -> (boxes, categories); `width`, `height`: the canvas.  The four corners move with the
+        pixels (`rotate_points`, in float64); the box becomes their enclosing axis-aligned box clipped to the canvas, and is dropped
+        when less than a pixel of its width or height is left.  None left: the "no box" row of `_get_target`."""
+        x, y, w, h = (boxes[:, k].double() for k in range(4))
+        xs, ys = rotate_points(torch.stack([x, x + w, x, x + w], 1), torch.stack([y, y, y + h, y + h], 1), width, height, angle)
+        left, right = xs.min(1).values.clamp(0, width), xs.max(1).values.clamp(0, width)
+        top, bottom = ys.min(1).values.clamp(0, height), ys.max(1).values.clamp(0, height)
+        moved = torch.stack([left, top, right - left, bottom - top], 1)
+        return self._kept_boxes(moved, categories, (moved[:, 2] >= 1) & (moved[:, 3] >= 1))
+
+    def _kept_boxes(self, boxes, categories, keep):
+        if not bool(keep.any()):
+            return torch.ones([1, self.box_fields]), torch.ones([1, 1]) * -1
+        return boxes[keep].float(), categories[keep]
+
     def _flip(self, im, boxes):
         im = im.transpose(Image.FLIP_LEFT_RIGHT)
         return im, self._flip_boxes(boxes, im.size[0])
@@ -610,7 +720,9 @@ class CocoDataset(data.dataset.Dataset):
         """The training item of `device_augment=True`: `(source pixels, (out_width, out_height, 0, canvas_width, canvas_height, map,
         flags, brightness, contrast, saturation, hue), target)`.  Every draw from `random` happens here, in the host path's order
         (jitter, quarter turn, flip, brightness, contrast, hue, saturation) and with `_colour`'s clamps; the turn and the flip
-        become the index map of `quarter_turn_map`, the colour operations flags and factors -- the pixels are untouched."""
+        become the index map of `quarter_turn_map`, the colour operations flags and factors -- the pixels are untouched.  With
+        `augment_free_rotate` the angle is drawn between the turn and the flip, the map holds the turn alone, and the tuple ends in
+        `(free_rotation_matrix of the turned canvas, flip)`."""
         im, ratio, size = self._open(image_id)
         pixels = torch.from_numpy(np.array(im, dtype=np.uint8))
         boxes, categories = self._get_target(image_id)
@@ -620,8 +732,13 @@ class CocoDataset(data.dataset.Dataset):
             boxes = self._turn_boxes(boxes, angle, *size)
         else:
             angle = 0
+        free = random.uniform(*self.augment_free_rotate) if self.augment_free_rotate else None
         mirror = random.randint(0, 1)
-        cw, ch, coefficients = quarter_turn_map(size[0], size[1], angle, self.turn_expands, mirror)
+        cw, ch, coefficients = quarter_turn_map(size[0], size[1], angle, self.turn_expands, mirror and free is None)
+        rotation = ()
+        if free is not None:
+            boxes, categories = self._rotate_boxes(boxes, categories, free, cw, ch)
+            rotation = (free_rotation_matrix(cw, ch, free), mirror)
         if mirror:
             boxes = self._flip_boxes(boxes, cw)
         flags, brightness, contrast, saturation, hue = 0, 1.0, 1.0, 1.0, 0
@@ -633,7 +750,7 @@ class CocoDataset(data.dataset.Dataset):
             flags, hue = flags | AUGMENT_HUE, hue_shift_byte(min(0.5, max(-0.5, random.normalvariate(0, self.augment_hue))))
         if self.augment_saturation:
             flags, saturation = flags | AUGMENT_SATURATION, max(0, random.normalvariate(1, self.augment_saturation))
-        geometry = size + (0, cw, ch, coefficients, flags, brightness, contrast, saturation, hue)
+        geometry = size + (0, cw, ch, coefficients, flags, brightness, contrast, saturation, hue) + rotation
         return pixels, geometry, torch.cat([boxes, categories], dim=1)
 
     def __getitem__(self, index):
@@ -650,6 +767,8 @@ class CocoDataset(data.dataset.Dataset):
             angle = random.randint(0, 3) * 90
             if self.rotate_augment and angle != 0:
                 im, boxes = self._quarter_turn(im, boxes, angle)
+            if self.augment_free_rotate:
+                im, boxes, categories = self._free_rotate(im, boxes, categories, random.uniform(*self.augment_free_rotate))
             if random.randint(0, 1):
                 im, boxes = self._flip(im, boxes)
             im = self._colour(im)
@@ -752,6 +871,23 @@ class RotatedCocoDataset(CocoDataset):
         boxes[:, 4] = t
         return boxes
 
+    def _rotate_boxes(self, boxes, categories, angle, width, height):
+        """The centre moves with the pixels, w and h stay, theta grows by the angle (counter-clockwise, the sign of `_turn_boxes`);
+        `absolute_angle` wraps theta as `_turn_boxes` does, otherwise theta is folded into [-pi / 4, pi / 4] by quarter turns of the
+        box about its own centre (an odd number of them swaps w and h).  A box whose centre leaves the canvas is dropped."""
+        x, y, w, h, t = (boxes[:, k].double() for k in range(5))
+        cx, cy = rotate_points(x + w / 2, y + h / 2, width, height, angle)
+        t = t + math.radians(float(angle) % 360.0)
+        if self.absolute_angle:
+            t = torch.remainder(torch.abs(t), math.pi) * torch.sign(t)
+        else:
+            quarters = torch.round(t / (math.pi / 2))
+            t = t - quarters * (math.pi / 2)
+            odd = torch.remainder(quarters, 2) == 1
+            w, h = torch.where(odd, h, w), torch.where(odd, w, h)
+        moved = torch.stack([cx - w / 2, cy - h / 2, w, h, t], 1)
+        return self._kept_boxes(moved, categories, (cx >= 0) & (cx <= width) & (cy >= 0) & (cy <= height))
+
     def _flip_boxes(self, boxes, width):
         boxes = super()._flip_boxes(boxes, width)
         boxes[:, 4] = -boxes[:, 4]
@@ -805,6 +941,8 @@ class DataIterator:
             lines.append('    resize on: {}'.format('the device (odtk_preprocess_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
         if self.device_augment:
             lines.append('    augmentations on: {}'.format('the device (odtk_augment_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
+        if self.dataset.augment_free_rotate:
+            lines.append('    free rotation: {:g} to {:g} degrees'.format(*self.dataset.augment_free_rotate))
         return '\n'.join(lines)
 
     def __len__(self):
@@ -821,7 +959,11 @@ class DataIterator:
         images = (_C.Image * batch.batch).from_buffer_copy(batch.images.tobytes())
         if batch.augments is not None:                              # resize to bytes, (sum of L,) gather + colour chain + table + pad
             augments = (_C.Augment * batch.batch).from_buffer_copy(batch.augments.tobytes())
-            return _C.augment_images(uploaded, images, augments, batch.tables(uploaded), self.table, batch.height, batch.width)
+            rotations = None                                        # (with them: + the free rotation, between the resize and the sum)
+            if batch.rotations is not None:
+                rotations = (_C.Rotation * batch.batch).from_buffer_copy(batch.rotations.tobytes())
+            return _C.augment_images(uploaded, images, augments, batch.tables(uploaded), self.table, batch.height, batch.width,
+                                     rotations=rotations)
         return _C.preprocess_images(uploaded, images, batch.tables(uploaded), self.table, batch.height, batch.width)
 
     def __iter__(self):

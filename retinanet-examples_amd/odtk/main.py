@@ -15,6 +15,8 @@ What differs from the reference, and why:
     HIP launch per batch (odtk/data.py), bit-identical to the default loader.
   * `--device-augment` (train) is new as well: `--device-resize` plus the training augmentations (`--augment-rotate` and the four
     colour options) on the GPU, as a short chain of HIP launches per batch, bit-identical to Pillow on the host.
+  * `--augment-free-rotate MIN MAX` (train), which the reference parses and ignores, rotates every training image by an angle drawn
+    from the range, bilinear, on its own canvas, and its boxes with it; with `--device-augment` on the GPU, the same pixels.
   * `--soft-nms {linear,gaussian}` (infer; train: its validation passes) with `--soft-nms-sigma` / `--soft-nms-min-score` is new:
     Soft-NMS (odtk/box.py:soft_nms, one HIP launch) instead of the reference's hard suppression.  Never stored in a checkpoint.
 """
@@ -84,7 +86,8 @@ TRAIN_FLAGS = [
     _flag('--device-augment', bool, text='--device-resize, and the quarter turns and colour augmentations run on the device as '
           'well, bit-identical to the host loader', default=argparse.SUPPRESS),
     _flag('--augment-rotate', bool, text='random quarter turns'),
-    _flag('--augment-free-rotate', float, [0, 0], 'accepted for compatibility (unused by the reference as well)', nargs=2,
+    _flag('--augment-free-rotate', float, [0, 0], 'rotate every training image about its centre by an angle drawn uniformly from '
+          'this range of degrees, counter-clockwise positive, and its boxes with it (0 0: off; not with --device-resize alone)', nargs=2,
           metavar='value value'),
     _flag('--augment-brightness', float, 0.002, 'sigma of the brightness factor', metavar='value'),
     _flag('--augment-contrast', float, 0.002, 'sigma of the contrast factor', metavar='value'),
@@ -217,7 +220,8 @@ def worker(rank, args, world, spawned=False):
                                augment_saturation=args.augment_saturation, regularization_l2=args.regularization_l2,
                                rotated_bbox=args.rotated_bbox, absolute_angle=args.absolute_angle,
                                num_workers=args.workers, device_resize=getattr(args, 'device_resize', False),
-                               device_augment=getattr(args, 'device_augment', False))
+                               device_augment=getattr(args, 'device_augment', False),
+                               augment_free_rotate=tuple(args.augment_free_rotate))
         if args.command == 'infer':
             return infer.infer(model, args.images, args.output, args.resize, args.max_size, args.batch,
                                annotations=args.annotations, mixed_precision=not args.full_precision,

@@ -253,14 +253,16 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
           val_iterations, lr, warmup, milestones, gamma, rank=0, world=1, mixed_precision=True, with_apex=False,
           use_dali=False, verbose=True, metrics_url=None, logdir=None, rotate_augment=False, augment_brightness=0.0,
           augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, regularization_l2=0.0001, rotated_bbox=False,
-          absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False):
+          absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False, augment_free_rotate=(0, 0)):
     """Train `model` on the images under `path` -- the reference's `train.train` (train.py:18-214), same
     arguments: COCO-style annotations through odtk/data.py (`jitter` = the range of short-side sizes),
     `train_batches` above, periodic validation through `infer.infer`, checkpoints to `state['path']`, scalars
     to `logdir`, metrics to `metrics_url`.  `with_apex` / `use_dali` are errors (dropped dependencies).  `device_resize`: resize,
     flip, padding and normalisation of the images run on the device (odtk/data.py), for training and validation alike; it excludes
     `rotate_augment` and the colour augmentations (ValueError).  `device_augment`: `device_resize`, and those augmentations run on the
-    device as well (odtk_augment_images), bit-identical to the host loader."""
+    device as well (odtk_augment_images), bit-identical to the host loader.  `augment_free_rotate` = (lo, hi) in degrees: every
+    training image is rotated about its centre by an angle drawn from that range, its boxes with it (odtk/data.py; on the host, or
+    with `device_augment` on the device, the same pixels either way); (0, 0) is off."""
     from . import infer as infer_module
     from .data import DataIterator, RotatedDataIterator
     if use_dali or with_apex:
@@ -274,7 +276,7 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
         path, jitter, max_size, batch_size, model.stride, world, annotations, training=True,
         rotate_augment=rotate_augment, augment_brightness=augment_brightness, augment_contrast=augment_contrast,
         augment_hue=augment_hue, augment_saturation=augment_saturation, device=device, num_workers=num_workers, device_resize=device_resize,
-        device_augment=device_augment, **extra)
+        device_augment=device_augment, augment_free_rotate=tuple(augment_free_rotate), **extra)
     if verbose:
         print(data_iterator)
         print('    device: {} {}'.format(world, 'cpu' if device.type == 'cpu' else 'GPU' if world == 1 else 'GPUs'))

@@ -9,9 +9,12 @@ up as preprocess_images_kernel<2> / <4>.
 `--augment` times the augmentation chain instead (odtk_augment_images, csrc/augment.hpp: resize to bytes, sum of L, gather + colour
 chain + table + pad) on the same batch, with all five options on, next to the plain launch and to its own bound (source read, the
 byte image written once and read twice, the output written).  It runs the chain with every image unturned, every image turned by
-90 degrees (expand: the gather walks columns of the byte image) and with the loader's mix of turns.
+90 degrees (expand: the gather walks columns of the byte image) and with the loader's mix of turns.  With `--free-rotate` as well
+it times odtk_augment_images_ex with EVERY image rotated by a free angle (one more pass: the finished canvas bytes written once
+and read by the sum and the colour pass), each row next to the chain without the rotation in the same process; under
+`rocprofv3 --kernel-trace --stats` the added pass shows up as augment_rotate_kernel next to preprocess_images_kernel<4, true>.
 
-  python tools/device_resize_probe.py [--iters 200] [--batch 8] [--source 640x480] [--augment]"""
+  python tools/device_resize_probe.py [--iters 200] [--batch 8] [--source 640x480] [--augment [--free-rotate]]"""
 import argparse
 import os
 import sys
@@ -71,6 +74,25 @@ def augment_probe(args, sources, ow, oh):
                       'bytes %d -> bound %.1f us at 8 TB/s (%.1f %% of that rate); %.2fx the plain launch'
                       % (str(dtype).replace('torch.', ''), label + ',', name, batch.batch, batch.height, batch.width, us, args.iters, moved,
                          bound, 100 * bound / us, us / us_plain))
+                if not args.free_rotate:
+                    continue
+                # the same images, each rotated by its own angle between the turn and the flip
+                geometry = []
+                for k in range(args.batch):
+                    cw, ch, coefficients = D.quarter_turn_map(ow, oh, angle(k), True, False)
+                    geometry.append((ow, oh, 0, cw, ch, coefficients) + colours + (D.free_rotation_matrix(cw, ch, -30.0 + 60.0 * (k + 0.5) / args.batch), k % 2))
+                rotated = D.SourceBatch(D.SourceBatch.pack(sources, geometry, 128))
+                rotated_up = rotated.buffer.cuda()
+                rotated_augments = (_C.Augment * rotated.batch).from_buffer_copy(rotated.augments.tobytes())
+                rotations = (_C.Rotation * rotated.batch).from_buffer_copy(rotated.rotations.tobytes())
+                run_rotated = lambda: _C.augment_images(rotated_up, images, rotated_augments, rotated.tables(rotated_up), table, rotated.height,
+                                                        rotated.width, rotations=rotations)
+                run_rotated()
+                us_rotated = timed(run_rotated, args.iters)
+                moved_rotated = moved + resized * 2                  # the canvas bytes written once, and the taps read
+                print('%-8s   + free rotation of every image (-30 .. 30 degrees): %.1f us per batch, %.1f us more than the row above (%.2fx); '
+                      'algorithmic bytes %d -> bound %.1f us at 8 TB/s'
+                      % (str(dtype).replace('torch.', ''), us_rotated, us_rotated - us, us_rotated / us, moved_rotated, moved_rotated / HBM_PEAK * 1e6))
 
 
 def main():
@@ -79,6 +101,8 @@ def main():
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--source', default='640x480')
     ap.add_argument('--augment', action='store_true', help='time the augmentation chain (odtk_augment_images)')
+    ap.add_argument('--free-rotate', action='store_true', help='with --augment: also time the chain with every image rotated by a free '
+                    'angle (odtk_augment_images_ex)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU: a timing from anywhere else says nothing'
     sw, sh = (int(v) for v in args.source.split('x'))

@@ -13,7 +13,11 @@ Pillow returns a copy: the resize is NOT in the host path's figures.  PROBE_SIZE
   python tools/loader_probe.py --augment
 the same for TRAINING items with all five augmentations on (quarter turns, brightness, contrast, hue, saturation): the host path
 (workers resize, turn and enhance with Pillow) against device_augment=True (workers ship source pixels and descriptors, the chain
-of odtk_augment_images does the rest)."""
+of odtk_augment_images does the rest).
+
+  python tools/loader_probe.py --augment --free-rotate
+the same with augment_free_rotate=(-30, 30) on top: the host path rotates the resized image with Pillow (bilinear, in double), the
+descriptor path ships six doubles per image and odtk_augment_images_ex rotates on the device."""
 import json
 import os
 import sys
@@ -32,8 +36,11 @@ N = int(os.environ.get('PROBE_IMAGES', 192))
 REPEAT = int(os.environ.get('PROBE_REPEAT', 1))
 WIDTH, HEIGHT = (int(v) for v in os.environ.get('PROBE_SIZE', '1280x800').split('x'))
 AUGMENT = '--augment' in sys.argv[1:]
+FREE_ROTATE = AUGMENT and '--free-rotate' in sys.argv[1:]
 OPTIONS = dict(training=True, rotate_augment=True, augment_brightness=0.002, augment_contrast=0.002, augment_hue=0.0002,
                augment_saturation=0.002) if AUGMENT else {}                # the sigmas are `odtk train`'s defaults
+if FREE_ROTATE:
+    OPTIONS['augment_free_rotate'] = (-30, 30)
 MODES = os.environ.get('PROBE_MODES', 'host,device').split(',')
 scratch = tempfile.mkdtemp(prefix='odtk_probe_')
 yy, xx = np.mgrid[0:HEIGHT, 0:WIDTH]
@@ -54,8 +61,8 @@ for mode in MODES:
     device_resize = mode == 'device'
     switch = {'device_augment' if AUGMENT else 'device_resize': device_resize}
     if AUGMENT:
-        print('--- training items, five augmentations on: %s' % ('device_augment=True: workers ship source pixels and descriptors' if device_resize
-                                                                 else 'host path: workers resize, turn and enhance with Pillow'))
+        print('--- training items, five augmentations on%s: %s' % (' and free rotation by -30 .. 30 degrees' if FREE_ROTATE else '', ('device_augment=True: workers ship source pixels and descriptors' if device_resize
+                                                                 else 'host path: workers resize, turn and enhance with Pillow')))
     else:
         print('--- %s' % ('device_resize=True: workers ship source pixels' if device_resize else 'host path: workers resize with Pillow'))
     ds = CocoDataset(scratch, 800, 1333, 128, ann, **switch, **OPTIONS)
