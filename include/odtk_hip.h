@@ -46,6 +46,7 @@ extern "C" {
 
 #define ODTK_MAX_LEVELS    6       /* pyramid levels per call (P3..P7 = 5); keeps kernargs < 4 KiB */
 #define ODTK_MAX_ANCHORS   32      /* anchors per cell (9 axis-aligned, 27 rotated)       */
+#define ODTK_ATSS_MAX_TOPK 16      /* nearest cells per box and level that ATSS may ask for */
 #define ODTK_MAX_TOP_N     16384   /* per-level top_n (<= 4096: 32 KiB LDS sort; beyond: a 128 KiB variant) */
 #define ODTK_MAX_NMS_COUNT 7680    /* candidates per image nms keeps LDS-resident (5 x 1000 by default);  */
 #define ODTK_MAX_NMS_COUNT_SCRATCH (1 << 22) /* beyond that, up to this, the key list lives in the workspace   */
@@ -459,6 +460,26 @@ int odtk_snap_to_anchors_levels(int batch_size, const float *targets, int n_max,
                                 float iou_background, float iou_foreground, void *stream);
 
 /*
+ * odtk_atss_assign_levels -- ATSS target assignment (adaptive training sample selection, Zhang et al., CVPR 2020) for all pyramid
+ * levels of the batch: the alternative to the fixed-IoU rule above, axis-aligned boxes only.  No reference equivalent; the
+ * definition -- the contract -- is spelled out in csrc/atss.hpp and restated in numpy in tests/atss_ref.py:
+ *   per box and level the `topk` cells whose centres are nearest to the box centre (ties: lower cell index) are its candidates,
+ *   with all their anchors; t = mean + sample standard deviation of the candidates' IoUs over ALL levels (float64, summed in list
+ *   order); a candidate is positive when its IoU >= t and its cell centre lies more than 0.01 inside the box; an anchor positive
+ *   for several boxes goes to the largest IoU (ties: the earliest row).
+ * Inputs and outputs as for the levels form of the fixed-IoU rule (its level descriptor is reused), except that
+ * depth is class + 1 or 0 -- ATSS has no ignore band -- and that every element of every output is written by this call.  n_max == 0
+ * or only padding rows: all outputs zero.  A small box that contains no cell centre gets no positives: that is ATSS.
+ * Two launches (one wave per target row: candidates + threshold into the workspace; one thread per anchor: assignment), no
+ * atomics, timed under ODTK_KERNEL_ATSS_STATS and ODTK_KERNEL_TARGETS.  Workspace: 96 bytes per target row and level (two-phase query).
+ * ODTK_ERR_INVALID: null pointers, n_levels outside 1..ODTK_MAX_LEVELS, topk outside 1..ODTK_ATSS_MAX_TOPK, num_anchors outside
+ * 1..ODTK_MAX_ANCHORS, non-positive sizes or strides, batch_size > 65535, levels or workspaces beyond 2^31 - 1.
+ */
+int odtk_atss_assign_levels(int batch_size, const float *targets, int n_max, int n_levels,
+                            const odtk_snap_level_t *levels, int num_anchors, int num_classes, int topk,
+                            void *workspace, size_t workspace_size, void *stream);
+
+/*
  * odtk_snap_to_anchors_rotated_levels -- the same assignment for ROTATED boxes (reference odtk/box.py:192-252, whose overlap is
  * the pairwise polygon IoU csrc/cuda/nms_iou.cu:324-387), all pyramid levels of the batch in ONE launch: no [27*H*W, N] IoU
  * matrix, no per-image host loop.  The ground truth arrives as the reference's `rotate_boxes` leaves it (utils.py:33-82):
@@ -563,7 +584,8 @@ int odtk_retina_loss_levels_backward(int n_levels, const odtk_loss_level_t *leve
 #define ODTK_KERNEL_UPSAMPLE  13  /* upsample_nearest2x_kernel                                         */
 #define ODTK_KERNEL_STEM_PACK 14  /* stem_pack_kernel (space-to-depth pack of the network input)        */
 #define ODTK_KERNEL_LOSS_REDUCE 15 /* loss_reduce_kernel (second launch of the forward through a workspace)   */
-#define ODTK_KERNEL_COUNT     16
+#define ODTK_KERNEL_ATSS_STATS 16 /* atss_stats_kernel (ATSS: candidates + threshold; its dense launch counts as ODTK_KERNEL_TARGETS) */
+#define ODTK_KERNEL_COUNT     17
 /* on: 0 = off, otherwise a bit mask of kernel ids (1 << ODTK_KERNEL_*), -1 = all.  An event pair
  * is a queue marker before and after the kernel: cheap for the 3 post-processing launches of a step,
  * measurably NOT free for the ~110 epilogue launches (about 10 % of an 8.7 ms step), so time those

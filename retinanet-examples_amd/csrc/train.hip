@@ -1,10 +1,11 @@
-// train.hip -- target assignment (odtk_snap_to_anchors*) and the focal + smooth-L1 loss: launch shapes, odtk_debug_loss_*,
-// odtk_retina_loss_*.
+// train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels) and the focal + smooth-L1 loss: launch shapes,
+// odtk_debug_loss_*, odtk_retina_loss_*.
 #include <cstring>
 #include <mutex>
 
 #include "runtime.hpp"
 #include "targets.hpp"
+#include "atss.hpp"
 #include "loss.hpp"
 
 namespace {
@@ -327,6 +328,59 @@ int odtk_snap_to_anchors_rotated_levels(int batch_size, const float *gt_axis, co
   for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) la.block_begin[l] = total;
   timed_launch(ODTK_KERNEL_TARGETS, odtk::snap_to_anchors_rotated_levels_kernel, dim3(total, batch_size), dim3(odtk::kSnapThreads), 0,
                static_cast<hipStream_t>(stream), la);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_atss_assign_levels(int batch_size, const float *targets, int n_max, int n_levels, const odtk_snap_level_t *levels,
+                            int num_anchors, int num_classes, int topk, void *workspace, size_t workspace_size, void *stream) {
+  // grid.y carries the image in both launches
+  if (batch_size <= 0 || batch_size > 65535 || n_max < 0 || n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || num_anchors <= 0 ||
+      num_anchors > ODTK_MAX_ANCHORS || num_classes <= 0 || topk < 1 || topk > ODTK_ATSS_MAX_TOPK)
+    return ODTK_ERR_INVALID;
+  const unsigned long long rows = 1ull * batch_size * n_max * n_levels;     // one record per image, level and target row
+  if (rows * sizeof(odtk::AtssRecord) > 0x7fffff00ull) return ODTK_ERR_INVALID;      // the size query answers in an int
+  const size_t need = align_up(rows ? rows * sizeof(odtk::AtssRecord) : 1);
+  if (!workspace) return static_cast<int>(need);                                      // two-phase convention of the reference's plugins
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!levels || (n_max > 0 && !targets) || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return ODTK_ERR_INVALID;
+  odtk::AtssArgs aa;
+  std::memset(&aa, 0, sizeof aa);
+  aa.targets = targets;
+  aa.records = static_cast<odtk::AtssRecord *>(workspace);
+  aa.by_anchors = odtk::fastdiv_make(num_anchors);
+  aa.n_levels = n_levels;
+  aa.n_max = n_max;
+  aa.num_anchors = num_anchors;
+  aa.num_classes = num_classes;
+  aa.topk = topk;
+  unsigned long long total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const odtk_snap_level_t &lv = levels[l];
+    if (!lv.anchors || !lv.box_target || !lv.depth || lv.height <= 0 || lv.width <= 0 || lv.stride <= 0) return ODTK_ERR_INVALID;
+    const long long cells = 1ll * num_anchors * lv.height * lv.width;
+    if (cells > 0x7fffffffll) return ODTK_ERR_INVALID;        // the kernels index cells with int
+    odtk::AtssLevel &al = aa.lv[l];
+    al.cls_target = lv.cls_target;
+    al.box_target = lv.box_target;
+    al.depth = lv.depth;
+    al.height = lv.height;
+    al.width = lv.width;
+    al.stride = static_cast<float>(lv.stride);
+    al.by_width = odtk::fastdiv_make(static_cast<uint32_t>(lv.width));
+    std::memcpy(al.anchors, lv.anchors, sizeof(float) * 4 * num_anchors);
+    aa.block_begin[l] = static_cast<uint32_t>(total);
+    total += static_cast<unsigned long long>((cells + odtk::kAtssThreads - 1) / odtk::kAtssThreads);
+  }
+  if (total > 0x7fffffffull) return ODTK_ERR_INVALID;
+  for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) aa.block_begin[l] = static_cast<uint32_t>(total);
+  if (n_max > 0) {
+    timed_launch(ODTK_KERNEL_ATSS_STATS, odtk::atss_stats_kernel, dim3(n_max, batch_size), dim3(odtk::kWave), 0,
+                 static_cast<hipStream_t>(stream), aa);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  timed_launch(ODTK_KERNEL_TARGETS, odtk::atss_assign_kernel, dim3(static_cast<unsigned>(total), batch_size), dim3(odtk::kAtssThreads), 0,
+               static_cast<hipStream_t>(stream), aa);
   ODTK_HIP_TRY(hipGetLastError());
   return ODTK_OK;
 }

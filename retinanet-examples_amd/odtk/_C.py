@@ -30,6 +30,7 @@ F32, BF16, F16 = 0, 1, 2
 FLAG_ROTATED, FLAG_LOGITS, FLAG_ROTATED_NMS_FIXED_ANGLE = 1, 2, 4
 MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32, 16384, 7680, 1 << 22
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
+ATSS_MAX_TOPK = 16
 
 _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
@@ -109,6 +110,8 @@ _SIGNATURES = {
                                             _vp, _vp, _vp, _vp]),
     'odtk_snap_to_anchors_levels': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SnapLevel),
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp]),
+    'odtk_atss_assign_levels': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SnapLevel), ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_retina_loss_forward': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 3 + [_vp, _vp]),
     'odtk_retina_loss_backward': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 3 +
                                   [_vp, _vp, _vp, _vp, _vp]),
@@ -162,7 +165,7 @@ _SIGNATURES = {
 KERNEL_NAMES = ('prefilter_scan_kernel', 'select_decode_kernel', 'nms_kernel', 'iou_pairs_kernel', 'bias_act_kernel',
                 'snap_to_anchors_kernel', 'gemm_bias_act', 'retina_loss_kernel', 'select_hist_kernel', 'select_filter_kernel',
                 'nms_first_round_kernel', 'rotated_sup_matrix_kernel', 'bias_act_maxpool_kernel', 'upsample_nearest2x_kernel',
-                'stem_pack_kernel', 'loss_reduce_kernel')
+                'stem_pack_kernel', 'loss_reduce_kernel', 'atss_stats_kernel')
 # HBM bytes the epilogue entry points move, per kernel name, while `traffic_count` is on (bench.py's epilogue_roofline: the
 # algorithmic bytes of every call -- each element read once and written once, + the skip input -- divided by the kernel time)
 traffic_count = False
@@ -584,16 +587,13 @@ def snap_to_anchors_rotated_levels(gt_axis, gt_quads, gt_class, anchors_list, nu
     return out
 
 
-def snap_to_anchors_levels(targets, anchors_list, num_classes, sizes, strides, iou_background, iou_foreground,
-                           want_cls_target=True):
-    """`snap_to_anchors` for every pyramid level in ONE launch.  anchors_list: per level [A, 4]; sizes: per level (H, W).
-    -> lists (cls_targets or Nones, box_targets, depths)."""
+def _snap_levels(what, targets, anchors_list, sizes, strides):
+    """Checks shared by the level forms over [B, N, 5] targets; enters every level's HOST anchor table into its descriptor
+    -> (descriptor array, the ctypes arrays it points into, number of levels, anchors per cell)."""
     _check_input(targets, 'targets')
     if targets.dim() != 3 or targets.shape[2] != 5:
         raise RuntimeError('targets must be [B, N, 5]')
-    n = _snap_level_count('snap_to_anchors_levels', anchors_list, sizes, strides)
-    b, n_max = targets.shape[0], targets.shape[1]
-    dev = targets.device
+    n = _snap_level_count(what, anchors_list, sizes, strides)
     arr = (SnapLevel * n)()
     keep = []
     a = None
@@ -602,12 +602,37 @@ def snap_to_anchors_levels(targets, anchors_list, num_classes, sizes, strides, i
         if a is None:
             a = ln // 4
         if ln != 4 * a:
-            raise RuntimeError('snap_to_anchors_levels: every level needs the same number of anchors')
+            raise RuntimeError('%s: every level needs the same number of anchors' % what)
         keep.append(carr)
         lv.anchors = ctypes.cast(carr, _fp)
+    return arr, keep, n, a
+
+
+def snap_to_anchors_levels(targets, anchors_list, num_classes, sizes, strides, iou_background, iou_foreground,
+                           want_cls_target=True):
+    """`snap_to_anchors` for every pyramid level in ONE launch.  anchors_list: per level [A, 4]; sizes: per level (H, W).
+    -> lists (cls_targets or Nones, box_targets, depths)."""
+    arr, keep, n, a = _snap_levels('snap_to_anchors_levels', targets, anchors_list, sizes, strides)
+    b, n_max = targets.shape[0], targets.shape[1]
+    dev = targets.device
     out = _snap_targets(arr, b, a, num_classes, 4, sizes, strides, dev, want_cls_target)
     _launch(library().odtk_snap_to_anchors_levels, 'snap_to_anchors_levels', dev, b, targets.data_ptr(), n_max, n, arr, a,
             int(num_classes), float(iou_background), float(iou_foreground))
+    return out
+
+
+def atss_assign_levels(targets, anchors_list, num_classes, sizes, strides, topk=9, want_cls_target=True):
+    """ATSS target assignment for every pyramid level of the batch (csrc/atss.hpp; two launches and a workspace).  Arguments and
+    results as `snap_to_anchors_levels`, with `topk` (1..ATSS_MAX_TOPK nearest cells per box and level) in place of the IoU
+    thresholds; depth is class + 1 or 0."""
+    arr, keep, n, a = _snap_levels('atss_assign_levels', targets, anchors_list, sizes, strides)
+    if not 1 <= int(topk) <= ATSS_MAX_TOPK:
+        raise RuntimeError('atss_assign_levels: topk must be in 1..%d' % ATSS_MAX_TOPK)
+    b, n_max = targets.shape[0], targets.shape[1]
+    dev = targets.device
+    out = _snap_targets(arr, b, a, num_classes, 4, sizes, strides, dev, want_cls_target)
+    _enqueue(library().odtk_atss_assign_levels, 'atss_assign_levels', dev, b, targets.data_ptr(), n_max, n, arr, a,
+             int(num_classes), int(topk))
     return out
 
 

@@ -17,6 +17,8 @@ Differences, all deliberate:
     box.py:408 calls an undefined `iou`).
   * `decode_levels` / `detect` are additions: all pyramid levels x the whole batch in one
     enqueue, with no host synchronisation (GPU only).
+  * `atss_assign_levels` is an addition: ATSS target assignment next to the reference's fixed-IoU
+    `snap_to_anchors` (HIP kernels for GPU tensors, pure torch otherwise).
 """
 
 import math
@@ -197,6 +199,135 @@ def snap_to_anchors_levels(targets, sizes, strides, anchors_list, num_classes, a
     _require_gpu(targets, 'snap_to_anchors_levels')
     return _C.snap_to_anchors_levels(targets.float().contiguous(), anchors_list, num_classes, [(int(h), int(w)) for h, w in sizes],
                                      [int(s) for s in strides], anchor_ious[0], anchor_ious[1], want_cls_target)
+
+
+def _atss_image(boxes, sizes, strides, anchors_list, num_classes, topk, want_cls_target):
+    """ATSS for the valid rows [N, 5] of one image, pure torch, in the steps of csrc/atss.hpp -> per level (cls, box, depth)."""
+    dev = boxes.device
+    n = boxes.shape[0]
+    if n == 0:
+        return [(boxes.new_zeros((anchors.shape[0], num_classes, h, w)) if want_cls_target else None,
+                 boxes.new_zeros((anchors.shape[0], 4, h, w)), boxes.new_zeros((anchors.shape[0], 1, h, w)))
+                for (h, w), anchors in zip(sizes, anchors_list)]
+    xy1 = boxes[:, :2]
+    xy2 = boxes[:, :2] + boxes[:, 2:4] - 1
+    xyxy = torch.cat([xy1, xy2], 1)
+    b_size = xy2 - xy1 + 1
+    b_area = b_size[:, 0] * b_size[:, 1]
+    b_ctr = xy1 + 0.5 * b_size
+    classes = boxes[:, 4]
+    margin = torch.tensor(0.01, dtype=torch.float32, device=dev)
+
+    # 1. candidates: per level the nearest cells (a stable ascending sort: ties to the lower cell, NaN last), all their anchors
+    levels = []
+    for (h, w), s, anchors in zip(sizes, strides, anchors_list):
+        s = float(s)
+        anchors = anchors.to(device=dev, dtype=torch.float32)
+        px = torch.arange(w, device=dev, dtype=torch.float32) * s + 0.5 * s + 0.5
+        py = torch.arange(h, device=dev, dtype=torch.float32) * s + 0.5 * s + 0.5
+        dx, dy = px[None, :] - b_ctr[:, 0:1], py[None, :] - b_ctr[:, 1:2]
+        d2 = ((dx * dx)[:, None, :] + (dy * dy)[:, :, None]).reshape(n, h * w)
+        near, cells = torch.sort(d2, dim=1, stable=True)
+        near, cells = near[:, :min(topk, h * w)], cells[:, :min(topk, h * w)]
+        yc, xc = torch.div(cells, w, rounding_mode='floor'), cells % w
+        gx, gy = xc.float() * s, yc.float() * s
+        a1x, a1y = gx[:, :, None] + anchors[:, 0], gy[:, :, None] + anchors[:, 1]                    # [N, k, A]
+        a2x, a2y = gx[:, :, None] + anchors[:, 2], gy[:, :, None] + anchors[:, 3]
+        a_area = (a2x - a1x + 1) * (a2y - a1y + 1)
+        iw = (torch.min(a2x, xy2[:, 0, None, None]) - torch.max(a1x, xy1[:, 0, None, None]) + 1).clamp(min=0)
+        ih = (torch.min(a2y, xy2[:, 1, None, None]) - torch.max(a1y, xy1[:, 1, None, None]) + 1).clamp(min=0)
+        inter = iw * ih
+        iou = inter / (a_area + b_area[:, None, None] - inter)
+        cx, cy = px[xc], py[yc]
+        inside = ((cx - xy1[:, 0:1] > margin) & (cy - xy1[:, 1:2] > margin) &
+                  (xy2[:, 0:1] - cx > margin) & (xy2[:, 1:2] - cy > margin))                       # [N, k]
+        levels.append((cells, ~torch.isnan(near), iou, inside))
+
+    # 2. threshold: float64 mean and sample deviation of the listed IoUs, summed one after the other in list order
+    a = anchors_list[0].shape[0]
+    listed = torch.cat([iou.reshape(n, -1) for _, _, iou, _ in levels], 1).double()
+    chosen = torch.cat([ok[:, :, None].expand(-1, -1, a).reshape(n, -1) for _, ok, _, _ in levels], 1)
+    count = chosen.sum(1)
+    total = torch.zeros(n, dtype=torch.float64, device=dev)
+    for i in range(listed.shape[1]):
+        total = torch.where(chosen[:, i], total + listed[:, i], total)
+    mean = total / count.double()
+    squares = torch.zeros(n, dtype=torch.float64, device=dev)
+    for i in range(listed.shape[1]):
+        d = listed[:, i] - mean
+        squares = torch.where(chosen[:, i], squares + d * d, squares)
+    var = torch.where(count > 1, squares / (count - 1).double(), torch.zeros_like(squares))
+    thresh = torch.where(count > 0, mean + torch.sqrt(var), torch.full_like(mean, float('nan')))
+
+    out = []
+    for (h, w), s, anchors, (cells, ok, iou, inside) in zip(sizes, strides, anchors_list, levels):
+        # 3. positives; 4. an anchor goes to the largest IoU, the earliest box on a tie
+        positive = (iou.double() >= thresh[:, None, None]) & (ok & inside)[:, :, None]            # [N, k, A]
+        flat = cells[:, :, None] + torch.arange(a, device=dev)[None, None, :] * (h * w)            # index into [A, H, W]
+        owner = torch.full((a * h * w,), -1, dtype=torch.long, device=dev)
+        best = torch.zeros(a * h * w, dtype=torch.float32, device=dev)
+        for g in range(n):
+            idx, ov = flat[g][positive[g]], iou[g][positive[g]]
+            take = (owner[idx] < 0) | (ov > best[idx])
+            owner[idx[take]] = g
+            best[idx[take]] = ov[take]
+        # 5. outputs in [A, *, H, W] order
+        hit = (owner >= 0).nonzero().view(-1)
+        box_target = torch.zeros((a * h * w, 4), dtype=torch.float32, device=dev)
+        depth = torch.zeros(a * h * w, dtype=torch.float32, device=dev)
+        if hit.numel():
+            cell = _cell_anchors(anchors, [w * float(s), h * float(s)], float(s), torch.float32, dev)
+            box_target[hit] = box2delta(xyxy[owner[hit]], cell[hit])
+            depth[hit] = classes[owner[hit]] + 1
+        cls_target = None
+        if want_cls_target:
+            cls_target = torch.zeros((a * h * w, num_classes + 1), dtype=torch.float32, device=dev)
+            if hit.numel():
+                label = classes[owner[hit]].long()
+                label[(label < 0) | (label >= num_classes)] = num_classes
+                cls_target[hit, label] = 1
+            cls_target = cls_target[:, :num_classes].view(a, h, w, num_classes).permute(0, 3, 1, 2).contiguous()
+        out.append((cls_target, box_target.view(a, h, w, 4).permute(0, 3, 1, 2).contiguous(), depth.view(a, 1, h, w)))
+    return out
+
+
+def atss_assign_levels(targets, sizes, strides, anchors_list, num_classes, topk=9, want_cls_target=True):
+    """ATSS target assignment (adaptive training sample selection, Zhang et al., CVPR 2020) for every image and pyramid level:
+    the alternative to the fixed-IoU rule of `snap_to_anchors*`, axis-aligned boxes only.  Per box and level the `topk` cells
+    whose centres are nearest to the box centre are its candidates, with all their anchors; an IoU of at least the mean + the
+    standard deviation of the box's candidates over all levels, and a cell centre inside the box, make a candidate positive; an
+    anchor positive for several boxes goes to the largest IoU.  The exact definition is in csrc/atss.hpp.
+    A small box may contain no cell centre and then gets no positive anchor at all: that is ATSS.
+
+    targets [B, N, 5] = (x, y, w, h, class), class < 0 rows are padding; sizes: per level (H, W) of the head tensors.
+    GPU tensors go to the HIP kernels; any other tensor takes the pure-torch branch, which follows the same definition.
+    -> lists (cls_targets [B, A, C, H, W] | Nones, box_targets [B, A, 4, H, W], depths [B, A, 1, H, W]); depth is class + 1
+    or 0 (there is no ignore band)."""
+    topk = int(topk)
+    if not 1 <= topk <= _C.ATSS_MAX_TOPK:
+        raise ValueError('atss_assign_levels: topk must be in 1..%d' % _C.ATSS_MAX_TOPK)
+    if len(sizes) > MAX_LEVELS_PER_CALL:
+        raise ValueError('atss_assign_levels: at most %d levels (the threshold spans all of them, so the call cannot be split)'
+                         % MAX_LEVELS_PER_CALL)
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    targets = targets.float()
+    if targets.is_cuda:
+        return _C.atss_assign_levels(targets.contiguous(), anchors_list, num_classes, sizes, [int(s) for s in strides], topk,
+                                     want_cls_target)
+    return _atss_assign_torch(targets, sizes, strides, anchors_list, num_classes, topk, want_cls_target)
+
+
+def _atss_assign_torch(targets, sizes, strides, anchors_list, num_classes, topk, want_cls_target):
+    """The pure-torch branch of atss_assign_levels (any device)."""
+    per_image = [_atss_image(t[t[:, -1] > -1], sizes, strides, anchors_list, num_classes, topk, want_cls_target) for t in targets]
+    cls_t, box_t, depth_t = [], [], []
+    for l, (h, w) in enumerate(sizes):
+        a = anchors_list[l].shape[0]
+        cls_t.append(torch.stack([img[l][0] for img in per_image]) if want_cls_target and per_image else
+                     (targets.new_zeros((0, a, num_classes, h, w)) if want_cls_target else None))
+        box_t.append(torch.stack([img[l][1] for img in per_image]) if per_image else targets.new_zeros((0, a, 4, h, w)))
+        depth_t.append(torch.stack([img[l][2] for img in per_image]) if per_image else targets.new_zeros((0, a, 1, h, w)))
+    return cls_t, box_t, depth_t
 
 
 def rotate_boxes(boxes, points=False):

@@ -19,6 +19,9 @@ What differs from the reference, and why:
     from the range, bilinear, on its own canvas, and its boxes with it; with `--device-augment` on the GPU, the same pixels.
   * `--soft-nms {linear,gaussian}` (infer; train: its validation passes) with `--soft-nms-sigma` / `--soft-nms-min-score` is new:
     Soft-NMS (odtk/box.py:soft_nms, one HIP launch) instead of the reference's hard suppression.  Never stored in a checkpoint.
+  * `--assigner {iou,atss}` (train) with `--atss-topk` is new: ATSS target assignment (odtk/box.py:atss_assign_levels, two HIP
+    launches) instead of the reference's fixed `--anchor-ious` rule; axis-aligned boxes only.  Never stored in a checkpoint: a
+    resumed run has to be given the flag again.
 """
 import argparse
 import os
@@ -97,6 +100,12 @@ TRAIN_FLAGS = [
     _flag('--rotated-bbox', bool, text='boxes are [x, y, w, h, theta]'),
     _flag('--anchor-ious', float, [0.4, 0.5], 'background / foreground overlap thresholds', nargs=2, metavar='value value'),
     _flag('--absolute-angle', bool, text='regress the absolute angle instead of -45..45 degrees'),
+    # not flags of the reference: absent from the namespace unless given (read with getattr)
+    _flag('--assigner', str, argparse.SUPPRESS, 'how ground truth becomes training targets: iou = the fixed --anchor-ious thresholds '
+          '(default), atss = adaptive training sample selection (not with --rotated-bbox).  Not stored in the checkpoint: give it '
+          'again when resuming', choices=['iou', 'atss']),
+    _flag('--atss-topk', int, argparse.SUPPRESS, 'nearest cells per box and pyramid level that ATSS considers, 1..16 (default 9; '
+          'needs --assigner atss)', metavar='num'),
 ]
 INFER_FLAGS = [
     _flag('--images', str, '.', 'image directory', metavar='path'),
@@ -140,6 +149,12 @@ def parse(args):
         parser.error('--soft-nms is not available with --rotated-bbox')
     if soft and 'soft_nms' not in soft:
         parser.error('--soft-nms-sigma / --soft-nms-min-score need --soft-nms {linear,gaussian}')
+    if hasattr(parsed, 'atss_topk') and getattr(parsed, 'assigner', 'iou') != 'atss':
+        parser.error('--atss-topk needs --assigner atss')
+    if hasattr(parsed, 'atss_topk') and not 1 <= parsed.atss_topk <= 16:
+        parser.error('--atss-topk must be in 1..16')
+    if getattr(parsed, 'assigner', 'iou') == 'atss' and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--assigner atss is not available with --rotated-bbox')
     return parsed
 
 
@@ -207,6 +222,10 @@ def worker(rank, args, world, spawned=False):
         model.soft_nms = soft_nms_options(args, model)
         if model.soft_nms is not None and args.rotated_bbox:
             raise RuntimeError('--soft-nms is not available for a model with rotated boxes')
+    if args.command == 'train':
+        model.assigner, model.atss_topk = getattr(args, 'assigner', 'iou'), getattr(args, 'atss_topk', 9)
+        if model.assigner == 'atss' and args.rotated_bbox:
+            raise RuntimeError('--assigner atss is not available for a model with rotated boxes')
     try:
         if args.command == 'train':
             return train.train(model, state, args.images, args.annotations, args.val_images or args.images,

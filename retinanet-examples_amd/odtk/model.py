@@ -84,6 +84,11 @@ class Model(nn.Module):
         # Soft-NMS instead of the reference's hard rule (odtk/box.py:soft_nms): None, or a dict with `method` ('linear' /
         # 'gaussian'), `sigma` and `min_score` (default: `threshold`).  A run-time option: never written into checkpoints
         self.soft_nms = None
+        # how ground truth becomes training targets: 'iou' (the reference's fixed thresholds, `anchor_ious`) or 'atss' (adaptive
+        # training sample selection over the `atss_topk` nearest cells per level, odtk/box.py:atss_assign_levels; axis-aligned
+        # boxes only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
+        self.assigner = 'iou'
+        self.atss_topk = 9
         self.exporting = False
         self.fused_postprocess = True
         self.fused_graph = True                             # eval on a GPU runs the BN-folded engine (odtk/fused.py)
@@ -286,10 +291,26 @@ class Model(nn.Module):
         """Focal + smooth-L1 losses summed over levels and normalised by the number of foreground
         anchors (reference model.py:186-210); `depth` is -1 ignore / 0 background / class+1."""
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
+        if self.assigner not in ('iou', 'atss'):
+            raise ValueError("Model.assigner must be 'iou' or 'atss', not {!r}".format(self.assigner))
+        atss = None
+        if self.assigner == 'atss':
+            if self.rotated_bbox:
+                raise ValueError("Model.assigner = 'atss' is not available for rotated boxes")
+            if len(cls_heads) > box_ops.MAX_LEVELS_PER_CALL:
+                raise ValueError("Model.assigner = 'atss' takes at most {} pyramid levels (its threshold spans all of them, so "
+                                 'the call cannot be split), not {}'.format(box_ops.MAX_LEVELS_PER_CALL, len(cls_heads)))
+            strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+            fused = self.fused_loss and cls_heads[0].is_cuda
+            atss = box_ops.atss_assign_levels(targets, [tuple(c.shape[-2:]) for c in cls_heads], strides,
+                                              [self.level_anchors(s) for s in strides], self.classes, self.atss_topk,
+                                              want_cls_target=not fused)
         if self.fused_loss and cls_heads[0].is_cuda:
             # targets of every level (ONE HIP launch for all of them; the class map is implied by depth and not even built), then focal
             # + smooth-L1 + masks + sums of ALL levels in one HIP pass -- and one more in backward (csrc/loss.hpp)
-            if len(cls_heads) <= box_ops.MAX_LEVELS_PER_CALL:
+            if atss is not None:
+                _, box_targets, depths = atss
+            elif len(cls_heads) <= box_ops.MAX_LEVELS_PER_CALL:
                 strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
                 assign = box_ops.snap_to_anchors_rotated_levels if self.rotated_bbox else box_ops.snap_to_anchors_levels
                 _, box_targets, depths = assign(
@@ -306,9 +327,12 @@ class Model(nn.Module):
                                                         self.cls_criterion.gamma, self.box_criterion.beta)
             foreground = fg.clamp(min=1).sum()              # per level, as the reference clamps (model.py:196)
             return cls_sums.sum() / foreground, box_sums.sum() / foreground
-        for cls_head, box_head in zip(cls_heads, box_heads):
+        for level, (cls_head, box_head) in enumerate(zip(cls_heads, box_heads)):
             stride = x.shape[-1] / cls_head.shape[-1]
-            cls_target, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:])
+            if atss is not None:
+                cls_target, box_target, depth = (per_level[level] for per_level in atss)
+            else:
+                cls_target, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:])
             foreground = foreground + (depth > 0).sum().float().clamp(min=1)
             cls_loss = self.cls_criterion(cls_head.view_as(cls_target).float(), cls_target)
             cls_total = cls_total + (cls_loss * (depth >= 0).expand_as(cls_target).float()).sum()
