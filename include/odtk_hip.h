@@ -66,8 +66,9 @@ extern "C" {
 
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
- * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t; -1 for any other value
- * (4 stays unassigned: tests/test_abi_host.py probes it as the first unknown id).  A binding compiled (or
+ * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t,
+ * 9 odtk_candidates_t; -1 for any other value (4 and 8 stay unassigned: tests/test_abi_host.py and tests/test_free_rotate.py probe
+ * them as unknown ids).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -220,6 +221,53 @@ int odtk_nms_sorted_runs(int batch_size, const void *const *inputs, void *const 
 int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs,
                   size_t count, int detections_per_im, float nms_thresh, int method, float sigma, float min_score,
                   uint32_t flags, void *workspace, size_t workspace_size, void *stream);
+
+/*
+ * odtk_box_vote -- box voting behind a suppression (Gidaris & Komodakis 2015; Detectron's bbox_vote) on axis-aligned boxes; no
+ * reference equivalent.  Per image the inputs are the SUPPRESSION'S INPUT LIST -- inputs[0..2] = scores [batch, count], boxes
+ * [batch, count, 4], classes [batch, count], float32, as odtk_nms takes them -- and kept, int32 [batch, detections_per_im]: the
+ * 4th output of odtk_nms_ex / odtk_soft_nms, the input position of each emitted detection or -1.  For slot r with p = kept[r]:
+ *   p < 0 or p >= count: out_boxes[r] is four zeros.  Otherwise the voters are
+ *     J = { j : scores[j] > 0, classes[j] == classes[p], (j == p or iou(p, j) >= vote_thresh) }
+ *   where iou is the float32 IoU of odtk_soft_nms, operation for operation: +1 pixel, torch max / min / clamp NaN rules,
+ *   inter / ((area_j + area_p) - inter).  A NaN IoU is not >= anything, so that candidate is no voter; the kept candidate always
+ *   votes for itself (given its score is > 0 and its class equals itself, which holds for every position a suppression emits).
+ *   out_boxes[r][k] = (float)( (SUM_J (double)scores[j] * (double)boxes[j][k]) / (SUM_J (double)scores[j]) ),  k = 0..3:
+ *   products and sums in double, the sums in ANY order (the library's order is fixed: the same bits on every run), one double
+ *   division, one rounding to float32.
+ * The weights are always the INPUT scores, also behind odtk_soft_nms, whose emitted score is the decayed one.  Scores, classes
+ * and the order of the detections are not touched: only out_boxes, float32 [batch, detections_per_im, 4], is written.  It may
+ * alias nothing the call reads; pass the suppression's INPUT boxes, not its output boxes.
+ * ODTK_ERR_INVALID: a null pointer, batch_size < 1, count outside 1..ODTK_MAX_NMS_COUNT_SCRATCH, detections_per_im outside
+ * 1..ODTK_MAX_NMS_DETECTIONS, vote_thresh not finite or outside (0, 1], any undefined flag bit.  ODTK_FLAG_ROTATED is
+ * ODTK_ERR_UNSUPPORTED.  No workspace; everything is checked on the host before anything touches HIP.  One launch (one wave per
+ * slot: csrc/box_vote.hpp), timed under ODTK_KERNEL_NMS.
+ */
+int odtk_box_vote(int batch_size, const void *const *inputs, const int32_t *kept, void *out_boxes, size_t count,
+                  int detections_per_im, float vote_thresh, uint32_t flags, void *stream);
+
+/*
+ * odtk_concat_candidates -- several candidate lists of the same batch as one, along the candidate axis (what torch.cat(.., 1)
+ * gives), un-mirroring the boxes of the lists that come from a horizontally flipped pass: the merge step of flip test-time
+ * augmentation.  parts is a HOST array of n_parts entries (they travel by value in the launch); outputs[0..2] = scores
+ * [batch, total], boxes [batch, total, 4], classes [batch, total] with total = the sum of the counts; part i occupies the
+ * positions behind those of parts 0..i-1, so on score ties a suppression prefers the earlier part.
+ * mirror_width = 0: the part is copied.  mirror_width = W > 0: the part was decoded from x.flip(-1) of a tensor W wide; for its
+ * entries with score > 0   x1' = (float)(W - 1) - x2,  x2' = (float)(W - 1) - x1   (one float32 subtraction each), y, score and
+ * class unchanged; entries with score <= 0 (or NaN) are copied unchanged.
+ * ODTK_ERR_INVALID: a null pointer, batch_size < 1, n_parts outside 1..8, a count of 0, a count or a total above
+ * ODTK_MAX_NMS_COUNT_SCRATCH, a negative mirror_width, any undefined flag bit.  ODTK_FLAG_ROTATED is ODTK_ERR_UNSUPPORTED.
+ * No workspace; everything is checked on the host.  One elementwise launch, timed under ODTK_KERNEL_NMS.
+ */
+typedef struct odtk_candidates {
+  const float *scores;      /* [batch, count]     */
+  const float *boxes;       /* [batch, count, 4]  */
+  const float *classes;     /* [batch, count]     */
+  uint32_t count;
+  int32_t mirror_width;     /* 0, or the width of the tensor whose flip this part was decoded from */
+} odtk_candidates_t;
+int odtk_concat_candidates(int batch_size, int n_parts, const odtk_candidates_t *parts, void *const *outputs, uint32_t flags,
+                           void *stream);
 
 /*
  * odtk_detect -- decode_levels + nms back to back on one stream (the whole post-processing of

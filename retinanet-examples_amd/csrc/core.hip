@@ -41,6 +41,7 @@ int odtk_abi_struct_size(int which) {
     case 5: return static_cast<int>(sizeof(odtk_image_t));
     case 6: return static_cast<int>(sizeof(odtk_augment_t));
     case 7: return static_cast<int>(sizeof(odtk_rotation_t));
+    case 9: return static_cast<int>(sizeof(odtk_candidates_t));
     default: return -1;
   }
 }

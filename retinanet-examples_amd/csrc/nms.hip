@@ -1,4 +1,4 @@
-// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
+// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS, box voting, candidate concatenation and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
 #include <cmath>
 #include <cstring>
 
@@ -6,6 +6,7 @@
 #include "iou.hpp"
 #include "nms.hpp"
 #include "soft_nms.hpp"
+#include "box_vote.hpp"
 
 namespace {
 
@@ -221,6 +222,78 @@ int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *output
   sa.min_score = min_score;
   return method == ODTK_SOFT_NMS_GAUSSIAN ? soft_nms_launch<true>(sa, batch_size, static_cast<hipStream_t>(stream))
                                           : soft_nms_launch<false>(sa, batch_size, static_cast<hipStream_t>(stream));
+}
+
+// everything is validated here, on the host, before anything touches the device
+int odtk_box_vote(int batch_size, const void *const *inputs, const int32_t *kept, void *out_boxes, size_t count,
+                  int detections_per_im, float vote_thresh, uint32_t flags, void *stream) {
+  if (batch_size <= 0 || count == 0 || count > ODTK_MAX_NMS_COUNT_SCRATCH || detections_per_im <= 0 ||
+      detections_per_im > ODTK_MAX_NMS_DETECTIONS)
+    return ODTK_ERR_INVALID;
+  if (!std::isfinite(vote_thresh) || !(vote_thresh > 0.0f) || !(vote_thresh <= 1.0f)) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (!inputs || !inputs[0] || !inputs[1] || !inputs[2] || !kept || !out_boxes) return ODTK_ERR_INVALID;
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  odtk::BoxVoteArgs va;
+  std::memset(&va, 0, sizeof va);
+  va.scores = static_cast<const float *>(inputs[0]);
+  va.boxes = static_cast<const float *>(inputs[1]);
+  va.classes = static_cast<const float *>(inputs[2]);
+  va.kept = kept;
+  va.out_boxes = static_cast<float *>(out_boxes);
+  va.count = static_cast<uint32_t>(count);
+  va.ndet = detections_per_im;
+  va.thresh = vote_thresh;
+  const unsigned groups = (static_cast<unsigned>(detections_per_im) + odtk::kVoteWaves - 1) / odtk::kVoteWaves;
+  const int per_launch = 65535;                                  // images per launch: the grid's y extent
+  for (int first = 0; first < batch_size; first += per_launch) {
+    const int n = batch_size - first < per_launch ? batch_size - first : per_launch;
+    odtk::BoxVoteArgs part = va;
+    part.scores += static_cast<size_t>(first) * count;
+    part.boxes += static_cast<size_t>(first) * count * 4;
+    part.classes += static_cast<size_t>(first) * count;
+    part.kept += static_cast<size_t>(first) * detections_per_im;
+    part.out_boxes += static_cast<size_t>(first) * detections_per_im * 4;
+    timed_launch(ODTK_KERNEL_NMS, odtk::box_vote_kernel, dim3(groups, static_cast<unsigned>(n)), dim3(odtk::kVoteThreads), 0,
+                 static_cast<hipStream_t>(stream), part);
+  }
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_concat_candidates(int batch_size, int n_parts, const odtk_candidates_t *parts, void *const *outputs, uint32_t flags,
+                           void *stream) {
+  if (batch_size <= 0 || n_parts < 1 || n_parts > odtk::kConcatMaxParts || !parts) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (!outputs || !outputs[0] || !outputs[1] || !outputs[2]) return ODTK_ERR_INVALID;
+  odtk::ConcatArgs ca;
+  std::memset(&ca, 0, sizeof ca);
+  size_t total = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    const odtk_candidates_t &c = parts[i];
+    if (!c.scores || !c.boxes || !c.classes || c.count == 0 || c.count > ODTK_MAX_NMS_COUNT_SCRATCH || c.mirror_width < 0)
+      return ODTK_ERR_INVALID;
+    ca.scores[i] = c.scores; ca.boxes[i] = c.boxes; ca.classes[i] = c.classes;
+    ca.offset[i] = static_cast<uint32_t>(total);
+    ca.mirror[i] = static_cast<float>(c.mirror_width - 1);
+    if (c.mirror_width > 0) ca.mirrored |= 1u << i;
+    total += c.count;
+    if (total > ODTK_MAX_NMS_COUNT_SCRATCH) return ODTK_ERR_INVALID;
+  }
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  for (int i = n_parts; i <= odtk::kConcatMaxParts; ++i) ca.offset[i] = static_cast<uint32_t>(total);
+  ca.total = static_cast<uint32_t>(total);
+  ca.n_parts = n_parts;
+  ca.out_scores = static_cast<float *>(outputs[0]);
+  ca.out_boxes = static_cast<float *>(outputs[1]);
+  ca.out_classes = static_cast<float *>(outputs[2]);
+  ca.elements = static_cast<uint64_t>(batch_size) * total;
+  uint64_t blocks = (ca.elements + odtk::kConcatThreads - 1) / odtk::kConcatThreads;
+  if (blocks > 256 * 16) blocks = 256 * 16;                  // grid-stride beyond 16 workgroups per CU
+  timed_launch(ODTK_KERNEL_NMS, odtk::concat_candidates_kernel, dim3(static_cast<unsigned>(blocks)), dim3(odtk::kConcatThreads), 0,
+               static_cast<hipStream_t>(stream), ca);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
 }
 
 int odtk_iou(const void *const *inputs, void *const *outputs, int num_boxes, int num_anchors, void *stream) {

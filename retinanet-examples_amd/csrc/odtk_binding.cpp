@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue) and `soft_nms`.  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote` and `concat_candidates`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -142,6 +142,58 @@ std::vector<torch::Tensor> soft_nms(torch::Tensor scores, torch::Tensor boxes, t
   return result;
 }
 
+// box voting behind a suppression (odtk_box_vote: no reference equivalent), the signature of odtk/_C.py:box_vote
+torch::Tensor box_vote(torch::Tensor scores, torch::Tensor boxes, torch::Tensor classes, torch::Tensor kept, float vote_thresh) {
+  require_gpu_contiguous(scores, "scores");
+  require_gpu_contiguous(boxes, "boxes");
+  require_gpu_contiguous(classes, "classes");
+  TORCH_CHECK(kept.is_cuda() && kept.is_contiguous() && kept.scalar_type() == torch::kInt32, "kept must be a contiguous int32 CUDA tensor");
+  TORCH_CHECK(scores.dim() == 2 && boxes.dim() == 3 && boxes.size(2) == 4 && boxes.size(0) == scores.size(0) &&
+              boxes.size(1) == scores.size(1) && classes.sizes() == scores.sizes() && kept.dim() == 2 && kept.size(0) == scores.size(0),
+              "box_vote: inconsistent shapes");
+  const int64_t batch = scores.size(0), count = scores.size(1), ndet = kept.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+  auto out = torch::empty({batch, ndet, 4}, scores.options());
+  const void *in[3] = {scores.data_ptr(), boxes.data_ptr(), classes.data_ptr()};
+  void *stream = current_stream(scores);
+  {
+    pybind11::gil_scoped_release nogil;
+    checked(odtk_box_vote(static_cast<int>(batch), in, static_cast<const int32_t *>(kept.data_ptr()), out.data_ptr(),
+                          static_cast<size_t>(count), static_cast<int>(ndet), vote_thresh, 0u, stream), "box_vote");
+  }
+  return out;
+}
+
+// candidate lists as one, mirrored passes un-mirrored (odtk_concat_candidates), the signature of odtk/_C.py:concat_candidates
+std::vector<torch::Tensor> concat_candidates(std::vector<std::vector<torch::Tensor>> parts, std::vector<int> mirror_widths) {
+  TORCH_CHECK(!parts.empty() && parts.size() == mirror_widths.size(), "concat_candidates: one mirror width per part");
+  std::vector<odtk_candidates_t> table(parts.size());
+  int64_t total = 0;
+  const int64_t batch = parts[0].at(0).size(0);
+  for (size_t i = 0; i < parts.size(); ++i) {
+    TORCH_CHECK(parts[i].size() == 3, "concat_candidates: a part is (scores, boxes, classes)");
+    const torch::Tensor &s = parts[i][0], &b = parts[i][1], &c = parts[i][2];
+    require_gpu_contiguous(s, "scores");
+    require_gpu_contiguous(b, "boxes");
+    require_gpu_contiguous(c, "classes");
+    TORCH_CHECK(s.dim() == 2 && s.size(0) == batch && b.dim() == 3 && b.size(0) == batch && b.size(1) == s.size(1) && b.size(2) == 4 &&
+                c.sizes() == s.sizes() && s.device() == parts[0][0].device(), "concat_candidates: inconsistent shapes");
+    table[i] = {static_cast<const float *>(s.data_ptr()), static_cast<const float *>(b.data_ptr()), static_cast<const float *>(c.data_ptr()),
+                static_cast<uint32_t>(s.size(1)), mirror_widths[i]};
+    total += s.size(1);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(parts[0][0].device());
+  auto opt = parts[0][0].options();
+  std::vector<torch::Tensor> result = {torch::empty({batch, total}, opt), torch::empty({batch, total, 4}, opt), torch::empty({batch, total}, opt)};
+  void *out[3] = {result[0].data_ptr(), result[1].data_ptr(), result[2].data_ptr()};
+  void *stream = current_stream(parts[0][0]);
+  {
+    pybind11::gil_scoped_release nogil;
+    checked(odtk_concat_candidates(static_cast<int>(batch), static_cast<int>(table.size()), table.data(), out, 0u, stream), "concat_candidates");
+  }
+  return result;
+}
+
 std::vector<torch::Tensor> iou(torch::Tensor boxes, torch::Tensor anchors) {
   require_gpu_contiguous(boxes, "boxes");
   require_gpu_contiguous(anchors, "anchors");
@@ -215,7 +267,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // have been compiled against the same struct layouts (a stale module would pass level arrays of the wrong stride)
   if (odtk_abi_struct_size(0) != static_cast<int>(sizeof(odtk_level_t)) ||
       odtk_abi_struct_size(1) != static_cast<int>(sizeof(odtk_snap_level_t)) ||
-      odtk_abi_struct_size(2) != static_cast<int>(sizeof(odtk_snap_rot_level_t)))
+      odtk_abi_struct_size(2) != static_cast<int>(sizeof(odtk_snap_rot_level_t)) ||
+      odtk_abi_struct_size(9) != static_cast<int>(sizeof(odtk_candidates_t)))
     throw py::import_error("odtk._C_ext was compiled against another revision of include/odtk_hip.h than libodtk_hip.so "
                            "(struct sizes differ): rebuild it -- make -C retinanet-examples_amd/csrc");
   py::class_<Engine>(m, "Engine")
@@ -231,6 +284,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rotated") = false);
   m.def("soft_nms", &soft_nms, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("nms_thresh"),
         py::arg("detections_per_im"), py::arg("method"), py::arg("sigma"), py::arg("min_score"), py::arg("return_indices") = false);
+  m.def("box_vote", &box_vote, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("kept"), py::arg("vote_thresh"));
+  m.def("concat_candidates", &concat_candidates, py::arg("parts"), py::arg("mirror_widths"));
   m.def("iou", &iou, py::arg("boxes"), py::arg("anchors"));
   m.def("detect", &detect, py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors"), py::arg("strides"), py::arg("score_thresh"),
         py::arg("top_n"), py::arg("nms_thresh"), py::arg("detections_per_im"), py::arg("rotated") = false, py::arg("logits") = false);

@@ -10,7 +10,8 @@ conventions, so `from ._C import decode, nms, iou` in a box.py keeps working:
     Engine                                                                        -> placeholder (TensorRT dropped)
 
 plus the MI355X-first batched forms (`decode_levels`, `detect`) that cover all pyramid levels of
-the whole batch in one enqueue, and `soft_nms` (linear / Gaussian Soft-NMS: no reference equivalent).
+the whole batch in one enqueue, `soft_nms` (linear / Gaussian Soft-NMS), `box_vote` (box voting behind a suppression) and
+`concat_candidates` (the merge of flip test-time augmentation): no reference equivalents.
 
 There is NO CPU fallback: tensors must live on the GPU and the shared library must be present
 (build it with `python __graft_entry__.py` or `make -C retinanet-examples_amd/csrc`); anything
@@ -29,6 +30,7 @@ OK, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
 FLAG_ROTATED, FLAG_LOGITS, FLAG_ROTATED_NMS_FIXED_ANGLE = 1, 2, 4
 MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32, 16384, 7680, 1 << 22
+MAX_CONCAT_PARTS = 8
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 ATSS_MAX_TOPK = 16
 
@@ -84,6 +86,11 @@ class Augment(ctypes.Structure):
 class Rotation(ctypes.Structure):
     """odtk_rotation_t"""
     _fields_ = [('matrix', ctypes.c_double * 6), ('enabled', ctypes.c_int32), ('flip', ctypes.c_int32)]
+
+
+class Candidates(ctypes.Structure):
+    """odtk_candidates_t"""
+    _fields_ = [('scores', _vp), ('boxes', _vp), ('classes', _vp), ('count', ctypes.c_uint32), ('mirror_width', ctypes.c_int32)]
 
 
 _SIGNATURES = {
@@ -152,6 +159,8 @@ _SIGNATURES = {
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_soft_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _vp, _sz, _vp]),
+    'odtk_box_vote': (ctypes.c_int, [ctypes.c_int, _vpp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, _vp]),
+    'odtk_concat_candidates': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Candidates), _vpp, ctypes.c_uint32, _vp]),
     'odtk_gemm_init': (ctypes.c_int, [ctypes.c_char_p]),
     'odtk_gemm_plan_export': (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
     'odtk_gemm_plan_import': (ctypes.c_int, [ctypes.c_char_p]),
@@ -194,7 +203,8 @@ def library():
             fn.restype = res
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
-        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation)):
+        for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation),
+                              (9, Candidates)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -351,6 +361,47 @@ def soft_nms(scores, boxes, classes, nms_thresh, detections_per_im, method, sigm
     out = _detections(batch, detections_per_im, 4, scores.device, return_indices)
     _enqueue(lib.odtk_soft_nms, 'soft_nms', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
              int(detections_per_im), float(nms_thresh), int(method), float(sigma), float(min_score), 0)
+    return out
+
+
+def box_vote(scores, boxes, classes, kept, vote_thresh):
+    """Box voting (include/odtk_hip.h: odtk_box_vote; no reference equivalent): one launch.  scores / boxes / classes are the
+    suppression's INPUT list, kept [B, D] int32 its position output (`nms(.., return_indices=True)[3]`) -> boxes [B, D, 4]."""
+    _check_input(scores, 'scores')
+    _check_input(boxes, 'boxes')
+    _check_input(classes, 'classes')
+    if not isinstance(kept, torch.Tensor) or not kept.is_cuda or not kept.is_contiguous() or kept.dtype != torch.int32:
+        raise RuntimeError('kept must be a contiguous int32 CUDA tensor')
+    lib = library()
+    batch, count = scores.shape
+    if boxes.shape != (batch, count, 4) or classes.shape != (batch, count) or kept.dim() != 2 or kept.shape[0] != batch:
+        raise RuntimeError('box_vote: inconsistent shapes')
+    out = torch.empty((batch, kept.shape[1], 4), dtype=torch.float32, device=scores.device)
+    _launch(lib.odtk_box_vote, 'box_vote', scores.device, batch, _ptrs([scores, boxes, classes]), kept.data_ptr(), out.data_ptr(),
+            count, int(kept.shape[1]), float(vote_thresh), 0)
+    return out
+
+
+def concat_candidates(parts, mirror_widths):
+    """Candidate lists as one along the candidate axis, the boxes of mirrored passes mapped back (include/odtk_hip.h:
+    odtk_concat_candidates): one launch.  parts: up to 8 (scores [B, n_i], boxes [B, n_i, 4], classes [B, n_i]); mirror_widths:
+    per part 0, or the width of the tensor whose horizontal flip the part was decoded from."""
+    lib = library()
+    if not parts or len(parts) != len(mirror_widths):
+        raise RuntimeError('concat_candidates: one mirror width per part')
+    table = (Candidates * len(parts))()
+    batch, dev, total = parts[0][0].shape[0], parts[0][0].device, 0
+    for entry, (s, b, c), width in zip(table, parts, mirror_widths):
+        _check_input(s, 'scores')
+        _check_input(b, 'boxes')
+        _check_input(c, 'classes')
+        if s.dim() != 2 or s.shape[0] != batch or b.shape != (batch, s.shape[1], 4) or c.shape != s.shape or s.device != dev:
+            raise RuntimeError('concat_candidates: inconsistent shapes')
+        entry.scores, entry.boxes, entry.classes = s.data_ptr(), b.data_ptr(), c.data_ptr()
+        entry.count, entry.mirror_width = s.shape[1], int(width)
+        total += s.shape[1]
+    out = _detections(batch, total, 4, dev)
+    _launch(lib.odtk_concat_candidates, 'concat_candidates', dev, batch, len(parts), table, _ptrs(out), 0)
     return out
 
 

@@ -435,16 +435,18 @@ def _decode_cpu(cls_heads, box_heads, stride, threshold, top_n, anchors):
     return scores_out, boxes_out, classes_out
 
 
-def _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections):
+def _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, return_indices=False):
     """CPU branch of `nms` (reference box.py:319-367): greedy, class-aware, +1 pixel IoU.  The reference
     compacts its arrays after every kept box; here one `alive` mask over the score-sorted candidates does
     the same bookkeeping: the i-th kept box is the i-th alive entry, and it retires every alive entry that
-    fails the reference's survivor test `score > s_i  or  IoU <= nms  or  class != c_i`."""
+    fails the reference's survivor test `score > s_i  or  IoU <= nms  or  class != c_i`.
+    return_indices: a fourth value, int32 [B, D], the input position of every kept box (-1: unused slot)."""
     all_scores, all_boxes, all_classes = all_scores.float(), all_boxes.float(), all_classes.float()
     batch = all_scores.shape[0]
     scores_out = all_scores.new_zeros((batch, ndetections))
     boxes_out = all_scores.new_zeros((batch, ndetections, 4))
     classes_out = all_scores.new_zeros((batch, ndetections))
+    index_out = torch.full((batch, ndetections), -1, dtype=torch.int32)
     for image in range(batch):
         positive = torch.nonzero(all_scores[image] > 0).view(-1)
         if positive.numel() == 0:
@@ -470,6 +472,9 @@ def _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections):
         scores_out[image, :kept] = scores[winners]
         boxes_out[image, :kept] = boxes[winners]
         classes_out[image, :kept] = classes[winners]
+        index_out[image, :kept] = order[winners].to(torch.int32)
+    if return_indices:
+        return scores_out, boxes_out, classes_out, index_out
     return scores_out, boxes_out, classes_out
 
 
@@ -537,6 +542,7 @@ def nms(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100):
 
 
 SOFT_NMS_METHODS = {'linear': _C.SOFT_NMS_LINEAR, 'gaussian': _C.SOFT_NMS_GAUSSIAN}
+MAX_SOFT_NMS_COUNT = _C.MAX_NMS_COUNT              # candidates per image odtk_soft_nms takes
 
 
 def _soft_nms_options(method, sigma, min_score):
@@ -556,6 +562,105 @@ def soft_nms(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, metho
         return _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score)[:3]
     return _C.soft_nms(all_scores.float().contiguous(), all_boxes.float().contiguous(), all_classes.float().contiguous(),
                        nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score)
+
+
+def _vote_option(vote):
+    vote = float(vote)
+    if not (math.isfinite(vote) and 0 < vote <= 1):
+        raise ValueError('box voting: the threshold must be finite and in (0, 1], not %r' % (vote,))
+    return vote
+
+
+def _box_vote_cpu(all_scores, all_boxes, all_classes, kept, vote_thresh):
+    """Pure-torch branch of `box_vote`: `_soft_nms_cpu`'s float32 IoU in its operation order, the weighted mean in float64."""
+    all_scores, all_boxes, all_classes = all_scores.float(), all_boxes.float(), all_classes.float()
+    batch, count = all_scores.shape
+    out = all_scores.new_zeros((batch, kept.shape[1], 4))
+    position = torch.arange(count, device=all_scores.device)
+    for image in range(batch):
+        scores, boxes, classes = all_scores[image], all_boxes[image], all_classes[image]
+        area = (boxes[:, 2] - boxes[:, 0] + 1) * (boxes[:, 3] - boxes[:, 1] + 1)
+        for slot, p in enumerate(kept[image].tolist()):
+            if p < 0 or p >= count:
+                continue
+            lo = torch.max(boxes[:, :2], boxes[p, :2])
+            hi = torch.min(boxes[:, 2:], boxes[p, 2:])
+            inter = torch.prod((hi - lo + 1).clamp(0), 1)
+            iou = inter / (area + area[p] - inter)
+            voters = (scores > 0) & (classes == classes[p]) & ((iou >= vote_thresh) | (position == p))
+            w = scores[voters].double()
+            out[image, slot] = ((w[:, None] * boxes[voters].double()).sum(0) / w.sum()).float()
+    return out
+
+
+def box_vote(all_scores, all_boxes, all_classes, kept, vote_thresh=0.65):
+    """Box voting behind a suppression (Gidaris & Komodakis 2015; no reference equivalent; definition in include/odtk_hip.h:
+    odtk_box_vote): every kept box becomes the score-weighted mean of the candidates of its class that overlap it by at least
+    `vote_thresh` (+1 pixel IoU), itself included.  all_scores / all_boxes / all_classes: the suppression's INPUT list (the weights
+    are its scores, also behind Soft-NMS); kept [B, D] int32: the input position of each emitted detection or -1, as
+    `_C.nms(.., return_indices=True)` and `_C.soft_nms(.., return_indices=True)` return it -> boxes [B, D, 4] (unused slots: zeros).
+    GPU tensors go to the HIP kernel (one launch); any other tensor takes the pure-torch float64 branch."""
+    vote_thresh = _vote_option(vote_thresh)
+    if not all_scores.is_cuda:
+        return _box_vote_cpu(all_scores, all_boxes, all_classes, kept, vote_thresh)
+    return _C.box_vote(all_scores.float().contiguous(), all_boxes.float().contiguous(), all_classes.float().contiguous(),
+                       kept.to(torch.int32).contiguous(), vote_thresh)
+
+
+def concat_candidates(parts, mirror_widths):
+    """Several candidate lists (scores [B, n_i], boxes [B, n_i, 4], classes [B, n_i]) as one along the candidate axis, the merge of
+    flip test-time augmentation (include/odtk_hip.h: odtk_concat_candidates).  mirror_widths: per part 0, or the width W of the
+    tensor whose horizontal flip the part was decoded from: its boxes with a score > 0 are mapped back, x1' = (W - 1) - x2 and
+    x2' = (W - 1) - x1 in float32.  GPU tensors: one HIP launch; any other tensor: the same in torch."""
+    parts = [tuple(t.float() for t in part) for part in parts]
+    widths = [int(w) for w in mirror_widths]
+    if not 1 <= len(parts) <= _C.MAX_CONCAT_PARTS or len(widths) != len(parts) or min(widths) < 0:
+        raise ValueError('concat_candidates: 1..%d parts, one non-negative mirror width each' % _C.MAX_CONCAT_PARTS)
+    if parts[0][0].is_cuda:
+        return _C.concat_candidates([tuple(t.contiguous() for t in part) for part in parts], widths)
+    unmirrored = []
+    for (scores, boxes, classes), width in zip(parts, widths):
+        if width > 0:
+            edge = torch.tensor(width - 1, dtype=torch.float32)
+            positive = scores > 0
+            x1, x2 = torch.where(positive, edge - boxes[..., 2], boxes[..., 0]), torch.where(positive, edge - boxes[..., 0], boxes[..., 2])
+            boxes = torch.stack([x1, boxes[..., 1], x2, boxes[..., 3]], -1)
+        unmirrored.append((scores, boxes, classes))
+    return [torch.cat(t, 1) for t in zip(*unmirrored)]
+
+
+def flip_batch(x):
+    """x.flip(-1) in x's memory format (the engine's plans and graphs are keyed by it)."""
+    flipped = x.flip(-1)
+    if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+        flipped = flipped.contiguous(memory_format=torch.channels_last)
+    return flipped
+
+
+def suppress(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, soft_nms=None, vote=None, threshold=0.05):
+    """The tail of the post-processing on ONE candidate list of axis-aligned boxes: hard NMS, or Soft-NMS when `soft_nms` is a dict
+    (`method`, `sigma`, `min_score`: default `threshold`), then box voting at IoU `vote` when that is not None.
+    -> (scores [B, D], boxes [B, D, 4], classes [B, D]).  GPU tensors: one launch for the suppression and one for the vote."""
+    want = vote is not None
+    if want:
+        vote = _vote_option(vote)
+    cuda = all_scores.is_cuda
+    if cuda:
+        all_scores, all_boxes, all_classes = (t.float().contiguous() for t in (all_scores, all_boxes, all_classes))
+    if soft_nms is not None:
+        method, sigma, min_score = _soft_nms_options(soft_nms.get('method', 'linear'), soft_nms.get('sigma', 0.5),
+                                                     soft_nms.get('min_score', threshold))
+        if cuda:
+            out = _C.soft_nms(all_scores, all_boxes, all_classes, nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score, want)
+        else:
+            out = _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score)
+    elif cuda:
+        out = _C.nms(all_scores, all_boxes, all_classes, nms, ndetections, False, want)
+    else:
+        out = _nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, want)
+    if not want:
+        return tuple(out[:3])
+    return out[0], box_vote(all_scores, all_boxes, all_classes, out[3], vote), out[2]
 
 
 def nms_rotated(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100):
@@ -595,34 +700,54 @@ def decode_levels(cls_heads, box_heads, strides, threshold, top_n, anchors_per_s
                             rotated, logits=logits)
 
 
+def _decode_groups(pairs, anchors, strides, threshold, top_n, logits, cls_bias, box_bias, cls_thresholds):
+    """decode_levels of axis-aligned (cls, box) pairs in groups of MAX_LEVELS levels (the level table of one call) -> one
+    candidate list."""
+    def bias_of(bias, lo, hi):
+        return bias[lo:hi] if isinstance(bias, (list, tuple)) else bias
+    parts = []
+    for lo in range(0, len(pairs), _C.MAX_LEVELS):
+        hi = min(lo + _C.MAX_LEVELS, len(pairs))
+        parts.append(_C.decode_levels([p[0] for p in pairs[lo:hi]], [p[1] for p in pairs[lo:hi]], anchors[lo:hi],
+                                      strides[lo:hi], threshold, top_n, False, logits=logits,
+                                      cls_bias=bias_of(cls_bias, lo, hi), box_bias=bias_of(box_bias, lo, hi),
+                                      cls_thresholds=cls_thresholds if len(pairs) <= _C.MAX_LEVELS else None))
+    return parts[0] if len(parts) == 1 else [torch.cat(t, 1) for t in zip(*parts)]
+
+
+def candidates(cls_heads, box_heads, strides, anchors_per_stride, threshold=0.05, top_n=1000, logits=False, cls_bias=None,
+               box_bias=None, cls_thresholds=None):
+    """The first half of `detect` on its own, axis-aligned boxes: (scores [B, L * top_n], boxes [B, L * top_n, 4], classes) of all
+    levels, reading the head tensors in place (GPU only) -- what the passes of test-time augmentation hand to
+    `concat_candidates` and `suppress`."""
+    for t in cls_heads:
+        _require_gpu(t, 'candidates')
+    pairs = [_pair(c, b) for c, b in zip(cls_heads, box_heads)]
+    return _decode_groups(pairs, [anchors_per_stride[s] for s in strides], strides, threshold, top_n, logits, cls_bias, box_bias,
+                          cls_thresholds)
+
+
 def detect(cls_heads, box_heads, strides, anchors_per_stride, threshold=0.05, top_n=1000, nms=0.5,
-           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None, soft_nms=None):
+           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None, soft_nms=None, vote=None):
     """sigmoid (logits=True) + decode of all levels + nms: the whole inference post-processing of the
     reference (model.py:140-165) in one enqueue of three launches (rotated: five to seven), reading the head tensors in place.
     cls_bias / box_bias: the heads' last-conv biases, added inside the kernels (see _C.decode_levels); cls_thresholds: the
     prefilter's threshold table for that cls_bias, made once by _C.prefilter_thresholds (optional).
     soft_nms: None, or a dict with `method` ('linear' / 'gaussian'), `sigma` and `min_score` -- the suppression is then Soft-NMS
-    (`soft_nms` above) on decode_levels' candidates: three launches as well."""
+    (`soft_nms` above) on decode_levels' candidates: three launches as well.
+    vote: None, or the IoU threshold of box voting (`box_vote` above) behind the suppression, hard or soft: decode_levels, the
+    general NMS with its position output, the vote -- four launches."""
     if soft_nms is not None and rotated:
         raise ValueError('detect: Soft-NMS is not available for rotated boxes')
+    if vote is not None and rotated:
+        raise ValueError('detect: box voting is not available for rotated boxes')
     anchors = [anchors_per_stride[s][0] if rotated else anchors_per_stride[s] for s in strides]
     for t in cls_heads:
         _require_gpu(t, 'detect')
     pairs = [_pair(c, b) for c, b in zip(cls_heads, box_heads)]
-    if soft_nms is not None:
-        method, sigma, min_score = _soft_nms_options(soft_nms.get('method', 'linear'), soft_nms.get('sigma', 0.5),
-                                                     soft_nms.get('min_score', threshold))
-        def bias_of(bias, lo, hi):
-            return bias[lo:hi] if isinstance(bias, (list, tuple)) else bias
-        parts = []
-        for lo in range(0, len(pairs), _C.MAX_LEVELS):
-            hi = min(lo + _C.MAX_LEVELS, len(pairs))
-            parts.append(_C.decode_levels([p[0] for p in pairs[lo:hi]], [p[1] for p in pairs[lo:hi]], anchors[lo:hi],
-                                          strides[lo:hi], threshold, top_n, False, logits=logits,
-                                          cls_bias=bias_of(cls_bias, lo, hi), box_bias=bias_of(box_bias, lo, hi),
-                                          cls_thresholds=cls_thresholds if len(pairs) <= _C.MAX_LEVELS else None))
-        candidates = parts[0] if len(parts) == 1 else [torch.cat(t, 1) for t in zip(*parts)]
-        return _C.soft_nms(*candidates, nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score)
+    if soft_nms is not None or vote is not None:
+        return suppress(*_decode_groups(pairs, anchors, strides, threshold, top_n, logits, cls_bias, box_bias, cls_thresholds),
+                        nms, ndetections, soft_nms=soft_nms, vote=vote, threshold=threshold)
     if len(pairs) > _C.MAX_LEVELS:
         # a model with several backbones has 5 levels per backbone (reference model.py:138): the level table of one call
         # holds MAX_LEVELS, so decode in groups and hand the concatenation to nms (its candidate count is not capped)

@@ -579,7 +579,10 @@ class FusedRetinaNet(nn.Module):
         bias = self.cls_head[-1].bias                                    # its state is baked in too: the prefilter's threshold table
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
                m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, bias.data_ptr(), bias._version,
-               tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None)     # (the suppression rule is baked in as well)
+               tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None,     # (the suppression rule is baked in as well,
+               getattr(m, 'box_voting', None))                                                               #  and so is box voting)
+        if getattr(m, 'tta', None) is not None:
+            raise RuntimeError('FusedRetinaNet.replay is not available with Model.tta (two passes of the engine)')
         entry = self._graphs.get(key)
         if entry is None:
             static_x = torch.empty_like(x)
@@ -709,6 +712,18 @@ class FusedRetinaNet(nn.Module):
     @torch.no_grad()
     def forward(self, x):
         m = self.model[0]
+        m.check_inference_options()
+        if getattr(m, 'tta', None) is None:
+            return self._postprocess(x, False)
+        # test-time augmentation by the horizontal flip: the first pass is decoded BEFORE the second runs (the head tensors may
+        # be views of a cached arena that the next pass overwrites), then one suppression over both candidate lists
+        first = self._postprocess(x, True)
+        second = self._postprocess(box_ops.flip_batch(x), True)
+        return m.suppress_tta(first, second, x.shape[-1])
+
+    def _postprocess(self, x, candidates_only):
+        """One pass of the engine and its decode: the detections, or (candidates_only) decode_levels' candidate list."""
+        m = self.model[0]
         self.plan(x)
         fold = self.dtype in (torch.bfloat16, torch.float16) and self.cls_head[-1].bias.numel() % 8 == 0
         if fold:
@@ -734,6 +749,9 @@ class FusedRetinaNet(nn.Module):
                 for i, t in enumerate(heads):
                     if not bool(torch.isfinite(t).all()):
                         raise FloatingPointError('FusedRetinaNet: non-finite values in the %s head tensor of level %d' % (name, i))
+        if candidates_only:
+            return box_ops.candidates(cls_heads, box_heads, strides, m.anchors, m.threshold, m.top_n, logits=True, cls_bias=cls_bias,
+                                      box_bias=box_bias, cls_thresholds=table)
         return box_ops.detect(cls_heads, box_heads, strides, m.anchors, m.threshold, m.top_n, m.nms, m.detections,
                               m.rotated_bbox, logits=True, cls_bias=cls_bias, box_bias=box_bias, cls_thresholds=table,
-                              soft_nms=getattr(m, 'soft_nms', None))
+                              soft_nms=getattr(m, 'soft_nms', None), vote=getattr(m, 'box_voting', None))

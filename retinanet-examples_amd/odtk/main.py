@@ -22,6 +22,10 @@ What differs from the reference, and why:
   * `--assigner {iou,atss}` (train) with `--atss-topk` is new: ATSS target assignment (odtk/box.py:atss_assign_levels, two HIP
     launches) instead of the reference's fixed `--anchor-ious` rule; axis-aligned boxes only.  Never stored in a checkpoint: a
     resumed run has to be given the flag again.
+  * `--box-voting value` and `--tta flip` (infer; train: its validation passes) are new: box voting behind the suppression
+    (odtk/box.py:box_vote, one HIP launch: every kept box becomes the score-weighted mean of its class's candidates that overlap it
+    by at least `value`) and test-time augmentation by the horizontal flip (the network also runs on the mirrored batch, one
+    suppression over both candidate lists).  Axis-aligned boxes only; never stored in a checkpoint.
 """
 import argparse
 import os
@@ -61,7 +65,12 @@ _COMMON = [_flag('--with-apex', bool, text=_DROPPED), _flag('--with-dali', bool,
                  'score (train: in the validation passes; not with --rotated-bbox)', choices=['linear', 'gaussian']),
            _flag('--soft-nms-sigma', float, argparse.SUPPRESS, 'width of the gaussian decay (default 0.5)', metavar='value'),
            _flag('--soft-nms-min-score', float, argparse.SUPPRESS, 'decayed scores below this are dropped (default: the '
-                 "model's score threshold)", metavar='value')]
+                 "model's score threshold)", metavar='value'),
+           _flag('--box-voting', float, argparse.SUPPRESS, 'box voting behind the suppression: every kept box becomes the score-weighted '
+                 'mean of the candidates of its class that overlap it by at least this IoU, in (0, 1] (0.65 is customary; not with '
+                 '--rotated-bbox)', metavar='value'),
+           _flag('--tta', str, argparse.SUPPRESS, 'test-time augmentation: flip = the network also runs on the mirrored batch and one '
+                 'suppression sees both candidate lists (about two forwards per batch; not with --rotated-bbox)', choices=['flip'])]
 
 # same names, types and defaults as the reference's parser (main.py:15-118)
 TRAIN_FLAGS = [
@@ -149,6 +158,11 @@ def parse(args):
         parser.error('--soft-nms is not available with --rotated-bbox')
     if soft and 'soft_nms' not in soft:
         parser.error('--soft-nms-sigma / --soft-nms-min-score need --soft-nms {linear,gaussian}')
+    for flag in ('box_voting', 'tta'):
+        if hasattr(parsed, flag) and getattr(parsed, 'rotated_bbox', False):
+            parser.error('--%s is not available with --rotated-bbox' % flag.replace('_', '-'))
+    if hasattr(parsed, 'box_voting') and not 0 < parsed.box_voting <= 1:          # (a NaN fails both comparisons)
+        parser.error('--box-voting must be in (0, 1]')
     if hasattr(parsed, 'atss_topk') and getattr(parsed, 'assigner', 'iou') != 'atss':
         parser.error('--atss-topk needs --assigner atss')
     if hasattr(parsed, 'atss_topk') and not 1 <= parsed.atss_topk <= 16:
@@ -222,6 +236,10 @@ def worker(rank, args, world, spawned=False):
         model.soft_nms = soft_nms_options(args, model)
         if model.soft_nms is not None and args.rotated_bbox:
             raise RuntimeError('--soft-nms is not available for a model with rotated boxes')
+        model.box_voting, model.tta = getattr(args, 'box_voting', None), getattr(args, 'tta', None)
+        for flag, value in (('--box-voting', model.box_voting), ('--tta', model.tta)):
+            if value is not None and args.rotated_bbox:
+                raise RuntimeError('%s is not available for a model with rotated boxes' % flag)
     if args.command == 'train':
         model.assigner, model.atss_topk = getattr(args, 'assigner', 'iou'), getattr(args, 'atss_topk', 9)
         if model.assigner == 'atss' and args.rotated_bbox:

@@ -84,6 +84,11 @@ class Model(nn.Module):
         # Soft-NMS instead of the reference's hard rule (odtk/box.py:soft_nms): None, or a dict with `method` ('linear' /
         # 'gaussian'), `sigma` and `min_score` (default: `threshold`).  A run-time option: never written into checkpoints
         self.soft_nms = None
+        # two more run-time options of inference, like `soft_nms` never constructor arguments and never written into checkpoints:
+        # box voting behind the suppression (odtk/box.py:box_vote) -- None, or its IoU threshold in (0, 1] -- and test-time
+        # augmentation -- None, or 'flip': the network also runs on the mirrored batch and one suppression sees both candidate lists
+        self.box_voting = None
+        self.tta = None
         # how ground truth becomes training targets: 'iou' (the reference's fixed thresholds, `anchor_ious`) or 'atss' (adaptive
         # training sample selection over the `atss_topk` nearest cells per level, odtk/box.py:atss_assign_levels; axis-aligned
         # boxes only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
@@ -237,6 +242,8 @@ class Model(nn.Module):
             dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else self.cls_head[0].weight.dtype
             engine = self.inference_engine(dtype)
             if engine is not None:
+                if graph and self.tta is not None:
+                    raise RuntimeError('Model.forward(graph=True) is not available with Model.tta (two passes of the engine)')
                 return engine.replay(x) if graph else engine(x)
         if graph:
             raise RuntimeError('Model.forward(graph=True) needs the fused inference engine (eval mode, GPU tensors, a single '
@@ -249,16 +256,51 @@ class Model(nn.Module):
             return [c.sigmoid() for c in cls_heads], box_heads
         for stride in strides:
             self.level_anchors(stride)
+        if self.tta is not None:
+            # the first pass is decoded before the second runs; one suppression over [pass 0 | mirrored pass mapped back]
+            self.check_inference_options()
+            first = self.candidates(cls_heads, box_heads, strides)
+            del cls_heads, box_heads
+            second = self.candidates(*self.heads(box_ops.flip_batch(x)), strides)
+            return self.suppress_tta(first, second, x.shape[-1])
         return self.postprocess(cls_heads, box_heads, strides)
+
+    def check_inference_options(self):
+        """The run-time options `soft_nms`, `box_voting` and `tta` against the model (axis-aligned boxes only) and their domains."""
+        if self.tta not in (None, 'flip'):
+            raise ValueError("Model.tta must be None or 'flip', not {!r}".format(self.tta))
+        for name, value in (('soft_nms', self.soft_nms), ('box_voting', self.box_voting), ('tta', self.tta)):
+            if value is not None and self.rotated_bbox:
+                raise ValueError('Model.{} is not available for rotated boxes'.format(name))
+
+    def candidates(self, cls_heads, box_heads, strides):
+        """Raw head tensors of axis-aligned boxes -> one candidate list (scores [B, L * top_n], boxes [.., 4], classes)."""
+        if self.fused_postprocess and cls_heads[0].is_cuda:
+            return box_ops.candidates(cls_heads, box_heads, strides, self.anchors, self.threshold, self.top_n, logits=True)
+        per_level = [box_ops.decode(c.sigmoid().contiguous(), b.contiguous(), s, self.threshold, self.top_n, self.anchors[s])
+                     for c, b, s in zip(cls_heads, box_heads, strides)]
+        return [torch.cat(parts, 1) for parts in zip(*per_level)]
+
+    def suppress_tta(self, first, second, width):
+        """The candidates of the pass on x and of the pass on its horizontal flip (`width` = x.shape[-1]) -> detections."""
+        if self.soft_nms is not None and first[0].shape[1] + second[0].shape[1] > box_ops.MAX_SOFT_NMS_COUNT:
+            raise ValueError('Model.tta with Model.soft_nms: the merged list has {} candidates per image, Soft-NMS takes {}: lower '
+                             'top_n'.format(first[0].shape[1] + second[0].shape[1], box_ops.MAX_SOFT_NMS_COUNT))
+        merged = box_ops.concat_candidates([first, second], [0, width])
+        return box_ops.suppress(*merged, self.nms, self.detections, soft_nms=self.soft_nms, vote=self.box_voting,
+                                threshold=self.threshold)
 
     def postprocess(self, cls_heads, box_heads, strides):
         """Raw head tensors -> (scores [B, D], boxes [B, D, 4|6], classes [B, D])."""
-        if self.soft_nms is not None and self.rotated_bbox:
-            raise ValueError('Model.soft_nms is not available for rotated boxes')
+        self.check_inference_options()
         if self.fused_postprocess and cls_heads[0].is_cuda:
             # sigmoid + decode x5 + nms on the head tensors as the convolutions wrote them
             return box_ops.detect(cls_heads, box_heads, strides, self.anchors, self.threshold, self.top_n,
-                                  self.nms, self.detections, self.rotated_bbox, logits=True, soft_nms=self.soft_nms)
+                                  self.nms, self.detections, self.rotated_bbox, logits=True, soft_nms=self.soft_nms,
+                                  vote=self.box_voting)
+        if self.box_voting is not None:
+            return box_ops.suppress(*self.candidates(cls_heads, box_heads, strides), self.nms, self.detections,
+                                    soft_nms=self.soft_nms, vote=self.box_voting, threshold=self.threshold)
         # the reference's sequence, call for call (model.py:140, :153-165); on CPU tensors this is the
         # pure-torch branch of odtk/box.py
         suppress = box_ops.nms_rotated if self.rotated_bbox else box_ops.nms
