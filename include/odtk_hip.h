@@ -67,8 +67,8 @@ extern "C" {
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
  * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t,
- * 9 odtk_candidates_t; -1 for any other value (4 and 8 stay unassigned: tests/test_abi_host.py and tests/test_free_rotate.py probe
- * them as unknown ids).  A binding compiled (or
+ * 9 odtk_candidates_t, 11 odtk_tile_t; -1 for any other value (4, 8 and 10 stay unassigned: tests/test_abi_host.py,
+ * tests/test_free_rotate.py and tests/test_box_vote.py probe them as unknown ids).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -268,6 +268,57 @@ typedef struct odtk_candidates {
 } odtk_candidates_t;
 int odtk_concat_candidates(int batch_size, int n_parts, const odtk_candidates_t *parts, void *const *outputs, uint32_t flags,
                            void *stream);
+
+/*
+ * Tiled (sliced) inference of large images: the image is cut into overlapping tiles of ONE fixed size, the detector runs on the
+ * tiles as a batch, the candidates move back into image coordinates and one suppression sees them all.  No reference equivalent.
+ * A tile table is a HOST array of up to ODTK_MAX_TILES entries; it travels by value in the launch.
+ */
+#define ODTK_MAX_TILES 64             /* entries per call: they travel by value, kernargs stay < 4 KiB */
+typedef struct odtk_tile {
+  int32_t image;            /* image of the batch the tile is cut from; < 0: a padding entry (an all-zero tile, skipped by the merge) */
+  int32_t slot;             /* the tile's position among the tiles of its image (odtk_merge_tile_candidates; the tiler ignores it)  */
+  int32_t x, y;             /* origin of the tile in its image, pixels, >= 0                                                         */
+} odtk_tile_t;              /* 16 bytes; odtk_abi_struct_size id 11 */
+
+/*
+ * odtk_tile_images -- x: device [batch, channels, height, width] of `dtype` (ODTK_F32 / BF16 / F16), NCHW-contiguous
+ * (channels_last = 0) or NHWC-contiguous (channels_last = 1); out: device [n_tiles, channels, tile_h, tile_w], same dtype and format.
+ *     out[i][c][r][q] = x[tiles[i].image][c][tiles[i].y + r][tiles[i].x + q]   where that lies inside the image, +0 elsewhere
+ * and an entry with image < 0 is an all-zero tile (the padding of a last, short chunk: the engine sees one shape only).  A bit copy:
+ * NaN payloads, -0.0 and infinities survive.  Every element of out is written; `slot` is ignored.
+ * ODTK_ERR_INVALID: a null pointer, n_tiles outside 1..ODTK_MAX_TILES, channels outside 1..16, a non-positive size, channels_last
+ * other than 0 / 1, image >= batch, a negative origin, channels * tile_h * tile_w or channels * height * width beyond 2^32 - 1, a
+ * pointer that is not aligned to the element.  Another dtype is ODTK_ERR_UNSUPPORTED.  No workspace; everything is checked on
+ * the host before anything touches HIP.  One elementwise launch (csrc/tile.hpp), timed under ODTK_KERNEL_EPILOGUE.
+ */
+int odtk_tile_images(const void *x, void *out, int batch, int channels, int height, int width, int dtype, int channels_last,
+                     int n_tiles, const odtk_tile_t *tiles, int tile_h, int tile_w, void *stream);
+
+/*
+ * odtk_merge_tile_candidates -- the candidates of the tiles, in tile coordinates, into the candidate lists of their images.
+ * inputs[0..2] = scores [n_tiles, count], boxes [n_tiles, count, 4], classes [n_tiles, count], float32: what odtk_decode_levels
+ * hands over for the batch of tiles.  outputs[0..2] = [batch, slots * count], [batch, slots * count, 4], [batch, slots * count].
+ * Entry i writes positions slot * count .. slot * count + count - 1 of row `image`, and nothing else; the caller covers every
+ * (image, slot) exactly once over its calls, so nothing is cleared.  Entries with image < 0 are skipped.  Per candidate of entry i:
+ *   its score is not > 0 (zero, negative, NaN): copied bit for bit -- score, box and class;
+ *   otherwise, with border > 0, the candidate is CUT when any of
+ *       tile.x > 0 && x1 < border                        tile.x + tile_w < width  && x2 > (float)(tile_w - 1) - border
+ *       tile.y > 0 && y1 < border                        tile.y + tile_h < height && y2 > (float)(tile_h - 1) - border
+ *     holds -- float32 comparisons on the tile-local coordinates, a NaN fails them all -- and becomes an empty slot: score +0, box
+ *     four zeros, class 0 (what decode leaves in unused slots);
+ *   otherwise x1 += (float)tile.x, y1 += (float)tile.y, x2 += (float)tile.x, y2 += (float)tile.y, one float32 addition each; score
+ *     and class unchanged.
+ * border == 0 switches the cut rule off.  The rule drops the truncated candidates that decode's clamp presses against an interior
+ * tile side; with an overlap at least as wide as the objects the neighbouring tile holds each such object whole.
+ * ODTK_ERR_INVALID: a null pointer, n_tiles outside 1..ODTK_MAX_TILES, a count of 0, a non-positive batch, slots or size,
+ * slots * count above ODTK_MAX_NMS_COUNT_SCRATCH, image >= batch, slot outside 0..slots - 1, a border that is negative or not
+ * finite, any undefined flag bit.  ODTK_FLAG_ROTATED is ODTK_ERR_UNSUPPORTED.  No workspace; everything is checked on the host
+ * before anything touches HIP.  One elementwise launch (csrc/tile.hpp), timed under ODTK_KERNEL_NMS.
+ */
+int odtk_merge_tile_candidates(int n_tiles, const odtk_tile_t *tiles, const void *const *inputs, void *const *outputs, size_t count,
+                               int batch, int slots, int tile_h, int tile_w, int height, int width, float border, uint32_t flags,
+                               void *stream);
 
 /*
  * odtk_detect -- decode_levels + nms back to back on one stream (the whole post-processing of

@@ -42,6 +42,7 @@ int odtk_abi_struct_size(int which) {
     case 6: return static_cast<int>(sizeof(odtk_augment_t));
     case 7: return static_cast<int>(sizeof(odtk_rotation_t));
     case 9: return static_cast<int>(sizeof(odtk_candidates_t));
+    case 11: return static_cast<int>(sizeof(odtk_tile_t));
     default: return -1;
   }
 }

@@ -1,11 +1,12 @@
 // input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise), odtk_augment_images and
-// odtk_augment_images_ex (the same with a free rotation).
+// odtk_augment_images_ex (the same with a free rotation); odtk_tile_images (the tiler of tiled inference).
 #include <cmath>
 #include <cstring>
 
 #include "runtime.hpp"
 #include "preprocess.hpp"
 #include "augment.hpp"
+#include "tile.hpp"
 
 extern "C" {
 
@@ -235,6 +236,45 @@ int odtk_augment_images_ex(int batch_size, const odtk_image_t *images, const odt
                            int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
   return augment_images(batch_size, images, augments, rotations, src, src_bytes, tables, tables_len, norm_table, out, height, width, dtype,
                         workspace, workspace_bytes, stream);
+}
+
+// everything is validated here, on the host, before anything touches the device
+int odtk_tile_images(const void *x, void *out, int batch, int channels, int height, int width, int dtype, int channels_last,
+                     int n_tiles, const odtk_tile_t *tiles, int tile_h, int tile_w, void *stream) {
+  if (!x || !out || !tiles || n_tiles < 1 || n_tiles > ODTK_MAX_TILES || channels < 1 || channels > 16) return ODTK_ERR_INVALID;
+  if (batch <= 0 || height <= 0 || width <= 0 || tile_h <= 0 || tile_w <= 0) return ODTK_ERR_INVALID;
+  if (channels_last != 0 && channels_last != 1) return ODTK_ERR_INVALID;
+  for (int i = 0; i < n_tiles; ++i)
+    if (tiles[i].image >= batch || tiles[i].x < 0 || tiles[i].y < 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned es = dtype == ODTK_F32 ? 4u : 2u;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & (es - 1u)) return ODTK_ERR_INVALID;
+  const unsigned long long per_tile = 1ull * channels * tile_h * tile_w;          // 32-bit offsets inside one tile and one image
+  if (per_tile > 0xf0000000ull || 1ull * channels * height * width > 0xffffffffull) return ODTK_ERR_INVALID;
+  static_assert(sizeof(odtk::TileArgs) <= 4096, "kernel arguments travel by value");
+  odtk::TileArgs args;
+  std::memset(&args, 0, sizeof args);
+  args.x = x;
+  args.out = out;
+  args.channels = static_cast<uint32_t>(channels);
+  args.height = static_cast<uint32_t>(height);
+  args.width = static_cast<uint32_t>(width);
+  args.tile_h = static_cast<uint32_t>(tile_h);
+  args.tile_w = static_cast<uint32_t>(tile_w);
+  args.per_tile = static_cast<uint32_t>(per_tile);
+  args.inner = odtk::fastdiv_make(channels_last ? args.channels : args.tile_w);
+  args.middle = odtk::fastdiv_make(channels_last ? args.tile_w : args.tile_h);
+  std::memcpy(args.tiles, tiles, sizeof(odtk_tile_t) * n_tiles);
+  unsigned long long blocks = (per_tile + odtk::kTileThreads * 4ull - 1) / (odtk::kTileThreads * 4ull);     // ~4 elements per lane
+  if (blocks > 4096) blocks = 4096;
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_tiles)), block(odtk::kTileThreads);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (es == 4 && channels_last) timed_launch(ODTK_KERNEL_EPILOGUE, odtk::tile_images_kernel<uint32_t, true>, grid, block, 0, s, args);
+  else if (es == 4) timed_launch(ODTK_KERNEL_EPILOGUE, odtk::tile_images_kernel<uint32_t, false>, grid, block, 0, s, args);
+  else if (channels_last) timed_launch(ODTK_KERNEL_EPILOGUE, odtk::tile_images_kernel<uint16_t, true>, grid, block, 0, s, args);
+  else timed_launch(ODTK_KERNEL_EPILOGUE, odtk::tile_images_kernel<uint16_t, false>, grid, block, 0, s, args);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS, box voting, candidate concatenation and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
+// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS, box voting, candidate concatenation, the merge of tiled inference and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
 #include <cmath>
 #include <cstring>
 
@@ -7,6 +7,7 @@
 #include "nms.hpp"
 #include "soft_nms.hpp"
 #include "box_vote.hpp"
+#include "tile.hpp"
 
 namespace {
 
@@ -292,6 +293,45 @@ int odtk_concat_candidates(int batch_size, int n_parts, const odtk_candidates_t 
   if (blocks > 256 * 16) blocks = 256 * 16;                  // grid-stride beyond 16 workgroups per CU
   timed_launch(ODTK_KERNEL_NMS, odtk::concat_candidates_kernel, dim3(static_cast<unsigned>(blocks)), dim3(odtk::kConcatThreads), 0,
                static_cast<hipStream_t>(stream), ca);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_merge_tile_candidates(int n_tiles, const odtk_tile_t *tiles, const void *const *inputs, void *const *outputs, size_t count,
+                               int batch, int slots, int tile_h, int tile_w, int height, int width, float border, uint32_t flags,
+                               void *stream) {
+  if (n_tiles < 1 || n_tiles > ODTK_MAX_TILES || !tiles || count == 0 || batch <= 0 || slots <= 0) return ODTK_ERR_INVALID;
+  if (tile_h <= 0 || tile_w <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
+  if (count > ODTK_MAX_NMS_COUNT_SCRATCH || static_cast<unsigned long long>(slots) * count > ODTK_MAX_NMS_COUNT_SCRATCH) return ODTK_ERR_INVALID;
+  if (!std::isfinite(border) || border < 0.0f) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (!inputs || !inputs[0] || !inputs[1] || !inputs[2] || !outputs || !outputs[0] || !outputs[1] || !outputs[2]) return ODTK_ERR_INVALID;
+  for (int i = 0; i < n_tiles; ++i) {
+    if (tiles[i].image >= batch) return ODTK_ERR_INVALID;
+    if (tiles[i].image >= 0 && (tiles[i].slot < 0 || tiles[i].slot >= slots)) return ODTK_ERR_INVALID;
+  }
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  static_assert(sizeof(odtk::TileMergeArgs) <= 4096, "kernel arguments travel by value");
+  odtk::TileMergeArgs ma;
+  std::memset(&ma, 0, sizeof ma);
+  ma.scores = static_cast<const uint32_t *>(inputs[0]);
+  ma.boxes = static_cast<const uint32_t *>(inputs[1]);
+  ma.classes = static_cast<const uint32_t *>(inputs[2]);
+  ma.out_scores = static_cast<uint32_t *>(outputs[0]);
+  ma.out_boxes = static_cast<uint32_t *>(outputs[1]);
+  ma.out_classes = static_cast<uint32_t *>(outputs[2]);
+  ma.count = static_cast<uint32_t>(count);
+  ma.total = static_cast<uint32_t>(static_cast<unsigned long long>(slots) * count);
+  ma.tile_h = tile_h;
+  ma.tile_w = tile_w;
+  ma.height = height;
+  ma.width = width;
+  ma.border = border;
+  std::memcpy(ma.tiles, tiles, sizeof(odtk_tile_t) * n_tiles);
+  const unsigned groups = static_cast<unsigned>((count + odtk::kTileThreads - 1) / odtk::kTileThreads);
+  const dim3 grid(groups, static_cast<unsigned>(n_tiles)), block(odtk::kTileThreads);
+  if (border > 0.0f) timed_launch(ODTK_KERNEL_NMS, odtk::merge_tile_candidates_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), ma);
+  else timed_launch(ODTK_KERNEL_NMS, odtk::merge_tile_candidates_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), ma);
   ODTK_HIP_TRY(hipGetLastError());
   return ODTK_OK;
 }

@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote` and `concat_candidates`.  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images` and `merge_tile_candidates`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -19,6 +19,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -194,6 +195,79 @@ std::vector<torch::Tensor> concat_candidates(std::vector<std::vector<torch::Tens
   return result;
 }
 
+// the tile table of tiled inference: one (image, slot, y, x) per entry, the convention of odtk/_C.py
+std::vector<odtk_tile_t> tile_table(const std::vector<std::vector<int>> &tiles, const char *what) {
+  TORCH_CHECK(!tiles.empty() && tiles.size() <= ODTK_MAX_TILES, what, ": 1..", ODTK_MAX_TILES, " tiles per call");
+  std::vector<odtk_tile_t> table(tiles.size());
+  for (size_t i = 0; i < tiles.size(); ++i) {
+    TORCH_CHECK(tiles[i].size() == 4, what, ": a tile is (image, slot, y, x)");
+    table[i] = {tiles[i][0], tiles[i][1], tiles[i][3], tiles[i][2]};
+  }
+  return table;
+}
+
+// the tiler of tiled inference (odtk_tile_images), the signature of odtk/_C.py:tile_images
+torch::Tensor tile_images(torch::Tensor x, std::vector<std::vector<int>> tiles, std::vector<int> size) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "x must be a 4-d CUDA tensor");
+  TORCH_CHECK(size.size() == 2, "tile_images: size is (tile_h, tile_w)");
+  const bool channels_last = !x.is_contiguous() && x.is_contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(x.is_contiguous() || channels_last, "x must be contiguous (NCHW or channels_last)");
+  const auto st = x.scalar_type();
+  TORCH_CHECK(st == torch::kFloat32 || st == torch::kBFloat16 || st == torch::kFloat16, "x must be float32, bfloat16 or float16");
+  const int dtype = st == torch::kFloat32 ? ODTK_F32 : st == torch::kBFloat16 ? ODTK_BF16 : ODTK_F16;
+  auto table = tile_table(tiles, "tile_images");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto out = torch::empty({static_cast<int64_t>(table.size()), x.size(1), size[0], size[1]},
+                          x.options().memory_format(channels_last ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous));
+  void *stream = current_stream(x);
+  {
+    pybind11::gil_scoped_release nogil;
+    checked(odtk_tile_images(x.data_ptr(), out.data_ptr(), static_cast<int>(x.size(0)), static_cast<int>(x.size(1)),
+                             static_cast<int>(x.size(2)), static_cast<int>(x.size(3)), dtype, channels_last ? 1 : 0,
+                             static_cast<int>(table.size()), table.data(), size[0], size[1], stream), "tile_images");
+  }
+  return out;
+}
+
+// the merge of tiled inference (odtk_merge_tile_candidates), the signature of odtk/_C.py:merge_tile_candidates
+std::vector<torch::Tensor> merge_tile_candidates(std::vector<torch::Tensor> parts, std::vector<std::vector<int>> tiles, int batch, int slots,
+                                                 std::vector<int> size, std::vector<int> extent, float border,
+                                                 std::optional<std::vector<torch::Tensor>> out) {
+  TORCH_CHECK(parts.size() == 3 && size.size() == 2 && extent.size() == 2, "merge_tile_candidates: parts is (scores, boxes, classes), size and "
+              "extent are (height, width)");
+  require_gpu_contiguous(parts[0], "scores");
+  require_gpu_contiguous(parts[1], "boxes");
+  require_gpu_contiguous(parts[2], "classes");
+  auto table = tile_table(tiles, "merge_tile_candidates");
+  const int64_t n = static_cast<int64_t>(table.size());
+  TORCH_CHECK(parts[0].dim() == 2 && parts[0].size(0) == n && parts[1].dim() == 3 && parts[1].size(0) == n &&
+              parts[1].size(1) == parts[0].size(1) && parts[1].size(2) == 4 && parts[2].sizes() == parts[0].sizes() && batch > 0 && slots > 0,
+              "merge_tile_candidates: inconsistent shapes");
+  const int64_t count = parts[0].size(1), total = count * slots;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(parts[0].device());
+  auto opt = parts[0].options();
+  std::vector<torch::Tensor> result;
+  if (out.has_value()) {
+    result = *out;
+    TORCH_CHECK(result.size() == 3, "merge_tile_candidates: out is (scores, boxes, classes)");
+    for (const auto &t : result) require_gpu_contiguous(t, "out");
+    TORCH_CHECK(result[0].dim() == 2 && result[0].size(0) == batch && result[0].size(1) == total && result[1].dim() == 3 &&
+                result[1].size(0) == batch && result[1].size(1) == total && result[1].size(2) == 4 && result[2].sizes() == result[0].sizes() &&
+                result[0].device() == parts[0].device(), "merge_tile_candidates: out does not match batch, slots and the parts");
+  } else {
+    result = {torch::zeros({batch, total}, opt), torch::zeros({batch, total, 4}, opt), torch::zeros({batch, total}, opt)};
+  }
+  const void *in[3] = {parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr()};
+  void *outp[3] = {result[0].data_ptr(), result[1].data_ptr(), result[2].data_ptr()};
+  void *stream = current_stream(parts[0]);
+  {
+    pybind11::gil_scoped_release nogil;
+    checked(odtk_merge_tile_candidates(static_cast<int>(n), table.data(), in, outp, static_cast<size_t>(count), batch, slots, size[0], size[1],
+                                       extent[0], extent[1], border, 0u, stream), "merge_tile_candidates");
+  }
+  return result;
+}
+
 std::vector<torch::Tensor> iou(torch::Tensor boxes, torch::Tensor anchors) {
   require_gpu_contiguous(boxes, "boxes");
   require_gpu_contiguous(anchors, "anchors");
@@ -268,7 +342,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   if (odtk_abi_struct_size(0) != static_cast<int>(sizeof(odtk_level_t)) ||
       odtk_abi_struct_size(1) != static_cast<int>(sizeof(odtk_snap_level_t)) ||
       odtk_abi_struct_size(2) != static_cast<int>(sizeof(odtk_snap_rot_level_t)) ||
-      odtk_abi_struct_size(9) != static_cast<int>(sizeof(odtk_candidates_t)))
+      odtk_abi_struct_size(9) != static_cast<int>(sizeof(odtk_candidates_t)) ||
+      odtk_abi_struct_size(11) != static_cast<int>(sizeof(odtk_tile_t)))
     throw py::import_error("odtk._C_ext was compiled against another revision of include/odtk_hip.h than libodtk_hip.so "
                            "(struct sizes differ): rebuild it -- make -C retinanet-examples_amd/csrc");
   py::class_<Engine>(m, "Engine")
@@ -286,6 +361,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("detections_per_im"), py::arg("method"), py::arg("sigma"), py::arg("min_score"), py::arg("return_indices") = false);
   m.def("box_vote", &box_vote, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("kept"), py::arg("vote_thresh"));
   m.def("concat_candidates", &concat_candidates, py::arg("parts"), py::arg("mirror_widths"));
+  m.def("tile_images", &tile_images, py::arg("x"), py::arg("tiles"), py::arg("size"));
+  m.def("merge_tile_candidates", &merge_tile_candidates, py::arg("parts"), py::arg("tiles"), py::arg("batch"), py::arg("slots"), py::arg("size"),
+        py::arg("extent"), py::arg("border"), py::arg("out") = py::none());
   m.def("iou", &iou, py::arg("boxes"), py::arg("anchors"));
   m.def("detect", &detect, py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors"), py::arg("strides"), py::arg("score_thresh"),
         py::arg("top_n"), py::arg("nms_thresh"), py::arg("detections_per_im"), py::arg("rotated") = false, py::arg("logits") = false);

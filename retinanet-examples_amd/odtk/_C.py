@@ -11,7 +11,8 @@ conventions, so `from ._C import decode, nms, iou` in a box.py keeps working:
 
 plus the MI355X-first batched forms (`decode_levels`, `detect`) that cover all pyramid levels of
 the whole batch in one enqueue, `soft_nms` (linear / Gaussian Soft-NMS), `box_vote` (box voting behind a suppression) and
-`concat_candidates` (the merge of flip test-time augmentation): no reference equivalents.
+`concat_candidates` (the merge of flip test-time augmentation), `tile_images` and `merge_tile_candidates` (tiled inference of
+large images): no reference equivalents.
 
 There is NO CPU fallback: tensors must live on the GPU and the shared library must be present
 (build it with `python __graft_entry__.py` or `make -C retinanet-examples_amd/csrc`); anything
@@ -31,6 +32,7 @@ F32, BF16, F16 = 0, 1, 2
 FLAG_ROTATED, FLAG_LOGITS, FLAG_ROTATED_NMS_FIXED_ANGLE = 1, 2, 4
 MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32, 16384, 7680, 1 << 22
 MAX_CONCAT_PARTS = 8
+MAX_TILES = 64
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 ATSS_MAX_TOPK = 16
 
@@ -91,6 +93,11 @@ class Rotation(ctypes.Structure):
 class Candidates(ctypes.Structure):
     """odtk_candidates_t"""
     _fields_ = [('scores', _vp), ('boxes', _vp), ('classes', _vp), ('count', ctypes.c_uint32), ('mirror_width', ctypes.c_int32)]
+
+
+class Tile(ctypes.Structure):
+    """odtk_tile_t"""
+    _fields_ = [('image', ctypes.c_int32), ('slot', ctypes.c_int32), ('x', ctypes.c_int32), ('y', ctypes.c_int32)]
 
 
 _SIGNATURES = {
@@ -161,6 +168,9 @@ _SIGNATURES = {
                                      ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_box_vote': (ctypes.c_int, [ctypes.c_int, _vpp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, _vp]),
     'odtk_concat_candidates': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Candidates), _vpp, ctypes.c_uint32, _vp]),
+    'odtk_tile_images': (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.POINTER(Tile), ctypes.c_int, ctypes.c_int, _vp]),
+    'odtk_merge_tile_candidates': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Tile), _vpp, _vpp, _sz] + [ctypes.c_int] * 6 +
+                                   [ctypes.c_float, ctypes.c_uint32, _vp]),
     'odtk_gemm_init': (ctypes.c_int, [ctypes.c_char_p]),
     'odtk_gemm_plan_export': (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
     'odtk_gemm_plan_import': (ctypes.c_int, [ctypes.c_char_p]),
@@ -204,7 +214,7 @@ def library():
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
         for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation),
-                              (9, Candidates)):
+                              (9, Candidates), (11, Tile)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -402,6 +412,72 @@ def concat_candidates(parts, mirror_widths):
         total += s.shape[1]
     out = _detections(batch, total, 4, dev)
     _launch(lib.odtk_concat_candidates, 'concat_candidates', dev, batch, len(parts), table, _ptrs(out), 0)
+    return out
+
+
+def _tile_table(tiles, what):
+    """The odtk_tile_t array of a list of (image, slot, y, x)."""
+    if not 1 <= len(tiles) <= MAX_TILES:
+        raise RuntimeError('%s: 1..%d tiles per call, not %d' % (what, MAX_TILES, len(tiles)))
+    table = (Tile * len(tiles))()
+    for entry, (image, slot, y, x) in zip(table, tiles):
+        entry.image, entry.slot, entry.x, entry.y = int(image), int(slot), int(x), int(y)
+    return table
+
+
+_TILE_DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+
+
+def tile_images(x, tiles, size):
+    """The tiler of tiled inference (include/odtk_hip.h: odtk_tile_images): one launch.  x [B, C, H, W], float32 / bfloat16 /
+    float16, NCHW- or channels_last-contiguous; tiles: up to 64 (image, slot, y, x), image < 0 = an all-zero tile; size (th, tw)
+    -> [len(tiles), C, th, tw] in x's dtype and memory format, zeros behind the image."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError('x must be a 4-d CUDA tensor')
+    channels_last = not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    if not (x.is_contiguous() or channels_last):
+        raise RuntimeError('x must be contiguous (NCHW or channels_last)')
+    if x.dtype not in _TILE_DTYPES:
+        raise RuntimeError('x must be float32, bfloat16 or float16')
+    lib = library()
+    table = _tile_table(tiles, 'tile_images')
+    th, tw = (int(v) for v in size)
+    batch, channels, height, width = x.shape
+    out = torch.empty((len(table), channels, th, tw), dtype=x.dtype, device=x.device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    _launch(lib.odtk_tile_images, 'tile_images', x.device, x.data_ptr(), out.data_ptr(), batch, channels, height, width,
+            _TILE_DTYPES[x.dtype], int(channels_last), len(table), table, th, tw)
+    return out
+
+
+def merge_tile_candidates(parts, tiles, batch, slots, size, extent, border, out=None):
+    """The merge of tiled inference (include/odtk_hip.h: odtk_merge_tile_candidates): one launch.  parts: (scores [n, count], boxes
+    [n, count, 4], classes [n, count]) of the n tiles; tiles: their (image, slot, y, x); size (th, tw); extent (H, W) of the images
+    -> [scores [batch, slots * count], boxes [.., 4], classes]: `out` when given (entry i writes its `count` positions of row
+    `image` and nothing else), otherwise new lists whose other positions are empty slots."""
+    lib = library()
+    scores, boxes, classes = parts
+    _check_input(scores, 'scores')
+    _check_input(boxes, 'boxes')
+    _check_input(classes, 'classes')
+    table = _tile_table(tiles, 'merge_tile_candidates')
+    batch, slots = int(batch), int(slots)
+    if scores.dim() != 2 or scores.shape[0] != len(table) or boxes.shape != (len(table), scores.shape[1], 4) or classes.shape != scores.shape \
+            or batch < 1 or slots < 1:
+        raise RuntimeError('merge_tile_candidates: inconsistent shapes')
+    count = scores.shape[1]
+    total = slots * count
+    if out is None:
+        out = [torch.zeros(shape, dtype=torch.float32, device=scores.device) for shape in ((batch, total), (batch, total, 4), (batch, total))]
+    else:
+        out = list(out)
+        for t in out:
+            _check_input(t, 'out')
+        if len(out) != 3 or out[0].shape != (batch, total) or out[1].shape != (batch, total, 4) or out[2].shape != (batch, total) \
+                or out[0].device != scores.device:
+            raise RuntimeError('merge_tile_candidates: out does not match batch, slots and the parts')
+    _launch(lib.odtk_merge_tile_candidates, 'merge_tile_candidates', scores.device, len(table), table, _ptrs([scores, boxes, classes]),
+            _ptrs(out), count, batch, slots, int(size[0]), int(size[1]), int(extent[0]), int(extent[1]), float(border), 0)
     return out
 
 

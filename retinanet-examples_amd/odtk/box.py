@@ -637,6 +637,123 @@ def flip_batch(x):
     return flipped
 
 
+MAX_TILES = _C.MAX_TILES                           # tile entries per call of `tile_images` / `merge_tile_candidates`
+
+
+def _pair_of_ints(value, name):
+    pair = (value, value) if isinstance(value, int) else tuple(value)
+    if len(pair) != 2 or any(int(v) != v for v in pair):
+        raise ValueError('%s must be an integer or a pair of integers, not %r' % (name, value))
+    return int(pair[0]), int(pair[1])
+
+
+def tile_grid(height, width, size, overlap):
+    """The origins (y, x), row-major, of the tiles of `size` = (th, tw) that cover a height x width image with `overlap` =
+    (oy, ox) pixels shared by neighbours, 0 <= overlap < size.  Per axis, with step = size - overlap: an extent <= size has the one
+    origin 0 (the tile is zero-padded behind the image); otherwise 0, step, 2 step, ... while origin + size < extent, then one last
+    origin extent - size: the last tile is shifted back, never padded."""
+    size, overlap = _pair_of_ints(size, 'size'), _pair_of_ints(overlap, 'overlap')
+    if height < 1 or width < 1 or min(size) < 1:
+        raise ValueError('tile_grid: sizes must be positive')
+    axes = []
+    for extent, tile, over in zip((int(height), int(width)), size, overlap):
+        if not 0 <= over < tile:
+            raise ValueError('tile_grid: the overlap must be in [0, size), not %d for size %d' % (over, tile))
+        origins = [0]
+        if extent > tile:
+            origins = list(range(0, extent - tile, tile - over)) + [extent - tile]
+        axes.append(origins)
+    return [(y, x) for y in axes[0] for x in axes[1]]
+
+
+def _tile_entries(tiles, what, batch=None):
+    tiles = [tuple(int(v) for v in t) for t in tiles]
+    if not 1 <= len(tiles) <= MAX_TILES or any(len(t) != 4 for t in tiles):
+        raise ValueError('%s: 1..%d tiles (image, slot, y, x) per call' % (what, MAX_TILES))
+    if any(t[2] < 0 or t[3] < 0 for t in tiles) or (batch is not None and any(t[0] >= batch for t in tiles)):
+        raise ValueError('%s: a tile names an image past the batch or a negative origin' % what)
+    return tiles
+
+
+def tile_images(x, tiles, size):
+    """The tiler of tiled inference (definition in include/odtk_hip.h: odtk_tile_images).  x [B, C, H, W]; tiles: up to 64 entries
+    (image, slot, y, x) -- the window of `image` at origin (y, x); image < 0: an all-zero tile, the padding of a short chunk; `slot`
+    is ignored here; size (th, tw) -> [len(tiles), C, th, tw] in x's dtype and memory format, +0 wherever a window leaves its image.
+    A bit copy.  GPU tensors (float32 / bfloat16 / float16): one HIP launch; any other tensor: the same in torch."""
+    th, tw = _pair_of_ints(size, 'size')
+    if x.dim() != 4 or th < 1 or tw < 1:
+        raise ValueError('tile_images: x is [B, C, H, W] and the size positive')
+    tiles = _tile_entries(tiles, 'tile_images', x.shape[0])
+    channels_last = not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    if x.is_cuda:
+        if not 1 <= x.shape[1] <= 16:
+            raise ValueError('tile_images: 1..16 channels, not %d' % x.shape[1])
+        return _C.tile_images(x if channels_last else x.contiguous(), tiles, (th, tw))
+    out = torch.zeros((len(tiles), x.shape[1], th, tw), dtype=x.dtype, device=x.device)
+    if channels_last:
+        out = out.contiguous(memory_format=torch.channels_last)
+    for i, (image, _, y, left) in enumerate(tiles):
+        rows, cols = min(th, x.shape[2] - y), min(tw, x.shape[3] - left)
+        if image >= 0 and rows > 0 and cols > 0:
+            out[i, :, :rows, :cols] = x[image, :, y:y + rows, left:left + cols]
+    return out
+
+
+def merge_tile_candidates(parts, tiles, batch, slots, size, extent, border=0.0, out=None):
+    """The merge of tiled inference (definition in include/odtk_hip.h: odtk_merge_tile_candidates).  parts: (scores [n, count], boxes
+    [n, count, 4], classes [n, count]) decoded from the n tiles, in tile coordinates; tiles: their entries (image, slot, y, x), image
+    < 0 skipped; size (th, tw); extent (H, W) of the images.  Entry i fills positions slot * count .. slot * count + count - 1 of row
+    `image` of (scores [batch, slots * count], boxes [.., 4], classes): candidates with a score > 0 move by the tile's origin (one
+    float32 addition per coordinate) unless `border` > 0 cuts them -- they reach into the outermost `border` pixels of a tile side
+    that is not an image side -- which leaves an empty slot; everything else is copied bit for bit.  `out`: lists to write into
+    (several calls that together cover every (image, slot)); without it new lists whose other positions are empty slots.
+    GPU tensors: one HIP launch; any other tensor: the same in torch."""
+    (th, tw), (height, width) = _pair_of_ints(size, 'size'), _pair_of_ints(extent, 'extent')
+    border, batch, slots = float(border), int(batch), int(slots)
+    if not (math.isfinite(border) and border >= 0):
+        raise ValueError('merge_tile_candidates: the border must be finite and not negative, not %r' % (border,))
+    if min(th, tw, height, width, batch, slots) < 1:
+        raise ValueError('merge_tile_candidates: batch, slots and sizes must be positive')
+    tiles = _tile_entries(tiles, 'merge_tile_candidates', batch)
+    if any(t[0] >= 0 and not 0 <= t[1] < slots for t in tiles):
+        raise ValueError('merge_tile_candidates: a slot outside 0..%d' % (slots - 1))
+    scores, boxes, classes = (t.float() for t in parts)
+    count = scores.shape[1]
+    if scores.shape != (len(tiles), count) or boxes.shape != (len(tiles), count, 4) or classes.shape != scores.shape or count < 1:
+        raise ValueError('merge_tile_candidates: the parts are (scores [n, count], boxes [n, count, 4], classes [n, count]) of the n tiles')
+    if slots * count > _C.MAX_NMS_COUNT_SCRATCH:
+        raise ValueError('merge_tile_candidates: %d candidates per image, the limit is %d' % (slots * count, _C.MAX_NMS_COUNT_SCRATCH))
+    if scores.is_cuda:
+        return _C.merge_tile_candidates((scores.contiguous(), boxes.contiguous(), classes.contiguous()), tiles, batch, slots, (th, tw),
+                                        (height, width), border, out)
+    if out is None:
+        out = [scores.new_zeros((batch, slots * count)), scores.new_zeros((batch, slots * count, 4)), scores.new_zeros((batch, slots * count))]
+    edge = torch.tensor(border, dtype=torch.float32)
+    far_x, far_y = torch.tensor(tw - 1, dtype=torch.float32) - edge, torch.tensor(th - 1, dtype=torch.float32) - edge
+    for i, (image, slot, y, left) in enumerate(tiles):
+        if image < 0:
+            continue
+        s, b, c = scores[i], boxes[i], classes[i]
+        positive = s > 0
+        cut = torch.zeros_like(positive)
+        if border > 0:
+            if left > 0:
+                cut |= b[:, 0] < edge
+            if y > 0:
+                cut |= b[:, 1] < edge
+            if left + tw < width:
+                cut |= b[:, 2] > far_x
+            if y + th < height:
+                cut |= b[:, 3] > far_y
+        cut &= positive
+        moved = torch.where(positive[:, None], b + torch.tensor([left, y, left, y], dtype=torch.float32), b)
+        span = slice(slot * count, (slot + 1) * count)
+        out[0][image, span] = torch.where(cut, torch.zeros_like(s), s)
+        out[1][image, span] = torch.where(cut[:, None], torch.zeros_like(b), moved)
+        out[2][image, span] = torch.where(cut, torch.zeros_like(c), c)
+    return out
+
+
 def suppress(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, soft_nms=None, vote=None, threshold=0.05):
     """The tail of the post-processing on ONE candidate list of axis-aligned boxes: hard NMS, or Soft-NMS when `soft_nms` is a dict
     (`method`, `sigma`, `min_score`: default `threshold`), then box voting at IoU `vote` when that is not None.

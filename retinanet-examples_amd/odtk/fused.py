@@ -583,6 +583,8 @@ class FusedRetinaNet(nn.Module):
                getattr(m, 'box_voting', None))                                                               #  and so is box voting)
         if getattr(m, 'tta', None) is not None:
             raise RuntimeError('FusedRetinaNet.replay is not available with Model.tta (two passes of the engine)')
+        if getattr(m, 'tile', None) is not None:
+            raise RuntimeError('FusedRetinaNet.replay is not available with Model.tile (several passes of the engine)')
         entry = self._graphs.get(key)
         if entry is None:
             static_x = torch.empty_like(x)
@@ -713,6 +715,9 @@ class FusedRetinaNet(nn.Module):
     def forward(self, x):
         m = self.model[0]
         m.check_inference_options()
+        if getattr(m, 'tile', None) is not None:
+            # tiled inference: every chunk of tiles is decoded BEFORE the next pass runs (same reason as below)
+            return m.forward_tiled(x, lambda tiles: self._postprocess(tiles, True))
         if getattr(m, 'tta', None) is None:
             return self._postprocess(x, False)
         # test-time augmentation by the horizontal flip: the first pass is decoded BEFORE the second runs (the head tensors may

@@ -26,6 +26,13 @@ What differs from the reference, and why:
     (odtk/box.py:box_vote, one HIP launch: every kept box becomes the score-weighted mean of its class's candidates that overlap it
     by at least `value`) and test-time augmentation by the horizontal flip (the network also runs on the mirrored batch, one
     suppression over both candidate lists).  Axis-aligned boxes only; never stored in a checkpoint.
+  * `--tile size` with `--tile-overlap px`, `--tile-border px` and `--tile-batch n` (infer; train: its validation passes) is new:
+    tiled inference of large images (odtk/model.py:forward_tiled).  Every image of the batch is cut into overlapping square tiles
+    of `size` pixels (a multiple of the model's stride; one HIP launch per chunk, csrc/tile.hpp), the network runs on chunks of
+    `--tile-batch` tiles (default 8) -- one tensor shape whatever the image, so one plan of the engine --, the candidates move back
+    into image coordinates (one more launch; `--tile-border` drops those that reach into the outermost pixels of an interior tile
+    side, where the neighbouring tile sees the object whole) and one suppression sees them all.  Default overlap: a quarter of the
+    size.  Axis-aligned boxes only, not together with `--tta`; never stored in a checkpoint.
 """
 import argparse
 import os
@@ -70,7 +77,14 @@ _COMMON = [_flag('--with-apex', bool, text=_DROPPED), _flag('--with-dali', bool,
                  'mean of the candidates of its class that overlap it by at least this IoU, in (0, 1] (0.65 is customary; not with '
                  '--rotated-bbox)', metavar='value'),
            _flag('--tta', str, argparse.SUPPRESS, 'test-time augmentation: flip = the network also runs on the mirrored batch and one '
-                 'suppression sees both candidate lists (about two forwards per batch; not with --rotated-bbox)', choices=['flip'])]
+                 'suppression sees both candidate lists (about two forwards per batch; not with --rotated-bbox)', choices=['flip']),
+           _flag('--tile', int, argparse.SUPPRESS, 'tiled inference of large images: cut every image into overlapping square tiles of this '
+                 "many pixels (a multiple of the model's stride), run the network on the tiles and suppress once over all their candidates "
+                 '(not with --rotated-bbox or --tta)', metavar='size'),
+           _flag('--tile-overlap', int, argparse.SUPPRESS, 'pixels that neighbouring tiles share (default: a quarter of --tile)', metavar='px'),
+           _flag('--tile-border', float, argparse.SUPPRESS, 'drop the candidates of a tile that reach into this many of its outermost pixels '
+                 'on a side that is not an image side (default 0: keep all)', metavar='px'),
+           _flag('--tile-batch', int, argparse.SUPPRESS, 'tiles per pass of the network (default 8, at most 64)', metavar='n')]
 
 # same names, types and defaults as the reference's parser (main.py:15-118)
 TRAIN_FLAGS = [
@@ -163,6 +177,22 @@ def parse(args):
             parser.error('--%s is not available with --rotated-bbox' % flag.replace('_', '-'))
     if hasattr(parsed, 'box_voting') and not 0 < parsed.box_voting <= 1:          # (a NaN fails both comparisons)
         parser.error('--box-voting must be in (0, 1]')
+    if not hasattr(parsed, 'tile'):
+        if any(hasattr(parsed, f) for f in ('tile_overlap', 'tile_border', 'tile_batch')):
+            parser.error('--tile-overlap / --tile-border / --tile-batch need --tile size')
+    else:
+        if getattr(parsed, 'rotated_bbox', False):
+            parser.error('--tile is not available with --rotated-bbox')
+        if hasattr(parsed, 'tta'):
+            parser.error('--tile is not available with --tta')
+        if parsed.tile < 1:
+            parser.error('--tile must be positive')
+        if not 0 <= getattr(parsed, 'tile_overlap', 0) < parsed.tile:
+            parser.error('--tile-overlap must be in [0, --tile)')
+        if not 0 <= getattr(parsed, 'tile_border', 0.0) < float('inf'):           # (a NaN fails both comparisons)
+            parser.error('--tile-border must be finite and not negative')
+        if not 1 <= getattr(parsed, 'tile_batch', 8) <= 64:
+            parser.error('--tile-batch must be in 1..64')
     if hasattr(parsed, 'atss_topk') and getattr(parsed, 'assigner', 'iou') != 'atss':
         parser.error('--atss-topk needs --assigner atss')
     if hasattr(parsed, 'atss_topk') and not 1 <= parsed.atss_topk <= 16:
@@ -178,6 +208,16 @@ def soft_nms_options(args, model):
         return None
     return {'method': args.soft_nms, 'sigma': getattr(args, 'soft_nms_sigma', 0.5),
             'min_score': getattr(args, 'soft_nms_min_score', model.threshold)}
+
+
+def tile_options(args):
+    """What `--tile*` ask for, as `Model.tile` takes it (None: the flags were not given)."""
+    if not hasattr(args, 'tile'):
+        return None
+    tile = {'size': (args.tile, args.tile), 'border': getattr(args, 'tile_border', 0.0), 'batch': getattr(args, 'tile_batch', 8)}
+    if hasattr(args, 'tile_overlap'):
+        tile['overlap'] = (args.tile_overlap, args.tile_overlap)
+    return tile
 
 
 def load_model(args, verbose=False):
@@ -240,6 +280,12 @@ def worker(rank, args, world, spawned=False):
         for flag, value in (('--box-voting', model.box_voting), ('--tta', model.tta)):
             if value is not None and args.rotated_bbox:
                 raise RuntimeError('%s is not available for a model with rotated boxes' % flag)
+        model.tile = tile_options(args)
+        if model.tile is not None:
+            if args.rotated_bbox:
+                raise RuntimeError('--tile is not available for a model with rotated boxes')
+            if args.tile % model.stride:
+                raise RuntimeError("--tile must be a multiple of the model's stride, {}".format(model.stride))
     if args.command == 'train':
         model.assigner, model.atss_topk = getattr(args, 'assigner', 'iou'), getattr(args, 'atss_topk', 9)
         if model.assigner == 'atss' and args.rotated_bbox:

@@ -89,6 +89,11 @@ class Model(nn.Module):
         # augmentation -- None, or 'flip': the network also runs on the mirrored batch and one suppression sees both candidate lists
         self.box_voting = None
         self.tta = None
+        # tiled inference of large images, one more run-time option of this kind: None, or a dict with `size` (th, tw) -- multiples
+        # of the model's stride --, `overlap` (default a quarter of the size), `border` (default 0: the cut rule of
+        # odtk/box.py:merge_tile_candidates is off) and `batch`, the tiles per pass of the network (default 8).  The image is cut
+        # into overlapping tiles of that one size, the network runs on chunks of `batch` tiles, one suppression sees all candidates
+        self.tile = None
         # how ground truth becomes training targets: 'iou' (the reference's fixed thresholds, `anchor_ious`) or 'atss' (adaptive
         # training sample selection over the `atss_topk` nearest cells per level, odtk/box.py:atss_assign_levels; axis-aligned
         # boxes only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
@@ -244,11 +249,15 @@ class Model(nn.Module):
             if engine is not None:
                 if graph and self.tta is not None:
                     raise RuntimeError('Model.forward(graph=True) is not available with Model.tta (two passes of the engine)')
+                if graph and self.tile is not None:
+                    raise RuntimeError('Model.forward(graph=True) is not available with Model.tile (several passes of the engine)')
                 return engine.replay(x) if graph else engine(x)
         if graph:
             raise RuntimeError('Model.forward(graph=True) needs the fused inference engine (eval mode, GPU tensors, a single '
                                'ResNet-FPN backbone)')
 
+        if self.tile is not None and not self.exporting:
+            return self.forward_tiled(x, self._tile_candidates)
         cls_heads, box_heads = self.heads(x)
         strides = [x.shape[-1] // c.shape[-1] for c in cls_heads]
         if self.exporting:
@@ -266,12 +275,73 @@ class Model(nn.Module):
         return self.postprocess(cls_heads, box_heads, strides)
 
     def check_inference_options(self):
-        """The run-time options `soft_nms`, `box_voting` and `tta` against the model (axis-aligned boxes only) and their domains."""
+        """The run-time options `soft_nms`, `box_voting`, `tta` and `tile` against the model (axis-aligned boxes only) and their
+        domains."""
         if self.tta not in (None, 'flip'):
             raise ValueError("Model.tta must be None or 'flip', not {!r}".format(self.tta))
-        for name, value in (('soft_nms', self.soft_nms), ('box_voting', self.box_voting), ('tta', self.tta)):
+        for name, value in (('soft_nms', self.soft_nms), ('box_voting', self.box_voting), ('tta', self.tta), ('tile', self.tile)):
             if value is not None and self.rotated_bbox:
                 raise ValueError('Model.{} is not available for rotated boxes'.format(name))
+        if self.tile is not None:
+            if self.tta is not None:
+                raise ValueError('Model.tile is not available together with Model.tta')
+            self.tile_options()
+
+    def tile_options(self):
+        """`Model.tile` checked and completed -> (size (th, tw), overlap (oy, ox), border, batch)."""
+        tile = self.tile
+        if not isinstance(tile, dict) or 'size' not in tile or set(tile) - {'size', 'overlap', 'border', 'batch'}:
+            raise ValueError("Model.tile must be None or a dict with 'size' and optionally 'overlap', 'border' and 'batch', not "
+                             '{!r}'.format(tile))
+        size = box_ops._pair_of_ints(tile['size'], 'Model.tile: size')
+        if min(size) < 1 or any(v % self.stride for v in size):
+            raise ValueError("Model.tile: the size must be a positive multiple of the model's stride {}, not {}".format(self.stride, size))
+        overlap = box_ops._pair_of_ints(tile['overlap'], 'Model.tile: overlap') if tile.get('overlap') is not None \
+            else (size[0] // 4, size[1] // 4)
+        if any(not 0 <= o < v for o, v in zip(overlap, size)):
+            raise ValueError('Model.tile: the overlap must be in [0, size), not {} for size {}'.format(overlap, size))
+        border = float(tile.get('border', 0) or 0)
+        if not (math.isfinite(border) and border >= 0):
+            raise ValueError('Model.tile: the border must be finite and not negative, not {!r}'.format(tile.get('border')))
+        batch = tile.get('batch', 8)
+        if int(batch) != batch or not 1 <= batch <= box_ops.MAX_TILES:
+            raise ValueError('Model.tile: batch (tiles per pass of the network) must be in 1..{}, not {!r}'.format(box_ops.MAX_TILES, batch))
+        return size, overlap, border, int(batch)
+
+    def _tile_candidates(self, tiles):
+        """One pass of the eager network on a batch of tiles -> their candidate list."""
+        cls_heads, box_heads = self.heads(tiles)
+        strides = [tiles.shape[-1] // c.shape[-1] for c in cls_heads]
+        for stride in strides:
+            self.level_anchors(stride)
+        return self.candidates(cls_heads, box_heads, strides)
+
+    def forward_tiled(self, x, candidates_of):
+        """Tiled inference (`Model.tile`): the grid of x.shape[-2:], the tiles image-major in chunks of `batch` (the last chunk
+        padded with zero tiles, so the network sees one shape only), per chunk the tiler, one pass of the network and its decode
+        (`candidates_of`: tiles -> candidate list; a chunk is decoded before the next pass runs), the merge into the lists
+        [B, T * L * top_n] of the whole images, and one suppression over them."""
+        self.check_inference_options()
+        size, overlap, border, chunk = self.tile_options()
+        batch, height, width = x.shape[0], x.shape[-2], x.shape[-1]
+        grid = box_ops.tile_grid(height, width, size, overlap)
+        entries = [(image, slot, y, left) for image in range(batch) for slot, (y, left) in enumerate(grid)]
+        merged = None
+        for first in range(0, len(entries), chunk):
+            part = entries[first:first + chunk]
+            part = part + [(-1, 0, 0, 0)] * (chunk - len(part))
+            found = candidates_of(box_ops.tile_images(x, part, size))
+            if merged is None:
+                count = found[0].shape[1]
+                if self.soft_nms is not None and len(grid) * count > box_ops.MAX_SOFT_NMS_COUNT:
+                    raise ValueError('Model.tile with Model.soft_nms: the merged list has {} candidates per image ({} tiles), Soft-NMS '
+                                     'takes {}: lower top_n'.format(len(grid) * count, len(grid), box_ops.MAX_SOFT_NMS_COUNT))
+                merged = [found[0].new_empty((batch, len(grid) * count), dtype=torch.float32),
+                          found[0].new_empty((batch, len(grid) * count, 4), dtype=torch.float32),
+                          found[0].new_empty((batch, len(grid) * count), dtype=torch.float32)]
+            box_ops.merge_tile_candidates(found, part, batch, len(grid), size, (height, width), border, out=merged)
+        return box_ops.suppress(*merged, self.nms, self.detections, soft_nms=self.soft_nms, vote=self.box_voting,
+                                threshold=self.threshold)
 
     def candidates(self, cls_heads, box_heads, strides):
         """Raw head tensors of axis-aligned boxes -> one candidate list (scores [B, L * top_n], boxes [.., 4], classes)."""
