@@ -528,6 +528,23 @@ int odtk_gemm_plan_pin_misses(void);
 int odtk_gemm_bias_act(void *y, const void *x, const void *w, const float *bias, const void *residual,
                        size_t m, int n, int k, int dtype, int relu,
                        void *workspace, size_t workspace_size, void *stream);
+/*
+ * odtk_bottleneck_seam -- the seam between two bottleneck blocks as ONE pass (csrc/seam.hpp): the last 1x1 convolution of a block
+ * with its skip and ReLU, and the first 1x1 convolution of the next block with its ReLU, which reads the first one's output from
+ * registers instead of from memory:
+ *     out[p][c] = rne(relu( sum_k y2[p][k] * w3[c][k] + b3[c] + skip[p][c] ))          c < c_mid,  k < c_in
+ *     z[p][n]   = rne(relu( sum_c out[p][c] * w1[n][c] + b1[n] ))                      n < c_next
+ * fp32 sums, rne = round-to-nearest-even to `dtype`; the second product reads the ROUNDED out, so both outputs are what the two
+ * odtk_gemm_bias_act calls it replaces define (up to the order of the fp32 sums).  y2 [m, c_in], skip and out [m, c_mid],
+ * z [m, c_next], w3 [c_mid, c_in], w1 [c_next, c_mid]: device, row-major, `dtype` (ODTK_BF16 / ODTK_F16), 16-byte aligned;
+ * b3 [c_mid] and b1 [c_next]: DEVICE float32.  The outputs must not alias each other or an input.
+ * ODTK_ERR_INVALID: a null, aliased or misaligned pointer, a channel count < 1.  ODTK_ERR_UNSUPPORTED: another dtype, or channel
+ * counts other than c_in = 64, c_mid = 256, c_next = 64 | 128 (ResNet-50/101/152's layer1 and its hand-over to layer2: the weights
+ * of the later layers do not fit the LDS beside the tile).  No workspace; one launch, timed under ODTK_KERNEL_SEAM.
+ * No reference equivalent as a kernel (torchvision Bottleneck.forward, reference odtk/backbones/resnet.py).
+ */
+int odtk_bottleneck_seam(void *out, void *z, const void *y2, const void *skip, const void *w3, const float *b3, const void *w1,
+                         const float *b1, size_t m, int c_in, int c_mid, int c_next, int dtype, void *stream);
 
 /*
  * odtk_snap_to_anchors -- fused training-target assignment for ONE pyramid level of the whole batch.
@@ -684,7 +701,8 @@ int odtk_retina_loss_levels_backward(int n_levels, const odtk_loss_level_t *leve
 #define ODTK_KERNEL_STEM_PACK 14  /* stem_pack_kernel (space-to-depth pack of the network input)        */
 #define ODTK_KERNEL_LOSS_REDUCE 15 /* loss_reduce_kernel (second launch of the forward through a workspace)   */
 #define ODTK_KERNEL_ATSS_STATS 16 /* atss_stats_kernel (ATSS: candidates + threshold; its dense launch counts as ODTK_KERNEL_TARGETS) */
-#define ODTK_KERNEL_COUNT     17
+#define ODTK_KERNEL_SEAM      17  /* bottleneck_seam_kernel (conv3 + skip + ReLU and the next conv1 in one pass)      */
+#define ODTK_KERNEL_COUNT     18
 /* on: 0 = off, otherwise a bit mask of kernel ids (1 << ODTK_KERNEL_*), -1 = all.  An event pair
  * is a queue marker before and after the kernel: cheap for the 3 post-processing launches of a step,
  * measurably NOT free for the ~110 epilogue launches (about 10 % of an 8.7 ms step), so time those

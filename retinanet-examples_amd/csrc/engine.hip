@@ -1,10 +1,12 @@
 // engine.hip -- what the inference engine runs between convolutions: bias + activation epilogues, the max-pool, nearest
-// 2x upsampling, the pyramid canvas, the stem pack, and the hipBLASLt GEMM (gemm_lt.hpp is included here only).
+// 2x upsampling, the pyramid canvas, the stem pack, the hipBLASLt GEMM (gemm_lt.hpp is included here only) and the bottleneck seam
+// (seam.hpp: two 1x1 convolutions of layer1 in one MFMA pass).
 #include <cstring>
 
 #include "runtime.hpp"
 #include "epilogue.hpp"
 #include "gemm_lt.hpp"
+#include "seam.hpp"
 
 namespace {
 
@@ -64,9 +66,50 @@ int stem_pack_launch(const void *x, void *out, int batch, int height, int width,
   return ODTK_OK;
 }
 
+template <typename T, int N2>
+int seam_launch(const void *y2, const void *skip, const void *w3, const float *b3, const void *w1, const float *b1, void *out, void *z,
+                uint64_t m, hipStream_t stream) {
+  constexpr size_t lds = odtk::seam_lds_bytes<N2>();
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(&odtk::bottleneck_seam_kernel<T, N2>), lds, "bottleneck_seam_kernel LDS");
+  if (rc != ODTK_OK) return rc;
+  int device = 0, cus = 0;
+  ODTK_HIP_TRY(hipGetDevice(&device));
+  ODTK_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  // persistent: as many workgroups as the LDS lets a CU hold (160 KiB: two with 64 outputs, one with 128), each staging the weights once
+  constexpr uint64_t per_group = odtk::kSeamThreads / 64 * 32;
+  uint64_t blocks = (m + per_group - 1) / per_group;
+  const uint64_t resident = static_cast<uint64_t>(cus > 0 ? cus : 1) * (160 * 1024 / lds);
+  if (blocks > resident) blocks = resident;
+  timed_launch(ODTK_KERNEL_SEAM, odtk::bottleneck_seam_kernel<T, N2>, dim3(static_cast<unsigned>(blocks)), dim3(odtk::kSeamThreads), lds, stream,
+               static_cast<const uint16_t *>(y2), static_cast<const uint16_t *>(skip), static_cast<const uint16_t *>(w3), b3,
+               static_cast<const uint16_t *>(w1), b1, static_cast<uint16_t *>(out), static_cast<uint16_t *>(z), m);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int odtk_bottleneck_seam(void *out, void *z, const void *y2, const void *skip, const void *w3, const float *b3, const void *w1,
+                         const float *b1, size_t m, int c_in, int c_mid, int c_next, int dtype, void *stream) {
+  if (!out || !z || !y2 || !skip || !w3 || !b3 || !w1 || !b1 || c_in <= 0 || c_mid <= 0 || c_next <= 0) return ODTK_ERR_INVALID;
+  if (out == z || out == y2 || out == skip || z == y2 || z == skip) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (c_in != odtk::kSeamCin || c_mid != odtk::kSeamCmid || (c_next != 64 && c_next != 128)) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(y2) | reinterpret_cast<uintptr_t>(skip) |
+       reinterpret_cast<uintptr_t>(w3) | reinterpret_cast<uintptr_t>(w1)) & 15u)
+    return ODTK_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(b3) | reinterpret_cast<uintptr_t>(b1)) & 3u) return ODTK_ERR_INVALID;
+  if (m > (1ull << 40)) return ODTK_ERR_INVALID;
+  if (m == 0) return ODTK_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == ODTK_BF16)
+    return c_next == 64 ? seam_launch<odtk::BF16, 64>(y2, skip, w3, b3, w1, b1, out, z, m, s)
+                        : seam_launch<odtk::BF16, 128>(y2, skip, w3, b3, w1, b1, out, z, m, s);
+  return c_next == 64 ? seam_launch<odtk::F16, 64>(y2, skip, w3, b3, w1, b1, out, z, m, s)
+                      : seam_launch<odtk::F16, 128>(y2, skip, w3, b3, w1, b1, out, z, m, s);
+}
 
 int odtk_bias_act(void *y, const float *bias, const void *residual, size_t n_pixels, int channels, int dtype,
                   int relu, void *stream) {

@@ -178,13 +178,14 @@ _SIGNATURES = {
     'odtk_gemm_bias_act': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'odtk_bottleneck_seam': (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_size_t] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     'odtk_profile_collect': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
 }
 
 KERNEL_NAMES = ('prefilter_scan_kernel', 'select_decode_kernel', 'nms_kernel', 'iou_pairs_kernel', 'bias_act_kernel',
                 'snap_to_anchors_kernel', 'gemm_bias_act', 'retina_loss_kernel', 'select_hist_kernel', 'select_filter_kernel',
                 'nms_first_round_kernel', 'rotated_sup_matrix_kernel', 'bias_act_maxpool_kernel', 'upsample_nearest2x_kernel',
-                'stem_pack_kernel', 'loss_reduce_kernel', 'atss_stats_kernel')
+                'stem_pack_kernel', 'loss_reduce_kernel', 'atss_stats_kernel', 'bottleneck_seam_kernel')
 # HBM bytes the epilogue entry points move, per kernel name, while `traffic_count` is on (bench.py's epilogue_roofline: the
 # algorithmic bytes of every call -- each element read once and written once, + the skip input -- divided by the kernel time)
 traffic_count = False
@@ -1093,6 +1094,32 @@ def gemm_bias_act(x, weight, bias, residual=None, relu=True):
                                             b * h * w, n, k, _DTYPES[x.dtype], 1 if relu else 0,
                                             ws.data_ptr(), ws.numel(), stream), 'gemm_bias_act')
     return y
+
+
+def bottleneck_seam(y2, skip, w3, b3, w1, b1):
+    """The seam between two bottleneck blocks as one HIP pass (csrc/seam.hpp): -> (out, z) with
+    out = relu(conv1x1(y2, w3) + b3 + skip) and z = relu(conv1x1(out, w1) + b1), both channels_last -- what two
+    `gemm_bias_act` calls compute, without reading `out` back.  y2 [B, 64, H, W] and skip [B, 256, H, W] channels_last, bfloat16 or
+    float16; w3 [256, 64(, 1, 1)], w1 [64 | 128, 256(, 1, 1)] of that dtype; b3, b1 float32.  Other shapes raise."""
+    if not y2.is_cuda or y2.dim() != 4 or y2.dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError('bottleneck_seam: y2 must be a 4-d CUDA tensor of bfloat16/float16')
+    b, k, h, w = y2.shape
+    c, n = w3.shape[0], w1.shape[0]
+    for name, wt, rows, cols in (('w3', w3, c, k), ('w1', w1, n, c)):
+        if wt.numel() != rows * cols or wt.shape[1] != cols or wt.dtype != y2.dtype or wt.device != y2.device or not (
+                wt.is_contiguous() or wt.is_contiguous(memory_format=torch.channels_last)):
+            raise RuntimeError('bottleneck_seam: %s must be a dense [%d, %d(, 1, 1)] tensor of y2.dtype' % (name, rows, cols))
+    if skip.shape != (b, c, h, w) or skip.dtype != y2.dtype or skip.device != y2.device or not _channels_last(skip, True) \
+            or not _channels_last(y2, True):
+        raise RuntimeError('bottleneck_seam: y2 and skip must be channels_last, skip [B, %d, H, W] of y2.dtype' % c)
+    if not _bias_vector(b3, c) or not _bias_vector(b1, n):
+        raise RuntimeError('bottleneck_seam: b3 / b1 must be float32 CUDA vectors of length %d / %d' % (c, n))
+    out = torch.empty((b, c, h, w), dtype=y2.dtype, device=y2.device, memory_format=torch.channels_last)
+    z = torch.empty((b, n, h, w), dtype=y2.dtype, device=y2.device, memory_format=torch.channels_last)
+    _launch(library().odtk_bottleneck_seam, 'bottleneck_seam', y2.device, out.data_ptr(), z.data_ptr(), y2.data_ptr(), skip.data_ptr(),
+            w3.data_ptr(), b3.data_ptr(), w1.data_ptr(), b1.data_ptr(), b * h * w, k, c, n, _DTYPES[y2.dtype])
+    _count('bottleneck_seam_kernel', (y2.numel() + skip.numel() + out.numel() + z.numel()) * y2.element_size())
+    return out, z
 
 
 # ---- libodtk_conv.so: k x k convolution with the bias + ReLU in its own epilogue (csrc/conv_ck.cpp) -----------------------------

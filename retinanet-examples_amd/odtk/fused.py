@@ -14,6 +14,9 @@ Measured on MI355X those passes cost more than the convolutions between them.  H
   * 1x1 stride-1 convolutions (two of the three convs of every bottleneck, the FPN laterals) are a
     plain GEMM on the channels_last activation: they run as ONE hipBLASLt call with bias, skip and ReLU
     in the GEMM epilogue (`odtk_gemm_bias_act`, csrc/gemm_lt.hpp) -- no epilogue pass at all;
+  * in layer1 of a bottleneck net the last 1x1 convolution of a block (+ skip + ReLU) and the first 1x1 convolution of the next block
+    run as ONE MFMA pass (`odtk_bottleneck_seam`, csrc/seam.hpp): the 256-channel activation between them is written once and not
+    read back by the GEMM that follows it (DESIGN.md section 5);
   * the head towers of the pyramid levels below P3 run as ONE convolution per layer over a packed canvas with zero gutters
     between the levels (`pyramid_canvas_layout`, `_canvas_towers`; DESIGN.md section 5) instead of one launch per level;
   * the post-processing reads the raw head tensors in place (odtk.box.detect(..., logits=True)); in
@@ -307,12 +310,29 @@ class _Block(nn.Module):
             raise TypeError('unsupported block %r' % type(block))
         self.down = None if block.downsample is None else _Conv(block.downsample[0], block.downsample[1], False, dtype)
 
-    def forward(self, x):
+    def forward(self, x, z=None, seam=None):
+        """z: this block's first convolution, already computed by the block before (its seam call).  seam: the NEXT block's first
+        convolution -- the block then returns (its output, that convolution's output) from one HIP pass (`odtk_bottleneck_seam`,
+        csrc/seam.hpp); where the call fails, from the two GEMMs it stands for."""
         skip = x if self.down is None else self.down(x)
-        y = x
-        for c in self.convs:
+        y = x if z is None else z
+        for c in (self.convs if z is None else self.convs[1:]):
             y = c(y)
-        return self.last(y, skip)                                       # relu(conv + shift + skip), one pass
+        if seam is None:
+            return self.last(y, skip)                                   # relu(conv + shift + skip), one pass
+        try:
+            return _C.bottleneck_seam(y, skip, self.last.weight, self.last.bias, seam.weight, seam.bias)
+        except RuntimeError:
+            out = self.last(y, skip)
+            return out, seam(out)
+
+    def seam_to(self, nxt, dtype):
+        """May this block's last convolution and `nxt`'s first run as one seam call?  64 -> 256 with the skip and a ReLU, then a
+        pointwise stride-1 256 -> 64 | 128 with a ReLU, in a 16-bit dtype (include/odtk_hip.h: odtk_bottleneck_seam)."""
+        last, first = self.last, nxt.convs[0]
+        return (len(self.convs) == 2 and dtype in (torch.bfloat16, torch.float16)
+                and all(c.pointwise and tuple(c.stride) == (1, 1) and c.relu for c in (last, first))
+                and tuple(last.weight.shape[:2]) == (256, 64) and tuple(first.weight.shape[:2]) in ((64, 256), (128, 256)))
 
 
 class FusedRetinaNet(nn.Module):
@@ -353,6 +373,11 @@ class FusedRetinaNet(nn.Module):
         self.stem_learned = False                                       # the last measured stem decision (unplanned geometries follow it)
         self.layers = nn.ModuleList([nn.ModuleList([_Block(b, dtype) for b in layer])
                                      for layer in (net.layer1, net.layer2, net.layer3, net.layer4)])
+        # block -> the block after it, where the last convolution of the one and the first of the other run as one pass
+        # (`_Block.seam_to`: layer1 of a Bottleneck net and its hand-over to layer2); ODTK_SEAM_FUSION=0: two GEMMs each, as before (A/B)
+        blocks = [b for layer in self.layers for b in layer]
+        self._seams = {a: b for a, b in zip(blocks, blocks[1:]) if a.seam_to(b, dtype)}
+        self.seam_fusion = os.environ.get('ODTK_SEAM_FUSION', '1') != '0'
         self.outputs = list(net.outputs)
         self.lateral = nn.ModuleList([_Conv(fpn.lateral3, None, False, dtype), _Conv(fpn.lateral4, None, False, dtype),
                                       _Conv(fpn.lateral5, None, False, dtype)])
@@ -414,9 +439,11 @@ class FusedRetinaNet(nn.Module):
         """x: the network input as the caller has it (the stem owns the cast to the engine's dtype and layout)."""
         x = self._stem(x)
         feats = []
+        z = None
         for level, layer in enumerate(self.layers, start=2):
             for block in layer:
-                x = block(x)
+                nxt = self._seams.get(block) if self.seam_fusion and x.is_cuda else None
+                x, z = block(x, z, nxt.convs[0]) if nxt is not None else (block(x, z), None)
             if level in self.outputs:
                 feats.append(x)
         c3, c4, c5 = feats
@@ -578,7 +605,7 @@ class FusedRetinaNet(nn.Module):
         m = self.model[0]                                                # (post-processing parameters are baked into the launches)
         bias = self.cls_head[-1].bias                                    # its state is baked in too: the prefilter's threshold table
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
-               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, bias.data_ptr(), bias._version,
+               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, self.seam_fusion, bias.data_ptr(), bias._version,
                tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None,     # (the suppression rule is baked in as well,
                getattr(m, 'box_voting', None))                                                               #  and so is box voting)
         if getattr(m, 'tta', None) is not None:
