@@ -675,6 +675,44 @@ int odtk_retina_loss_levels_backward(int n_levels, const odtk_loss_level_t *leve
                                      int num_classes, int box_params, int dtype, float alpha, float gamma, float beta,
                                      const float *grad_cls_sums, const float *grad_box_sums, void *stream);
 
+/*
+ * odtk_box_iou_loss_levels_forward / _backward -- IoU, GIoU or DIoU box-regression loss at the foreground anchors of ALL pyramid
+ * levels of the batch: the opt-in alternative to the smooth-L1 sum above (Model.box_loss, `odtk train --box-loss`), axis-aligned
+ * boxes only.  No reference equivalent; the definition -- the contract -- restated in torch in odtk/loss.py:box_iou_loss:
+ *   one foreground anchor (depth > 0) of anchor slot a, (aw, ah) = (x2 - x1 + 1, y2 - y1 + 1) of the level's anchor table,
+ *   p = the predicted deltas (head dtype -> float32), t = the target deltas; both boxes decoded relative to the anchor centre:
+ *     CLIP = log(1000 / 16);  pw' = min(pw, CLIP), ph' = min(ph, CLIP)       (predictions only; gradient 0 beyond the clip)
+ *     P: centre (px aw, py ah), size (exp(pw') aw, exp(ph') ah)             T: the same from t, unclipped
+ *     inter = max(0, min(Px2, Tx2) - max(Px1, Tx1)) max(0, min(Py2, Ty2) - max(Py1, Ty1))     (corners: centre -+ size / 2)
+ *     union = area(P) + area(T) - inter + eps,  iou = inter / union,  eps = 1e-7;  (ew, eh) = size of the box enclosing both
+ *     ODTK_BOX_LOSS_IOU : L = 1 - iou
+ *     ODTK_BOX_LOSS_GIOU: c = ew eh + eps,         L = 1 - iou + (c - union) / c
+ *     ODTK_BOX_LOSS_DIOU: c2 = ew^2 + eh^2 + eps,  L = 1 - iou + ((Pcx - Tcx)^2 + (Pcy - Tcy)^2) / c2
+ * The level descriptor of the smooth-L1 entry points is reused: `cls` / `dcls` are ignored and may be NULL, box has 4 parameters
+ * per anchor by definition.  `anchors`: HOST array of n_levels pointers to HOST float[4 * num_anchors] (only the sizes are used).
+ *   forward:  sums = DEVICE double[n_levels][2] = (sum of L over the level's foreground anchors, their number), overwritten.  The
+ *             sum is accumulated in float64 in one fixed order (per-workgroup sums in the workspace, added up by a second, tiny
+ *             launch): no atomics, the same bits on every run.  Workspace: two-phase query as everywhere.
+ *   backward: grad_sums = DEVICE float32[n_levels] (NULL = zeros), read on the device; levels[l].dbox receives grad_sums[l] dL/dp
+ *             at the foreground cells and +0 everywhere else -- every element is written -- in the dtype and layout of box,
+ *             rounded once at the store.  At a tie (min / max / clamp, inter = 0, pw = CLIP) the gradient is that of one side.
+ * A NaN delta at a foreground anchor gives a NaN sum; cells that are not foreground are never read from box.  Arithmetic: IEEE
+ * float32 per anchor.  Everything is checked on the host before anything touches HIP.  ODTK_ERR_INVALID: a null pointer,
+ * n_levels outside 1..ODTK_MAX_LEVELS, num_anchors outside 1..ODTK_MAX_ANCHORS, batch_size < 1, a non-positive size, an
+ * undefined kind, an anchor whose width or height is not finite and > 0, a level with batch * A * 4 * H * W >= 2^31, a misaligned
+ * pointer (channels_last: 16 bytes for fp32 heads, 8 for 16-bit ones), a workspace that is too small.  Another dtype is
+ * ODTK_ERR_UNSUPPORTED.  One launch per direction over one lane per anchor cell (csrc/box_iou_loss.hpp), timed under
+ * ODTK_KERNEL_LOSS; the forward's second launch under ODTK_KERNEL_LOSS_REDUCE.
+ */
+#define ODTK_BOX_LOSS_IOU   1
+#define ODTK_BOX_LOSS_GIOU  2
+#define ODTK_BOX_LOSS_DIOU  3
+int odtk_box_iou_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                     int num_anchors, int dtype, int kind, double *sums, void *workspace, size_t workspace_size,
+                                     void *stream);
+int odtk_box_iou_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                      int num_anchors, int dtype, int kind, const float *grad_sums, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (used by bench.py; off by default, zero cost when off).
  * While enabled, a kernel launch of this library carries a hipEvent pair (asynchronous -- still no

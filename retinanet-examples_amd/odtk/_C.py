@@ -35,6 +35,8 @@ MAX_CONCAT_PARTS = 8
 MAX_TILES = 64
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 ATSS_MAX_TOPK = 16
+BOX_LOSS_IOU, BOX_LOSS_GIOU, BOX_LOSS_DIOU = 1, 2, 3
+BOX_LOSS_KINDS = {'iou': BOX_LOSS_IOU, 'giou': BOX_LOSS_GIOU, 'diou': BOX_LOSS_DIOU}
 
 _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
@@ -135,6 +137,10 @@ _SIGNATURES = {
                                            [ctypes.c_float] * 3 + [_vp, _vp, _sz, _vp]),
     'odtk_retina_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel)] + [ctypes.c_int] * 5 +
                                          [ctypes.c_float] * 3 + [_vp, _vp, _vp]),
+    'odtk_box_iou_loss_levels_forward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                         [ctypes.c_int] * 4 + [_vp, _vp, _sz, _vp]),
+    'odtk_box_iou_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                          [ctypes.c_int] * 4 + [_vp, _vp]),
     'odtk_bias_act': (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     'odtk_profile_enable': (ctypes.c_int, [ctypes.c_int]),
     'odtk_debug_set_trace': (ctypes.c_int, [_vp]),
@@ -838,6 +844,80 @@ def retina_loss_levels_backward(cls_heads, box_heads, depths, box_targets, alpha
             float(alpha), float(gamma), float(beta), g_cls.data_ptr() if g_cls is not None else None,
             g_box.data_ptr() if g_box is not None else None)
     return dcls, dbox
+
+
+def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, grads=None):
+    """Validation and level table shared by the IoU-family box losses -> (descriptors, anchor pointers, the ctypes arrays they
+    point into, levels, batch, anchors, dtype enum, kind enum)."""
+    n = len(box_heads)
+    if not (n == len(depths) == len(box_targets) == len(anchors_list)) or n == 0 or n > MAX_LEVELS:
+        raise RuntimeError('%s: need 1..%d levels with matching lists' % (what, MAX_LEVELS))
+    if kind not in BOX_LOSS_KINDS:
+        raise RuntimeError("%s: kind must be 'iou', 'giou' or 'diou', not %r" % (what, kind))
+    arr = (LossLevel * n)()
+    tables = (_fp * n)()
+    keep, geo = [], None
+    for i, (head, depth, target, anchors) in enumerate(zip(box_heads, depths, box_targets, anchors_list)):
+        if not (head.is_cuda and depth.is_cuda and target.is_cuda):
+            raise RuntimeError('%s: tensors must be on the GPU' % what)
+        if head.dim() != 4 or depth.dim() != 5 or target.dim() != 5 or head.dtype not in _DTYPES:
+            raise RuntimeError('%s: box heads must be [B, A*4, H, W] float32 / bfloat16 / float16, depth [B, A, 1, H, W], '
+                               'box_target [B, A, 4, H, W]' % what)
+        b, ch, h, w = head.shape
+        a = target.shape[1]
+        if head.is_contiguous():
+            lay = 0
+        elif head.is_contiguous(memory_format=torch.channels_last):
+            lay = 1
+        else:
+            raise RuntimeError('%s: box heads must be dense NCHW or channels_last' % what)
+        if ch != 4 * a or tuple(depth.shape) != (b, a, 1, h, w) or tuple(target.shape) != (b, a, 4, h, w):
+            raise RuntimeError('%s: inconsistent shapes' % what)
+        if depth.dtype != torch.float32 or target.dtype != torch.float32 or not depth.is_contiguous() or not target.is_contiguous():
+            raise RuntimeError('%s: depth and box_target must be contiguous float32' % what)
+        if geo is None:
+            geo = (b, a, _DTYPES[head.dtype])
+        elif geo != (b, a, _DTYPES[head.dtype]):
+            raise RuntimeError('%s: every level must share batch, anchors and dtype' % what)
+        carr, ln = _anchor_array(anchors.reshape(-1).tolist() if isinstance(anchors, torch.Tensor) else anchors)
+        if ln != 4 * a:
+            raise RuntimeError('%s: every level needs an [A, 4] anchor table' % what)
+        keep.append(carr)
+        tables[i] = ctypes.cast(carr, _fp)
+        arr[i].box, arr[i].depth, arr[i].box_target = head.data_ptr(), depth.data_ptr(), target.data_ptr()
+        arr[i].height, arr[i].width, arr[i].channels_last = h, w, lay
+        if grads is not None:
+            arr[i].dbox = grads[i].data_ptr()
+    return arr, tables, keep, n, geo[0], geo[1], geo[2], BOX_LOSS_KINDS[kind]
+
+
+def box_iou_loss_levels_forward(box_heads, depths, box_targets, anchors_list, kind):
+    """IoU / GIoU / DIoU box loss ('iou' | 'giou' | 'diou') at the foreground anchors of all pyramid levels (csrc/box_iou_loss.hpp)
+    -> float64 CUDA tensor [L, 2] = per level (sum of the losses, #foreground).  anchors_list: per level [A, 4].  Two launches, no
+    atomics: the same bits on every run."""
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('box_iou_loss_levels_forward', box_heads, depths, box_targets,
+                                                              anchors_list, kind)
+    dev = box_heads[0].device
+    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    _enqueue(library().odtk_box_iou_loss_levels_forward, 'box_iou_loss_levels_forward', dev, n, arr, tables, b, a, dtype, code,
+             sums.data_ptr())
+    return sums
+
+
+def box_iou_loss_levels_backward(box_heads, depths, box_targets, anchors_list, kind, grad_sums):
+    """Gradients of sum_l grad_sums[l] * box_sum[l] w.r.t. every box head, in the heads' dtype and layout, ONE launch.
+    grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
+    dev = box_heads[0].device
+    dbox = [torch.empty_like(t) for t in box_heads]
+    for g, t in zip(dbox, box_heads):
+        if g.stride() != t.stride():
+            raise RuntimeError('box_iou_loss_levels_backward: could not allocate gradients in the heads\' layout')
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('box_iou_loss_levels_backward', box_heads, depths, box_targets,
+                                                              anchors_list, kind, dbox)
+    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+    _launch(library().odtk_box_iou_loss_levels_backward, 'box_iou_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
+            g.data_ptr() if g is not None else None)
+    return dbox
 
 
 def retina_loss_forward(cls_head, box_head, depth, box_target, alpha, gamma, beta):

@@ -7,7 +7,12 @@
 (reference model.py:193-209): focal loss, smooth-L1, both masks and the three sums in ONE hand-written HIP
 pass over the head tensors as the convolutions wrote them, and ONE pass in backward (csrc/loss.hpp) -- an
 `autograd.Function`, so it drops into the training graph; the torch modules below stay as the reference
-implementation it is tested against (tests/test_gpu_loss.py) and as the CPU path."""
+implementation it is tested against (tests/test_gpu_loss.py) and as the CPU path.
+
+`box_iou_loss` (IoU / GIoU / DIoU on the boxes the deltas decode to; no reference equivalent) is the opt-in alternative to the
+smooth-L1 box loss (`Model.box_loss`): the definition in torch -- the CPU path and the tests' ground truth -- and
+`fused_pyramid_box_iou_loss`, its HIP form over all pyramid levels (csrc/box_iou_loss.hpp)."""
+import math
 
 import torch
 import torch.nn as nn
@@ -30,6 +35,54 @@ def smooth_l1_loss(pred, target, beta=0.11):
     quadratic = 0.5 * dist ** 2 / beta
     linear = dist - 0.5 * beta
     return torch.where(dist >= beta, linear, quadratic)
+
+
+BOX_LOSS_KINDS = ('iou', 'giou', 'diou')
+BBOX_XFORM_CLIP = math.log(1000.0 / 16)      # Detectron's clip of the predicted log-sizes
+BOX_IOU_EPS = 1e-7
+
+
+def box_iou_loss(pred, target, anchor_sizes, kind):
+    """IoU-family loss of the boxes that predicted and target deltas decode to; per anchor, axis-aligned boxes only.
+
+    pred, target [B, A, 4, H, W] deltas (dx, dy, dw, dh); anchor_sizes [A, 2] = (x2 - x1 + 1, y2 - y1 + 1) of the level's anchor
+    table; kind 'iou' | 'giou' | 'diou' -> [B, A, H, W].  Both boxes are decoded relative to the anchor centre (the cell position
+    cancels), the predicted log-sizes clipped at BBOX_XFORM_CLIP; then torchvision's {,generalized_,distance_}box_iou_loss:
+        iou = inter / (area(P) + area(T) - inter + eps)                L = 1 - iou
+        giou: c = area of the enclosing box + eps                      L = 1 - iou + (c - union) / c
+        diou: c2 = squared diagonal of the enclosing box + eps         L = 1 - iou + |centre(P) - centre(T)|^2 / c2
+    The arithmetic runs in pred's dtype (float64 in: the tests' ground truth)."""
+    if kind not in BOX_LOSS_KINDS:
+        raise ValueError("box_iou_loss: kind must be 'iou', 'giou' or 'diou', not {!r}".format(kind))
+    sizes = torch.as_tensor(anchor_sizes, dtype=pred.dtype, device=pred.device)
+    aw, ah = sizes[:, 0].view(1, -1, 1, 1), sizes[:, 1].view(1, -1, 1, 1)
+
+    def corners(d, clip):
+        dw, dh = (d[:, :, 2].clamp(max=BBOX_XFORM_CLIP), d[:, :, 3].clamp(max=BBOX_XFORM_CLIP)) if clip else (d[:, :, 2], d[:, :, 3])
+        cx, cy, w, h = d[:, :, 0] * aw, d[:, :, 1] * ah, dw.exp() * aw, dh.exp() * ah
+        return cx, cy, w, h, cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h
+
+    pcx, pcy, pw, ph, px1, py1, px2, py2 = corners(pred, True)
+    tcx, tcy, tw, th, tx1, ty1, tx2, ty2 = corners(target.to(pred.dtype), False)
+    inter = (torch.minimum(px2, tx2) - torch.maximum(px1, tx1)).clamp(min=0) * \
+            (torch.minimum(py2, ty2) - torch.maximum(py1, ty1)).clamp(min=0)
+    union = pw * ph + tw * th - inter + BOX_IOU_EPS
+    loss = 1 - inter / union
+    ew = torch.maximum(px2, tx2) - torch.minimum(px1, tx1)
+    eh = torch.maximum(py2, ty2) - torch.minimum(py1, ty1)
+    if kind == 'giou':
+        c = ew * eh + BOX_IOU_EPS
+        loss = loss + (c - union) / c
+    elif kind == 'diou':
+        c2 = ew ** 2 + eh ** 2 + BOX_IOU_EPS
+        loss = loss + ((pcx - tcx) ** 2 + (pcy - tcy) ** 2) / c2
+    return loss
+
+
+def anchor_wh(anchors):
+    """[A, 4] anchor table (x1, y1, x2, y2) -> [A, 2] = (x2 - x1 + 1, y2 - y1 + 1), what `box_iou_loss` decodes with."""
+    anchors = torch.as_tensor(anchors, dtype=torch.float32).reshape(-1, 4)
+    return torch.stack([anchors[:, 2] - anchors[:, 0] + 1, anchors[:, 3] - anchors[:, 1] + 1], 1)
 
 
 class FocalLoss(nn.Module):
@@ -142,3 +195,47 @@ def fused_level_loss(cls_head, box_head, depth, box_target, alpha=0.25, gamma=2.
                                      * (depth > 0)).sum(), (depth > 0).sum()"""
     pair = _as_written_pair(cls_head, box_head)
     return _FusedLevelLoss.apply(pair[0], pair[1], depth.contiguous(), box_target.contiguous(), alpha, gamma, beta)
+
+
+class _FusedPyramidBoxIouLoss(torch.autograd.Function):
+    """(box_heads...) of ALL levels -> (box_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward."""
+
+    @staticmethod
+    def forward(ctx, n, kind, anchors_list, *tensors):
+        from . import _C
+        sums = _C.box_iou_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], anchors_list, kind).float()
+        ctx.save_for_backward(*tensors)
+        ctx.meta = (n, kind, anchors_list)
+        box_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.mark_non_differentiable(foreground)
+        return box_sums, foreground
+
+    @staticmethod
+    def backward(ctx, grad_box_sums, _grad_foreground):
+        from . import _C
+        n, kind, anchors_list = ctx.meta
+        t = ctx.saved_tensors
+        dbox = _C.box_iou_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], anchors_list, kind, grad_box_sums)
+        return (None, None, None) + tuple(dbox) + (None,) * (2 * n)
+
+
+def fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, kind):
+    """`box_iou_loss` masked by `depth > 0` and summed, for every pyramid level at once: per-level (box_sums [L], foreground [L])
+    from the HIP pass of csrc/box_iou_loss.hpp.  box_heads [B, A*4, H, W] as the convolutions wrote them (float32 / bfloat16 /
+    float16, NCHW or channels_last); depths [B, A, 1, H, W] and box_targets [B, A, 4, H, W] float32 from target assignment;
+    anchors_list: per level the [A, 4] anchor table.  Equals, and differentiates like, per level
+
+        (box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(anchors), kind) * (depth[:, :, 0] > 0)).sum()"""
+    from . import _C
+    if kind not in BOX_LOSS_KINDS:
+        raise ValueError("fused_pyramid_box_iou_loss: kind must be 'iou', 'giou' or 'diou', not {!r}".format(kind))
+    if len(box_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
+        groups = [fused_pyramid_box_iou_loss(box_heads[i:i + _C.MAX_LEVELS], depths[i:i + _C.MAX_LEVELS], box_targets[i:i + _C.MAX_LEVELS],
+                                             anchors_list[i:i + _C.MAX_LEVELS], kind)
+                  for i in range(0, len(box_heads), _C.MAX_LEVELS)]
+        return tuple(torch.cat(parts) for parts in zip(*groups))
+    heads = [t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) else t.contiguous() for t in box_heads]
+    n = len(heads)
+    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
+    return _FusedPyramidBoxIouLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
+                                         *[t.contiguous() for t in box_targets])

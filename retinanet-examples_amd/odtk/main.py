@@ -33,6 +33,10 @@ What differs from the reference, and why:
     into image coordinates (one more launch; `--tile-border` drops those that reach into the outermost pixels of an interior tile
     side, where the neighbouring tile sees the object whole) and one suppression sees them all.  Default overlap: a quarter of the
     size.  Axis-aligned boxes only, not together with `--tta`; never stored in a checkpoint.
+  * `--box-loss {smooth-l1,iou,giou,diou}` (train) with `--box-loss-weight value` is new: the box regression is trained with an IoU,
+    GIoU or DIoU loss on the boxes the deltas decode to (odtk/loss.py:box_iou_loss; a HIP pass of its own over the foreground
+    anchors, csrc/box_iou_loss.hpp) instead of the reference's smooth-L1 on the four deltas, times the weight (default 1).
+    Axis-aligned boxes only.  Never stored in a checkpoint: a resumed run has to be given the flags again.
 """
 import argparse
 import os
@@ -129,6 +133,11 @@ TRAIN_FLAGS = [
           'again when resuming', choices=['iou', 'atss']),
     _flag('--atss-topk', int, argparse.SUPPRESS, 'nearest cells per box and pyramid level that ATSS considers, 1..16 (default 9; '
           'needs --assigner atss)', metavar='num'),
+    _flag('--box-loss', str, argparse.SUPPRESS, 'what the box regression is trained with: smooth-l1 on the four deltas (default), or an '
+          'iou / giou / diou loss on the boxes they decode to (not with --rotated-bbox).  Not stored in the checkpoint: give it again '
+          'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou']),
+    _flag('--box-loss-weight', float, argparse.SUPPRESS, 'factor on the box loss, finite and > 0 (default 1; needs --box-loss iou, '
+          'giou or diou)', metavar='value'),
 ]
 INFER_FLAGS = [
     _flag('--images', str, '.', 'image directory', metavar='path'),
@@ -199,6 +208,13 @@ def parse(args):
         parser.error('--atss-topk must be in 1..16')
     if getattr(parsed, 'assigner', 'iou') == 'atss' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--assigner atss is not available with --rotated-bbox')
+    if hasattr(parsed, 'box_loss_weight'):
+        if getattr(parsed, 'box_loss', 'smooth-l1') == 'smooth-l1':
+            parser.error('--box-loss-weight needs --box-loss iou, giou or diou')
+        if not 0 < parsed.box_loss_weight < float('inf'):                         # (a NaN fails both comparisons)
+            parser.error('--box-loss-weight must be finite and > 0')
+    if getattr(parsed, 'box_loss', 'smooth-l1') != 'smooth-l1' and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--box-loss {} is not available with --rotated-bbox'.format(parsed.box_loss))
     return parsed
 
 
@@ -290,6 +306,10 @@ def worker(rank, args, world, spawned=False):
         model.assigner, model.atss_topk = getattr(args, 'assigner', 'iou'), getattr(args, 'atss_topk', 9)
         if model.assigner == 'atss' and args.rotated_bbox:
             raise RuntimeError('--assigner atss is not available for a model with rotated boxes')
+        model.box_loss = getattr(args, 'box_loss', 'smooth-l1').replace('-', '_')
+        model.box_loss_weight = getattr(args, 'box_loss_weight', 1.0)
+        if model.box_loss != 'smooth_l1' and args.rotated_bbox:
+            raise RuntimeError('--box-loss {} is not available for a model with rotated boxes'.format(args.box_loss))
     try:
         if args.command == 'train':
             return train.train(model, state, args.images, args.annotations, args.val_images or args.images,

@@ -27,7 +27,8 @@ import torch.nn as nn
 
 from . import backbones as backbones_mod
 from . import box as box_ops
-from .loss import FocalLoss, SmoothL1Loss, fused_pyramid_loss
+from .loss import (BOX_LOSS_KINDS, FocalLoss, SmoothL1Loss, anchor_wh, box_iou_loss, fused_pyramid_box_iou_loss,
+                   fused_pyramid_loss)
 
 DEFAULT_RATIOS = [1.0, 2.0, 0.5]
 DEFAULT_SCALES = [4 * 2 ** (i / 3) for i in range(3)]
@@ -99,6 +100,11 @@ class Model(nn.Module):
         # boxes only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
         self.assigner = 'iou'
         self.atss_topk = 9
+        # what the box regression is trained with: 'smooth_l1' (the reference's loss on the four deltas) or 'iou' | 'giou' | 'diou' on
+        # the boxes the deltas decode to (odtk/loss.py:box_iou_loss, csrc/box_iou_loss.hpp; axis-aligned boxes only), times
+        # `box_loss_weight` (those three only).  Run-time options like `assigner`: never written into checkpoints
+        self.box_loss = 'smooth_l1'
+        self.box_loss_weight = 1.0
         self.exporting = False
         self.fused_postprocess = True
         self.fused_graph = True                             # eval on a GPU runs the BN-folded engine (odtk/fused.py)
@@ -405,6 +411,16 @@ class Model(nn.Module):
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
         if self.assigner not in ('iou', 'atss'):
             raise ValueError("Model.assigner must be 'iou' or 'atss', not {!r}".format(self.assigner))
+        iou_kind = None
+        if self.box_loss != 'smooth_l1':
+            if self.box_loss not in BOX_LOSS_KINDS:
+                raise ValueError("Model.box_loss must be 'smooth_l1', 'iou', 'giou' or 'diou', not {!r}".format(self.box_loss))
+            if self.rotated_bbox:
+                raise ValueError('Model.box_loss = {!r} is not available for rotated boxes'.format(self.box_loss))
+            weight = self.box_loss_weight
+            if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (math.isfinite(weight) and weight > 0):
+                raise ValueError('Model.box_loss_weight must be finite and > 0, not {!r}'.format(weight))
+            iou_kind = self.box_loss
         atss = None
         if self.assigner == 'atss':
             if self.rotated_bbox:
@@ -438,6 +454,13 @@ class Model(nn.Module):
             cls_sums, box_sums, fg = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
                                                         self.cls_criterion.gamma, self.box_criterion.beta)
             foreground = fg.clamp(min=1).sum()              # per level, as the reference clamps (model.py:196)
+            if iou_kind is not None:
+                # the smooth-L1 sum of the pass above is not used (autograd hands it a zero gradient); the IoU-family loss is a
+                # pass of its own over the foreground anchors (csrc/box_iou_loss.hpp)
+                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+                box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, [self.level_anchors(s) for s in strides],
+                                                         iou_kind)
+                return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
             return cls_sums.sum() / foreground, box_sums.sum() / foreground
         for level, (cls_head, box_head) in enumerate(zip(cls_heads, box_heads)):
             stride = x.shape[-1] / cls_head.shape[-1]
@@ -448,6 +471,12 @@ class Model(nn.Module):
             foreground = foreground + (depth > 0).sum().float().clamp(min=1)
             cls_loss = self.cls_criterion(cls_head.view_as(cls_target).float(), cls_target)
             cls_total = cls_total + (cls_loss * (depth >= 0).expand_as(cls_target).float()).sum()
+            if iou_kind is not None:
+                box_loss = box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)), iou_kind)
+                box_total = box_total + (box_loss * (depth[:, :, 0] > 0).float()).sum()
+                continue
             box_loss = self.box_criterion(box_head.view_as(box_target).float(), box_target)
             box_total = box_total + (box_loss * (depth > 0).expand_as(box_target).float()).sum()
+        if iou_kind is not None:
+            return cls_total / foreground, self.box_loss_weight * box_total / foreground
         return cls_total / foreground, box_total / foreground
