@@ -713,6 +713,39 @@ int odtk_box_iou_loss_levels_forward(int n_levels, const odtk_loss_level_t *leve
 int odtk_box_iou_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                       int num_anchors, int dtype, int kind, const float *grad_sums, void *stream);
 
+/*
+ * odtk_quality_loss_levels_forward / _backward -- Quality Focal Loss (GFL, arXiv 2006.04388 eq. 4) or Varifocal Loss (arXiv
+ * 2008.13367 eq. 2, as mmdetection implements it) over the class logits of ALL pyramid levels of the batch: the opt-in
+ * alternatives to the focal sum of odtk_retina_loss_* (Model.cls_loss, `odtk train --cls-loss`), axis-aligned boxes only.  No
+ * reference equivalent; the definition -- the contract -- restated in torch in odtk/loss.py (quality_focal_loss, varifocal_loss,
+ * box_quality, quality_target):
+ *   x = a class logit (head dtype -> float32), s = sigmoid(x), sp = softplus(x); depth as everywhere (-1 / 0 / class + 1);
+ *   q = 1 - (the ODTK_BOX_LOSS_IOU loss above of the anchor's predicted and target deltas), foreground anchors only: a constant
+ *       of this loss (nothing flows into the box head), NaN where a delta is NaN;
+ *   y = q where depth - 1 == class, else 0; elements of ignored anchors (depth < 0) contribute 0 and get gradient +0;
+ *     ODTK_CLS_LOSS_QFL (gamma >= 1): L = |s - y|^gamma (sp - y x), with y x = 0 where y = 0 whatever the logit
+ *     ODTK_CLS_LOSS_VFL (alpha >= 0): y > 0 (or NaN): L = y (sp - y x);  otherwise: L = alpha s^gamma sp
+ * The level descriptor is reused once more: `dbox` is ignored and may be NULL (d(deltas) is never written); `anchors` as for the
+ * box losses.  Every level shares batch, num_anchors, num_classes and dtype; cls and box share the layout.
+ *   forward:  sums = DEVICE double[n_levels][2] = (sum of L over the elements of non-ignored anchors, number of foreground anchors),
+ *             overwritten; float64 in one fixed order through the workspace (two-phase query as everywhere): the same bits on every run.
+ *   backward: grad_sums = DEVICE float32[n_levels] (NULL = zeros), read on the device; levels[l].dcls receives grad_sums[l] dL/dx,
+ *             every element written, in the dtype and layout of cls, rounded once at the store.
+ * The box head is never read at a cell that is not foreground.  Everything is checked on the host before anything touches HIP.
+ * ODTK_ERR_INVALID: what the box losses refuse, a null or misaligned cls / dcls (16 bytes), num_classes < 1, an undefined kind, a
+ * gamma that is not finite or < 1, an alpha that is not finite or < 0, a level with batch * A * C * H * W >= 2^32.  A workspace
+ * that is too small is ODTK_ERR_WORKSPACE, another dtype ODTK_ERR_UNSUPPORTED.  One streaming launch per direction
+ * (csrc/quality_loss.hpp), timed under ODTK_KERNEL_LOSS; the forward's second launch under ODTK_KERNEL_LOSS_REDUCE.
+ */
+#define ODTK_CLS_LOSS_QFL   1
+#define ODTK_CLS_LOSS_VFL   2
+int odtk_quality_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                     int num_anchors, int num_classes, int dtype, int kind, float alpha, float gamma, double *sums,
+                                     void *workspace, size_t workspace_size, void *stream);
+int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                      int num_anchors, int num_classes, int dtype, int kind, float alpha, float gamma,
+                                      const float *grad_sums, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (used by bench.py; off by default, zero cost when off).
  * While enabled, a kernel launch of this library carries a hipEvent pair (asynchronous -- still no

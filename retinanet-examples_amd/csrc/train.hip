@@ -1,5 +1,6 @@
 // train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels) and the focal + smooth-L1 loss: launch shapes,
-// odtk_debug_loss_*, odtk_retina_loss_*; the IoU-family box losses (odtk_box_iou_loss_levels_*).
+// odtk_debug_loss_*, odtk_retina_loss_*; the IoU-family box losses (odtk_box_iou_loss_levels_*); the quality / varifocal
+// classification losses (odtk_quality_loss_levels_*).
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -9,6 +10,7 @@
 #include "atss.hpp"
 #include "loss.hpp"
 #include "box_iou_loss.hpp"
+#include "quality_loss.hpp"
 
 namespace {
 
@@ -226,6 +228,60 @@ int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_level
   for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) ba.block_begin[l] = static_cast<uint32_t>(total);
   *total_blocks = static_cast<unsigned>(total);                   // <= 6 * 2^29 / 256
   return ODTK_OK;
+}
+
+// The kernel arguments of odtk_quality_loss_levels_* (csrc/quality_loss.hpp): the box side of every level through box_iou_fill (its
+// checks are the box loss's own), then the logits.  Launch shape as the focal walk's: 256 threads, at least
+// two trips per lane where the level is large enough, at most 256 * per_cu workgroups per level -- so a trip's stride stays below
+// 2^21 vectors and the walk's 32-bit vector index cannot wrap.
+int quality_fill(odtk::QualityArgs &qa, bool backward, bool pointers, int n_levels, const odtk_loss_level_t *levels,
+                 const float *const *anchors, int batch, int A, int C, int dtype, int kind, float alpha, float gamma, const float *g,
+                 unsigned *total_blocks) {
+  if (kind != ODTK_CLS_LOSS_QFL && kind != ODTK_CLS_LOSS_VFL) return ODTK_ERR_INVALID;
+  if (!std::isfinite(gamma) || gamma < 1.0f || !std::isfinite(alpha) || alpha < 0.0f || C < 1) return ODTK_ERR_INVALID;
+  odtk::BoxIouArgs ba;
+  unsigned box_blocks = 0;
+  const int rc = box_iou_fill(ba, false, pointers, n_levels, levels, anchors, batch, A, dtype, ODTK_BOX_LOSS_IOU, nullptr, &box_blocks);
+  if (rc != ODTK_OK) return rc;
+  std::memset(&qa, 0, sizeof qa);
+  qa.n_levels = n_levels; qa.num_anchors = A; qa.num_classes = C; qa.kind = kind;
+  qa.alpha = alpha; qa.gamma = gamma;
+  const unsigned per = dtype == ODTK_F32 ? 4u : 8u, unroll = dtype == ODTK_F32 ? 2u : 1u;
+  const unsigned long long cap = 256ull * (backward && dtype == ODTK_F32 ? 8 : 4);
+  unsigned long long total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const odtk_loss_level_t &lv = levels[l];
+    odtk::QualityLevel &ql = qa.lv[l];
+    const unsigned long long n = 1ull * ba.lv[l].cells * C;
+    if (n >= (1ull << 32)) return ODTK_ERR_INVALID;              // the walk indexes the logits with 32 bits
+    if (pointers) {
+      if (!lv.cls || (backward && !lv.dcls)) return ODTK_ERR_INVALID;
+      if ((reinterpret_cast<uintptr_t>(lv.cls) | (backward ? reinterpret_cast<uintptr_t>(lv.dcls) : 0u)) & 15u) return ODTK_ERR_INVALID;   // 16-B vectors
+    }
+    ql.b = ba.lv[l];
+    ql.b.g = (backward && g) ? g + l : nullptr;
+    ql.cls = lv.cls;
+    ql.dcls = backward ? lv.dcls : nullptr;
+    ql.n = static_cast<uint32_t>(n);
+    ql.by_channels = odtk::fastdiv_make(static_cast<uint32_t>(A) * C);
+    ql.by_classes = odtk::fastdiv_make(C);
+    unsigned long long blocks = (n / per + odtk::kQualityThreads * unroll * 2ull - 1) / (odtk::kQualityThreads * unroll * 2ull);
+    if (blocks < 1) blocks = 1;
+    if (blocks > cap) blocks = cap;
+    qa.block_begin[l] = static_cast<uint32_t>(total);
+    total += blocks;
+  }
+  for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) qa.block_begin[l] = static_cast<uint32_t>(total);
+  *total_blocks = static_cast<unsigned>(total);
+  return ODTK_OK;
+}
+
+template <bool kBackward>
+void quality_dispatch(int dtype, const odtk::QualityArgs &qa, unsigned total, hipStream_t stream) {
+  const dim3 grid(total), block(odtk::kQualityThreads);
+  if (dtype == ODTK_F32) timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::F32, kBackward, 2>, grid, block, 0, stream, qa);
+  else if (dtype == ODTK_BF16) timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::BF16, kBackward, 1>, grid, block, 0, stream, qa);
+  else timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::F16, kBackward, 1>, grid, block, 0, stream, qa);
 }
 
 }  // namespace
@@ -535,6 +591,46 @@ int odtk_box_iou_loss_levels_backward(int n_levels, const odtk_loss_level_t *lev
     timed_launch(ODTK_KERNEL_LOSS, odtk::box_iou_loss_backward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
                  static_cast<hipStream_t>(stream), ba);
   });
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_quality_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                     int num_anchors, int num_classes, int dtype, int kind, float alpha, float gamma, double *sums,
+                                     void *workspace, size_t workspace_size, void *stream) {
+  odtk::QualityArgs qa;
+  unsigned total = 0;
+  const int rc = quality_fill(qa, false, workspace != nullptr, n_levels, levels, anchors, batch_size, num_anchors, num_classes, dtype,
+                              kind, alpha, gamma, nullptr, &total);
+  if (rc != ODTK_OK) return rc;
+  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
+  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!sums || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u)) return ODTK_ERR_INVALID;
+  qa.partial = static_cast<double *>(workspace);
+  quality_dispatch<false>(dtype, qa, total, static_cast<hipStream_t>(stream));
+  ODTK_HIP_TRY(hipGetLastError());
+  odtk::BoxIouReduceArgs ra;
+  std::memset(&ra, 0, sizeof ra);
+  ra.partial = qa.partial;
+  ra.sums = sums;
+  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = qa.block_begin[l];
+  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::box_iou_reduce_kernel, dim3(n_levels), dim3(odtk::kBoxIouThreads), 0,
+               static_cast<hipStream_t>(stream), ra);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                      int num_anchors, int num_classes, int dtype, int kind, float alpha, float gamma,
+                                      const float *grad_sums, void *stream) {
+  odtk::QualityArgs qa;
+  unsigned total = 0;
+  const int rc = quality_fill(qa, true, true, n_levels, levels, anchors, batch_size, num_anchors, num_classes, dtype, kind, alpha, gamma,
+                              grad_sums, &total);
+  if (rc != ODTK_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
+  quality_dispatch<true>(dtype, qa, total, static_cast<hipStream_t>(stream));
   ODTK_HIP_TRY(hipGetLastError());
   return ODTK_OK;
 }

@@ -37,6 +37,8 @@ SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 ATSS_MAX_TOPK = 16
 BOX_LOSS_IOU, BOX_LOSS_GIOU, BOX_LOSS_DIOU = 1, 2, 3
 BOX_LOSS_KINDS = {'iou': BOX_LOSS_IOU, 'giou': BOX_LOSS_GIOU, 'diou': BOX_LOSS_DIOU}
+CLS_LOSS_QFL, CLS_LOSS_VFL = 1, 2
+CLS_LOSS_KINDS = {'qfl': CLS_LOSS_QFL, 'vfl': CLS_LOSS_VFL}
 
 _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
@@ -141,6 +143,10 @@ _SIGNATURES = {
                                          [ctypes.c_int] * 4 + [_vp, _vp, _sz, _vp]),
     'odtk_box_iou_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
                                           [ctypes.c_int] * 4 + [_vp, _vp]),
+    'odtk_quality_loss_levels_forward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                         [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [_vp, _vp, _sz, _vp]),
+    'odtk_quality_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                          [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [_vp, _vp]),
     'odtk_bias_act': (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     'odtk_profile_enable': (ctypes.c_int, [ctypes.c_int]),
     'odtk_debug_set_trace': (ctypes.c_int, [_vp]),
@@ -918,6 +924,64 @@ def box_iou_loss_levels_backward(box_heads, depths, box_targets, anchors_list, k
     _launch(library().odtk_box_iou_loss_levels_backward, 'box_iou_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
             g.data_ptr() if g is not None else None)
     return dbox
+
+
+def _quality_levels(what, cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha, gamma, grads=None):
+    """Validation and level table of the quality / varifocal classification losses: the box side as the IoU-family box losses
+    check it, then the logits -> (descriptors, anchor pointers, what they point into, levels, batch, anchors, classes, dtype enum,
+    kind enum)."""
+    if kind not in CLS_LOSS_KINDS:
+        raise RuntimeError("%s: kind must be 'qfl' or 'vfl', not %r" % (what, kind))
+    if not (float(gamma) >= 1 and float(gamma) < float('inf')) or not (float(alpha) >= 0 and float(alpha) < float('inf')):
+        raise RuntimeError('%s: gamma must be finite and >= 1, alpha finite and >= 0 (not %r, %r)' % (what, gamma, alpha))
+    if len(cls_heads) != len(box_heads):
+        raise RuntimeError('%s: need 1..%d levels with matching lists' % (what, MAX_LEVELS))
+    arr, tables, keep, n, b, a, dtype, _ = _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, 'iou')
+    classes = None
+    for i, (cls_head, box_head) in enumerate(zip(cls_heads, box_heads)):
+        lay = _pair_layout(cls_head, box_head, 'cls_head', 'box_head', what + ': ')
+        if cls_head.dtype != box_head.dtype:
+            raise RuntimeError('%s: heads must share one dtype out of float32 / bfloat16 / float16' % what)
+        if cls_head.shape[0] != b or cls_head.shape[1] % a or tuple(cls_head.shape[2:]) != tuple(box_head.shape[2:]):
+            raise RuntimeError('%s: inconsistent shapes' % what)
+        if classes is None:
+            classes = cls_head.shape[1] // a
+        if cls_head.shape[1] != a * classes or classes < 1:
+            raise RuntimeError('%s: every level must share the number of classes' % what)
+        arr[i].cls, arr[i].channels_last = cls_head.data_ptr(), lay
+        if grads is not None:
+            arr[i].dcls = grads[i].data_ptr()
+    return arr, tables, keep, n, b, a, classes, dtype, CLS_LOSS_KINDS[kind]
+
+
+def quality_loss_levels_forward(cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha=0.75, gamma=2.0):
+    """Quality focal ('qfl') or varifocal ('vfl') classification loss over the logits of all pyramid levels (csrc/quality_loss.hpp;
+    the definition: odtk/loss.py) -> float64 CUDA tensor [L, 2] = per level (sum of the losses, #foreground).  The soft target --
+    the IoU of the predicted and the assigned box at every foreground anchor -- is computed in the walk from box_heads / box_targets /
+    anchors_list (per level [A, 4]).  Two launches, no atomics: the same bits on every run."""
+    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels('quality_loss_levels_forward', cls_heads, box_heads, depths, box_targets,
+                                                                 anchors_list, kind, alpha, gamma)
+    dev = cls_heads[0].device
+    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    _enqueue(library().odtk_quality_loss_levels_forward, 'quality_loss_levels_forward', dev, n, arr, tables, b, a, c, dtype, code,
+             float(alpha), float(gamma), sums.data_ptr())
+    return sums
+
+
+def quality_loss_levels_backward(cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha, gamma, grad_sums):
+    """Gradients of sum_l grad_sums[l] * cls_sum[l] w.r.t. every class head, in the heads' dtype and layout, ONE launch (the box
+    heads get none: the quality is a constant of this loss).  grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
+    dev = cls_heads[0].device
+    dcls = [torch.empty_like(t) for t in cls_heads]
+    for g, t in zip(dcls, cls_heads):
+        if g.stride() != t.stride():
+            raise RuntimeError('quality_loss_levels_backward: could not allocate gradients in the heads\' layout')
+    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels('quality_loss_levels_backward', cls_heads, box_heads, depths, box_targets,
+                                                                 anchors_list, kind, alpha, gamma, dcls)
+    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+    _launch(library().odtk_quality_loss_levels_backward, 'quality_loss_levels_backward', dev, n, arr, tables, b, a, c, dtype, code,
+            float(alpha), float(gamma), g.data_ptr() if g is not None else None)
+    return dcls
 
 
 def retina_loss_forward(cls_head, box_head, depth, box_target, alpha, gamma, beta):

@@ -11,7 +11,15 @@ implementation it is tested against (tests/test_gpu_loss.py) and as the CPU path
 
 `box_iou_loss` (IoU / GIoU / DIoU on the boxes the deltas decode to; no reference equivalent) is the opt-in alternative to the
 smooth-L1 box loss (`Model.box_loss`): the definition in torch -- the CPU path and the tests' ground truth -- and
-`fused_pyramid_box_iou_loss`, its HIP form over all pyramid levels (csrc/box_iou_loss.hpp)."""
+`fused_pyramid_box_iou_loss`, its HIP form over all pyramid levels (csrc/box_iou_loss.hpp).
+
+`quality_focal_loss` (GFL) and `varifocal_loss` (VarifocalNet) are the opt-in alternatives to the focal loss (`Model.cls_loss`;
+no reference equivalent): the class score is trained towards a soft target -- at a foreground anchor, for the assigned class,
+`box_quality`, the IoU of the predicted and the assigned box, a constant of the loss; 0 everywhere else (`quality_target`).  The
+definition, per level, with s = sigmoid(x), sp = softplus(x), y the target:
+    qfl: L = |s - y|^gamma (sp - y x)        (y x = 0 where y = 0)        vfl: L = y (sp - y x) where y > 0, else alpha s^gamma sp
+masked by `depth >= 0` and summed.  The torch functions are the CPU / eager path; `fused_pyramid_quality_loss` is the HIP form
+over all pyramid levels (csrc/quality_loss.hpp), which builds neither the quality map nor the target."""
 import math
 
 import torch
@@ -83,6 +91,48 @@ def anchor_wh(anchors):
     """[A, 4] anchor table (x1, y1, x2, y2) -> [A, 2] = (x2 - x1 + 1, y2 - y1 + 1), what `box_iou_loss` decodes with."""
     anchors = torch.as_tensor(anchors, dtype=torch.float32).reshape(-1, 4)
     return torch.stack([anchors[:, 2] - anchors[:, 0] + 1, anchors[:, 3] - anchors[:, 1] + 1], 1)
+
+
+CLS_LOSS_KINDS = ('qfl', 'vfl')
+
+
+def box_quality(pred, target, anchor_sizes):
+    """The localisation quality the class score is trained towards under `Model.cls_loss = 'qfl' | 'vfl'`: the IoU of the boxes that
+    predicted and target deltas decode to, as `1 - box_iou_loss(pred, target, anchor_sizes, 'iou')` -- the same clip, eps and
+    decoding; [B, A, 4, H, W] twice -> [B, A, H, W] in [0, 1] (identical boxes: within a few ulp of 1; it is not clamped, so that it
+    stays the box loss's own number), NaN where a delta is NaN.  Meaningful at foreground anchors only."""
+    return 1 - box_iou_loss(pred, target, anchor_sizes, 'iou')
+
+
+def quality_target(depth, quality, classes):
+    """The soft class target y of the eager path: depth [B, A, 1, H, W] (-1 ignore / 0 background / class + 1), quality
+    [B, A, H, W] -> [B, A, classes, H, W] with y = quality where depth - 1 == class and 0 everywhere else."""
+    cls_index = torch.arange(classes, device=depth.device, dtype=depth.dtype).view(1, 1, -1, 1, 1)
+    return torch.where(depth - 1 == cls_index, quality.unsqueeze(2), torch.zeros((), dtype=quality.dtype, device=quality.device))
+
+
+def _softplus(x):
+    """log(1 + exp(x)) without overflow, 0 at -inf, with sigmoid(x) as its gradient (F.softplus switches to x beyond a threshold,
+    2e-9 off in float64)."""
+    return torch.logaddexp(x, torch.zeros_like(x))
+
+
+def quality_focal_loss(logits, quality_target, gamma=2.0):
+    """Quality Focal Loss (GFL, arXiv 2006.04388, eq. 4), per element: |sigmoid(x) - y|^gamma (softplus(x) - y x), the binary cross
+    entropy against the soft target y in [0, 1] scaled by the distance to it; gamma >= 1.  For y = 0 it is sigmoid(x)^gamma
+    softplus(x) (y x counts as 0 there even for an infinite logit); for y in {0, 1} twice `focal_loss` with alpha = 0.5.  The arithmetic runs in the logits' dtype."""
+    y = quality_target.to(logits.dtype)
+    yx = torch.where(y == 0, torch.zeros((), dtype=logits.dtype, device=logits.device), y * logits)      # 0 * -inf is 0 here
+    return (torch.sigmoid(logits) - y).abs() ** gamma * (_softplus(logits) - yx)
+
+
+def varifocal_loss(logits, quality_target, alpha=0.75, gamma=2.0):
+    """Varifocal Loss (VarifocalNet, arXiv 2008.13367, eq. 2, as mmdetection implements it), per element: y (softplus(x) - y x)
+    where y > 0, the focal negative term alpha sigmoid(x)^gamma softplus(x) where y <= 0 (also a foreground anchor whose predicted
+    box misses its target entirely).  A NaN y takes the first form, so it reaches the sum.  The arithmetic runs in the logits' dtype."""
+    y = quality_target.to(logits.dtype)
+    softplus = _softplus(logits)
+    return torch.where(y <= 0, alpha * torch.sigmoid(logits) ** gamma * softplus, y * (softplus - y * logits))
 
 
 class FocalLoss(nn.Module):
@@ -239,3 +289,55 @@ def fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, kin
     tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
     return _FusedPyramidBoxIouLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
                                          *[t.contiguous() for t in box_targets])
+
+
+class _FusedPyramidQualityLoss(torch.autograd.Function):
+    """(cls_heads...) of ALL levels -> (cls_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward.
+    The box heads are inputs without a gradient: the quality is a constant of this loss."""
+
+    @staticmethod
+    def forward(ctx, n, kind, alpha, gamma, anchors_list, *tensors):
+        from . import _C
+        sums = _C.quality_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], tensors[3 * n:4 * n], anchors_list,
+                                              kind, alpha, gamma).float()
+        ctx.save_for_backward(*tensors)
+        ctx.meta = (n, kind, alpha, gamma, anchors_list)
+        cls_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.mark_non_differentiable(foreground)
+        return cls_sums, foreground
+
+    @staticmethod
+    def backward(ctx, grad_cls_sums, _grad_foreground):
+        from . import _C
+        n, kind, alpha, gamma, anchors_list = ctx.meta
+        t = ctx.saved_tensors
+        dcls = _C.quality_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n], anchors_list, kind, alpha, gamma,
+                                               grad_cls_sums)
+        return (None, None, None, None, None) + tuple(dcls) + (None,) * (3 * n)
+
+
+def fused_pyramid_quality_loss(cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha=0.75, gamma=2.0):
+    """`quality_focal_loss` ('qfl') or `varifocal_loss` ('vfl') against the soft target, masked by `depth >= 0` and summed, for every
+    pyramid level at once: per-level (cls_sums [L], foreground [L]) from the HIP pass of csrc/quality_loss.hpp.  cls_heads
+    [B, A*C, H, W] and box_heads [B, A*4, H, W] as the convolutions wrote them (float32 / bfloat16 / float16, NCHW or channels_last);
+    depths [B, A, 1, H, W] and box_targets [B, A, 4, H, W] float32 from target assignment; anchors_list: per level the [A, 4] anchor
+    table.  `alpha` is varifocal's only.  Equals, and differentiates like, per level
+
+        q = box_quality(box_head.view_as(box_target).float(), box_target, anchor_wh(anchors)).detach()
+        (loss(cls_head.view(B, A, C, H, W).float(), quality_target(depth, q, C)) * (depth >= 0)).sum(), (depth > 0).sum()
+
+    with no gradient into the box heads; neither the quality map nor the target is ever built."""
+    from . import _C
+    if kind not in CLS_LOSS_KINDS:
+        raise ValueError("fused_pyramid_quality_loss: kind must be 'qfl' or 'vfl', not {!r}".format(kind))
+    if len(cls_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
+        m = _C.MAX_LEVELS
+        groups = [fused_pyramid_quality_loss(cls_heads[i:i + m], box_heads[i:i + m], depths[i:i + m], box_targets[i:i + m],
+                                             anchors_list[i:i + m], kind, alpha, gamma)
+                  for i in range(0, len(cls_heads), m)]
+        return tuple(torch.cat(parts) for parts in zip(*groups))
+    pairs = [_as_written_pair(c, b.detach()) for c, b in zip(cls_heads, box_heads)]
+    n = len(pairs)
+    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
+    return _FusedPyramidQualityLoss.apply(n, kind, float(alpha), float(gamma), tables, *[p[0] for p in pairs], *[p[1] for p in pairs],
+                                          *[d.contiguous() for d in depths], *[t.contiguous() for t in box_targets])

@@ -37,6 +37,11 @@ What differs from the reference, and why:
     GIoU or DIoU loss on the boxes the deltas decode to (odtk/loss.py:box_iou_loss; a HIP pass of its own over the foreground
     anchors, csrc/box_iou_loss.hpp) instead of the reference's smooth-L1 on the four deltas, times the weight (default 1).
     Axis-aligned boxes only.  Never stored in a checkpoint: a resumed run has to be given the flags again.
+  * `--cls-loss {focal,qfl,vfl}` (train) is new: the class scores are trained as localisation-quality estimates, with the quality
+    focal loss (GFL) or the varifocal loss (VarifocalNet) on a soft target -- at a foreground anchor the IoU of the box the network
+    predicts there and the box it was assigned (odtk/loss.py:quality_focal_loss / varifocal_loss; a HIP pass over the logits that
+    computes the target in place, csrc/quality_loss.hpp) -- instead of the reference's focal loss on a one-hot target.  Inference
+    is unchanged.  Axis-aligned boxes only.  Never stored in a checkpoint: a resumed run has to be given the flag again.
 """
 import argparse
 import os
@@ -138,6 +143,9 @@ TRAIN_FLAGS = [
           'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou']),
     _flag('--box-loss-weight', float, argparse.SUPPRESS, 'factor on the box loss, finite and > 0 (default 1; needs --box-loss iou, '
           'giou or diou)', metavar='value'),
+    _flag('--cls-loss', str, argparse.SUPPRESS, 'what the class scores are trained with: focal on the one-hot target (default), or the '
+          'quality focal (qfl) / varifocal (vfl) loss on the IoU of the predicted and the assigned box (not with --rotated-bbox).  Not '
+          'stored in the checkpoint: give it again when resuming', choices=['focal', 'qfl', 'vfl']),
 ]
 INFER_FLAGS = [
     _flag('--images', str, '.', 'image directory', metavar='path'),
@@ -215,6 +223,8 @@ def parse(args):
             parser.error('--box-loss-weight must be finite and > 0')
     if getattr(parsed, 'box_loss', 'smooth-l1') != 'smooth-l1' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--box-loss {} is not available with --rotated-bbox'.format(parsed.box_loss))
+    if getattr(parsed, 'cls_loss', 'focal') != 'focal' and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--cls-loss {} is not available with --rotated-bbox'.format(parsed.cls_loss))
     return parsed
 
 
@@ -310,6 +320,9 @@ def worker(rank, args, world, spawned=False):
         model.box_loss_weight = getattr(args, 'box_loss_weight', 1.0)
         if model.box_loss != 'smooth_l1' and args.rotated_bbox:
             raise RuntimeError('--box-loss {} is not available for a model with rotated boxes'.format(args.box_loss))
+        model.cls_loss = getattr(args, 'cls_loss', 'focal')
+        if model.cls_loss != 'focal' and args.rotated_bbox:
+            raise RuntimeError('--cls-loss {} is not available for a model with rotated boxes'.format(args.cls_loss))
     try:
         if args.command == 'train':
             return train.train(model, state, args.images, args.annotations, args.val_images or args.images,

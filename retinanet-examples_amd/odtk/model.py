@@ -27,8 +27,9 @@ import torch.nn as nn
 
 from . import backbones as backbones_mod
 from . import box as box_ops
-from .loss import (BOX_LOSS_KINDS, FocalLoss, SmoothL1Loss, anchor_wh, box_iou_loss, fused_pyramid_box_iou_loss,
-                   fused_pyramid_loss)
+from .loss import (BOX_LOSS_KINDS, CLS_LOSS_KINDS, FocalLoss, SmoothL1Loss, anchor_wh, box_iou_loss, box_quality,
+                   fused_pyramid_box_iou_loss, fused_pyramid_loss, fused_pyramid_quality_loss, quality_focal_loss, quality_target,
+                   varifocal_loss)
 
 DEFAULT_RATIOS = [1.0, 2.0, 0.5]
 DEFAULT_SCALES = [4 * 2 ** (i / 3) for i in range(3)]
@@ -105,6 +106,11 @@ class Model(nn.Module):
         # `box_loss_weight` (those three only).  Run-time options like `assigner`: never written into checkpoints
         self.box_loss = 'smooth_l1'
         self.box_loss_weight = 1.0
+        # what the class scores are trained with: 'focal' (the reference's loss on a one-hot target) or 'qfl' | 'vfl', the quality
+        # focal and varifocal losses on a soft target -- at a foreground anchor the IoU of the predicted and the assigned box
+        # (odtk/loss.py:quality_focal_loss / varifocal_loss, csrc/quality_loss.hpp; axis-aligned boxes only).  A run-time option like
+        # `box_loss`: never written into checkpoints
+        self.cls_loss = 'focal'
         self.exporting = False
         self.fused_postprocess = True
         self.fused_graph = True                             # eval on a GPU runs the BN-folded engine (odtk/fused.py)
@@ -407,7 +413,12 @@ class Model(nn.Module):
 
     def _compute_loss(self, x, cls_heads, box_heads, targets):
         """Focal + smooth-L1 losses summed over levels and normalised by the number of foreground
-        anchors (reference model.py:186-210); `depth` is -1 ignore / 0 background / class+1."""
+        anchors (reference model.py:186-210); `depth` is -1 ignore / 0 background / class+1.
+
+        `cls_loss = 'qfl' | 'vfl'` replaces the focal term by the quality focal / varifocal loss on the soft target (odtk/loss.py),
+        normalised in the same way.  On the fused path the quality pass then supplies the classification sums and the foreground
+        count; `fused_pyramid_loss` is called only while `box_loss` is 'smooth_l1', for its box sum -- its classification half goes
+        unused, as its box half does under an IoU-family `box_loss`."""
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
         if self.assigner not in ('iou', 'atss'):
             raise ValueError("Model.assigner must be 'iou' or 'atss', not {!r}".format(self.assigner))
@@ -421,6 +432,13 @@ class Model(nn.Module):
             if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (math.isfinite(weight) and weight > 0):
                 raise ValueError('Model.box_loss_weight must be finite and > 0, not {!r}'.format(weight))
             iou_kind = self.box_loss
+        quality_kind = None
+        if self.cls_loss != 'focal':
+            if self.cls_loss not in CLS_LOSS_KINDS:
+                raise ValueError("Model.cls_loss must be 'focal', 'qfl' or 'vfl', not {!r}".format(self.cls_loss))
+            if self.rotated_bbox:
+                raise ValueError('Model.cls_loss = {!r} is not available for rotated boxes'.format(self.cls_loss))
+            quality_kind = self.cls_loss
         atss = None
         if self.assigner == 'atss':
             if self.rotated_bbox:
@@ -451,6 +469,21 @@ class Model(nn.Module):
                     _, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:], False)
                     depths.append(depth)
                     box_targets.append(box_target)
+            if quality_kind is not None:
+                # the quality pass (csrc/quality_loss.hpp) supplies the classification sums and the foreground count.  With an
+                # IoU-family box loss the focal + smooth-L1 pass is not called at all: nothing streams the logits twice.  With
+                # smooth-L1 it still runs for its box sum; its classification half goes unused (autograd hands it a zero
+                # gradient), as its box half does under `box_loss`
+                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+                anchors_list = [self.level_anchors(s) for s in strides]
+                cls_sums, fg = fused_pyramid_quality_loss(cls_heads, box_heads, depths, box_targets, anchors_list, quality_kind)
+                foreground = fg.clamp(min=1).sum()
+                if iou_kind is not None:
+                    box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, iou_kind)
+                    return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
+                _, box_sums, _ = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
+                                                    self.cls_criterion.gamma, self.box_criterion.beta)
+                return cls_sums.sum() / foreground, box_sums.sum() / foreground
             cls_sums, box_sums, fg = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
                                                         self.cls_criterion.gamma, self.box_criterion.beta)
             foreground = fg.clamp(min=1).sum()              # per level, as the reference clamps (model.py:196)
@@ -469,7 +502,14 @@ class Model(nn.Module):
             else:
                 cls_target, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:])
             foreground = foreground + (depth > 0).sum().float().clamp(min=1)
-            cls_loss = self.cls_criterion(cls_head.view_as(cls_target).float(), cls_target)
+            if quality_kind is not None:
+                # the soft target: the IoU of the predicted and the assigned box at the anchor's class, a constant of this loss
+                quality = box_quality(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride))).detach()
+                soft = quality_target(depth, quality, cls_target.shape[2])
+                criterion = quality_focal_loss if quality_kind == 'qfl' else varifocal_loss
+                cls_loss = criterion(cls_head.view_as(cls_target).float(), soft)
+            else:
+                cls_loss = self.cls_criterion(cls_head.view_as(cls_target).float(), cls_target)
             cls_total = cls_total + (cls_loss * (depth >= 0).expand_as(cls_target).float()).sum()
             if iou_kind is not None:
                 box_loss = box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)), iou_kind)
