@@ -596,6 +596,33 @@ int odtk_atss_assign_levels(int batch_size, const float *targets, int n_max, int
                             void *workspace, size_t workspace_size, void *stream);
 
 /*
+ * odtk_tal_assign_levels -- task-aligned target assignment (TOOD, Feng et al., ICCV 2021; the assigner of PP-YOLOE and YOLOv8) for
+ * all pyramid levels of the batch: the assigner that looks at what the network predicts, axis-aligned boxes only.  No reference
+ * equivalent; the definition -- the contract -- is spelled out in csrc/tal.hpp and restated in numpy in tests/tal_ref.py:
+ *   a row is valid when its class is a whole number in 0..num_classes-1; its candidates are all anchors whose cell centre lies more
+ *   than 0.01 inside the box; m = s^alpha * u^beta by repeated float32 multiplication, s the sigmoid of the logit of the row's class
+ *   at the anchor, u the IoU of the box the deltas decode to there (no clamp to the image) with the row's box; the row selects its
+ *   `topk` candidates with the largest m over all levels together (NaN never, 0 eligible; ties: the lower global anchor index); an
+ *   anchor selected by several rows goes to the largest u (ties: the earliest row).
+ * `levels` (anchors, outputs, H, W, stride) as for ATSS; `heads` gives per level the class logits [batch, A*C, H, W] and box deltas
+ * [batch, A*4, H, W] of element type `dtype`, as the convolutions wrote them (cls, box, channels_last; every other field is
+ * ignored).  topk in 1..ODTK_ATSS_MAX_TOPK, alpha in 0..4, beta in 1..8.  depth is class + 1 or 0 -- no ignore band -- and every
+ * element of every output is written by this call.  n_max == 0 or only padding rows: all outputs zero.
+ * Three launches (one workgroup per target row: a streaming top-k selection into the workspace; zeros to the outputs; one thread
+ * per selected entry: conflicts and the winners' targets), no atomics, timed under ODTK_KERNEL_ATSS_STATS (the selection) and
+ * ODTK_KERNEL_TARGETS.  Workspace: 144 bytes per target row (two-phase query); too small: ODTK_ERR_WORKSPACE.
+ * ODTK_ERR_INVALID: null pointers (cls_target excepted), n_levels outside 1..ODTK_MAX_LEVELS, num_anchors outside
+ * 1..ODTK_MAX_ANCHORS, topk, alpha or beta out of range, num_classes < 1, non-positive sizes or strides, batch_size outside
+ * 1..65535, a level or a total anchor count beyond 2^31 - 1, heads misaligned for their element.  Another dtype:
+ * ODTK_ERR_UNSUPPORTED.  Everything is checked on the host before anything is enqueued.
+ */
+struct odtk_loss_level;
+int odtk_tal_assign_levels(int batch_size, const float *targets, int n_max, int n_levels,
+                           const odtk_snap_level_t *levels, const struct odtk_loss_level *heads,
+                           int num_anchors, int num_classes, int dtype, int topk, int alpha, int beta,
+                           void *workspace, size_t workspace_size, void *stream);
+
+/*
  * odtk_snap_to_anchors_rotated_levels -- the same assignment for ROTATED boxes (reference odtk/box.py:192-252, whose overlap is
  * the pairwise polygon IoU csrc/cuda/nms_iou.cu:324-387), all pyramid levels of the batch in ONE launch: no [27*H*W, N] IoU
  * matrix, no per-image host loop.  The ground truth arrives as the reference's `rotate_boxes` leaves it (utils.py:33-82):

@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images` and `merge_tile_candidates`.  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images`, `merge_tile_candidates` and `tal_assign_levels`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -330,6 +330,62 @@ std::vector<torch::Tensor> detect(std::vector<torch::Tensor> cls_heads, std::vec
   return {scores, boxes, classes};
 }
 
+// task-aligned target assignment (odtk_tal_assign_levels: no reference equivalent), the signature of odtk/_C.py:tal_assign_levels.
+// The heads are taken as the convolutions wrote them: one dtype out of float32 / bfloat16 / float16, NCHW or channels_last.
+std::vector<std::vector<std::optional<torch::Tensor>>> tal_assign_levels(torch::Tensor targets, std::vector<torch::Tensor> cls_heads,
+                                                                         std::vector<torch::Tensor> box_heads,
+                                                                         std::vector<std::vector<float>> anchors, int num_classes,
+                                                                         std::vector<int> strides, int topk, int alpha, int beta,
+                                                                         bool want_cls_target) {
+  require_gpu_contiguous(targets, "targets");
+  TORCH_CHECK(targets.dim() == 3 && targets.size(2) == 5, "targets must be [B, N, 5]");
+  const size_t n = cls_heads.size();
+  TORCH_CHECK(n >= 1 && n <= ODTK_MAX_LEVELS && box_heads.size() == n && anchors.size() == n && strides.size() == n,
+              "tal_assign_levels: need 1..", ODTK_MAX_LEVELS, " levels with matching lists");
+  const auto dtype = cls_heads[0].scalar_type();
+  const int dt = dtype == torch::kFloat32 ? ODTK_F32 : dtype == torch::kBFloat16 ? ODTK_BF16 : dtype == torch::kFloat16 ? ODTK_F16 : -1;
+  TORCH_CHECK(dt >= 0, "tal_assign_levels: heads must be float32 / bfloat16 / float16");
+  const int64_t batch = targets.size(0);
+  const int num_anchors = static_cast<int>(anchors[0].size() / 4);
+  TORCH_CHECK(num_anchors >= 1 && num_classes >= 1, "tal_assign_levels: need anchors and classes");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(targets.device());
+  auto opt = targets.options();
+  std::vector<odtk_snap_level_t> levels(n);
+  std::vector<odtk_loss_level_t> heads(n);
+  std::vector<std::vector<std::optional<torch::Tensor>>> out(3);
+  for (size_t i = 0; i < n; ++i) {
+    const auto &c = cls_heads[i], &b = box_heads[i];
+    TORCH_CHECK(c.is_cuda() && b.is_cuda() && c.dim() == 4 && b.dim() == 4 && c.scalar_type() == dtype && b.scalar_type() == dtype,
+                "tal_assign_levels: level ", i, ": CUDA 4-d tensors of one dtype expected");
+    const bool c_nchw = c.is_contiguous(), c_nhwc = c.is_contiguous(at::MemoryFormat::ChannelsLast);
+    const bool b_nchw = b.is_contiguous(), b_nhwc = b.is_contiguous(at::MemoryFormat::ChannelsLast);
+    TORCH_CHECK(c_nchw || c_nhwc, "cls_head[", i, "] must be contiguous (NCHW or channels_last)");
+    TORCH_CHECK((c_nchw && b_nchw) || (c_nhwc && b_nhwc), "box_head[", i, "] must share cls_head's memory format");
+    const int64_t h = c.size(2), w = c.size(3);
+    TORCH_CHECK(static_cast<int>(anchors[i].size()) == 4 * num_anchors && c.size(0) == batch && b.size(0) == batch &&
+                c.size(1) == static_cast<int64_t>(num_anchors) * num_classes && b.size(1) == static_cast<int64_t>(num_anchors) * 4 &&
+                b.size(2) == h && b.size(3) == w, "tal_assign_levels: inconsistent level ", i);
+    out[0].push_back(want_cls_target ? std::optional<torch::Tensor>(torch::empty({batch, num_anchors, num_classes, h, w}, opt)) : std::nullopt);
+    out[1].push_back(torch::empty({batch, num_anchors, 4, h, w}, opt));
+    out[2].push_back(torch::empty({batch, num_anchors, 1, h, w}, opt));
+    levels[i] = odtk_snap_level_t{anchors[i].data(), want_cls_target ? static_cast<float *>(out[0][i]->data_ptr()) : nullptr,
+                                  static_cast<float *>(out[1][i]->data_ptr()), static_cast<float *>(out[2][i]->data_ptr()),
+                                  static_cast<int32_t>(h), static_cast<int32_t>(w), strides[i], 0};
+    heads[i] = odtk_loss_level_t{c.data_ptr(), b.data_ptr(), nullptr, nullptr, nullptr, nullptr, static_cast<int32_t>(h),
+                                 static_cast<int32_t>(w), (c_nchw && b_nchw) ? 0 : 1, 0};
+  }
+  void *stream = current_stream(targets);
+  {
+    pybind11::gil_scoped_release nogil;
+    with_scratch(targets, "tal_assign_levels", [&](void *ws, size_t size) {
+      return odtk_tal_assign_levels(static_cast<int>(batch), static_cast<const float *>(targets.data_ptr()), static_cast<int>(targets.size(1)),
+                                    static_cast<int>(n), levels.data(), heads.data(), num_anchors, num_classes, dt, topk, alpha, beta, ws, size,
+                                    ws ? stream : nullptr);
+    });
+  }
+  return out;
+}
+
 struct Engine {};   // csrc/engine.h: the TensorRT engine class -- not available on MI355X (BASELINE.json north_star)
 
 }  // namespace
@@ -367,6 +423,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("iou", &iou, py::arg("boxes"), py::arg("anchors"));
   m.def("detect", &detect, py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors"), py::arg("strides"), py::arg("score_thresh"),
         py::arg("top_n"), py::arg("nms_thresh"), py::arg("detections_per_im"), py::arg("rotated") = false, py::arg("logits") = false);
+  m.def("tal_assign_levels", &tal_assign_levels, py::arg("targets"), py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors_list"),
+        py::arg("num_classes"), py::arg("strides"), py::arg("topk") = 13, py::arg("alpha") = 1, py::arg("beta") = 6,
+        py::arg("want_cls_target") = true);
   m.def("version", [] { return std::string(odtk_version()); });
   // sizes of the ABI structs THIS module was compiled against: a module older than include/odtk_hip.h passes arrays of the
   // wrong stride (tests/test_compiled_binding.py compares them with the ctypes mirror on every CPU run)

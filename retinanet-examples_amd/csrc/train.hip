@@ -1,4 +1,4 @@
-// train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels) and the focal + smooth-L1 loss: launch shapes,
+// train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels, odtk_tal_assign_levels) and the focal + smooth-L1 loss: launch shapes,
 // odtk_debug_loss_*, odtk_retina_loss_*; the IoU-family box losses (odtk_box_iou_loss_levels_*); the quality / varifocal
 // classification losses (odtk_quality_loss_levels_*).
 #include <cmath>
@@ -8,6 +8,7 @@
 #include "runtime.hpp"
 #include "targets.hpp"
 #include "atss.hpp"
+#include "tal.hpp"
 #include "loss.hpp"
 #include "box_iou_loss.hpp"
 #include "quality_loss.hpp"
@@ -489,6 +490,101 @@ int odtk_atss_assign_levels(int batch_size, const float *targets, int n_max, int
   timed_launch(ODTK_KERNEL_TARGETS, odtk::atss_assign_kernel, dim3(static_cast<unsigned>(total), batch_size), dim3(odtk::kAtssThreads), 0,
                static_cast<hipStream_t>(stream), aa);
   ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_tal_assign_levels(int batch_size, const float *targets, int n_max, int n_levels, const odtk_snap_level_t *levels,
+                           const odtk_loss_level_t *heads, int num_anchors, int num_classes, int dtype, int topk, int alpha, int beta,
+                           void *workspace, size_t workspace_size, void *stream) {
+  // grid.y carries the image in the selection and the scatter
+  if (batch_size <= 0 || batch_size > 65535 || n_max < 0 || n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || num_anchors <= 0 ||
+      num_anchors > ODTK_MAX_ANCHORS || num_classes < 1 || topk < 1 || topk > ODTK_ATSS_MAX_TOPK || alpha < 0 || alpha > 4 || beta < 1 ||
+      beta > 8)
+    return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const unsigned long long rows = 1ull * batch_size * n_max;                  // one record per image and target row
+  if (rows * sizeof(odtk::TalRecord) > 0x7fffff00ull) return ODTK_ERR_INVALID;        // the size query answers in an int
+  const size_t need = align_up(rows ? rows * sizeof(odtk::TalRecord) : 1);
+  if (!workspace) return static_cast<int>(need);                                      // two-phase convention of the reference's plugins
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!levels || !heads || (n_max > 0 && !targets) || (reinterpret_cast<uintptr_t>(workspace) & 15u) ||
+      (reinterpret_cast<uintptr_t>(targets) & 3u))
+    return ODTK_ERR_INVALID;
+  odtk::TalArgs ta;
+  odtk::TalFillArgs fa;
+  std::memset(&ta, 0, sizeof ta);
+  std::memset(&fa, 0, sizeof fa);
+  ta.targets = targets;
+  ta.records = static_cast<odtk::TalRecord *>(workspace);
+  ta.n_levels = n_levels;
+  ta.n_max = n_max;
+  ta.num_anchors = num_anchors;
+  ta.num_classes = num_classes;
+  ta.topk = topk;
+  ta.alpha = alpha;
+  ta.beta = beta;
+  const uintptr_t element = dtype == ODTK_F32 ? 3u : 1u;
+  unsigned long long anchors_total = 0, fill_blocks = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const odtk_snap_level_t &lv = levels[l];
+    const odtk_loss_level_t &hd = heads[l];
+    if (!lv.anchors || !lv.box_target || !lv.depth || !hd.cls || !hd.box || lv.height <= 0 || lv.width <= 0 || lv.stride <= 0 ||
+        (hd.channels_last != 0 && hd.channels_last != 1))
+      return ODTK_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(hd.cls) | reinterpret_cast<uintptr_t>(hd.box)) & element) return ODTK_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(lv.box_target) | reinterpret_cast<uintptr_t>(lv.depth) | reinterpret_cast<uintptr_t>(lv.cls_target)) & 3u)
+      return ODTK_ERR_INVALID;
+    const unsigned long long pixels = 1ull * lv.height * lv.width;
+    if (pixels > 0x7fffffffull || pixels * num_anchors > 0x7fffffffull) return ODTK_ERR_INVALID;   // the kernels index a level's anchors with 32 bits
+    const unsigned long long cells = pixels * num_anchors;
+    odtk::TalLevel &tl = ta.lv[l];
+    tl.cls = hd.cls;
+    tl.box = hd.box;
+    tl.cls_target = lv.cls_target;
+    tl.box_target = lv.box_target;
+    tl.depth = lv.depth;
+    tl.height = lv.height;
+    tl.width = lv.width;
+    tl.stride = static_cast<float>(lv.stride);
+    tl.channels_last = hd.channels_last;
+    tl.base = static_cast<uint32_t>(anchors_total);
+    std::memcpy(tl.anchors, lv.anchors, sizeof(float) * 4 * num_anchors);
+    anchors_total += cells;
+    if (anchors_total > 0x7fffffffull) return ODTK_ERR_INVALID;                       // g, the global anchor index, has 31 bits
+    // the fill: depth, box_target and cls_target of the level, at most four vectors per lane and 4096 workgroups per segment
+    float *const out[3] = {lv.depth, lv.box_target, lv.cls_target};
+    const unsigned long long per[3] = {1ull, 4ull, static_cast<unsigned long long>(num_classes)};
+    for (int k = 0; k < 3; ++k) {
+      if (!out[k]) continue;
+      if (per[k] > (1ull << 62) / (batch_size * cells)) return ODTK_ERR_INVALID;      // an output no address space holds
+      const unsigned long long count = batch_size * cells * per[k];
+      unsigned long long blocks = (count / 4 + 4ull * odtk::kTalFillThreads - 1) / (4ull * odtk::kTalFillThreads);
+      blocks = blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks;
+      fa.ptr[fa.n_segments] = out[k];
+      fa.count[fa.n_segments] = count;
+      fa.block_begin[fa.n_segments] = static_cast<uint32_t>(fill_blocks);
+      fill_blocks += blocks;
+      ++fa.n_segments;
+    }
+  }
+  for (int s = fa.n_segments; s <= odtk::kTalFillSegments; ++s) fa.block_begin[s] = static_cast<uint32_t>(fill_blocks);
+  if (n_max > 0) {
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      timed_launch(ODTK_KERNEL_ATSS_STATS, odtk::tal_select_kernel<T>, dim3(n_max, batch_size), dim3(odtk::kTalThreads), 0,
+                   static_cast<hipStream_t>(stream), ta);
+    });
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  timed_launch(ODTK_KERNEL_TARGETS, odtk::tal_fill_kernel, dim3(static_cast<unsigned>(fill_blocks)), dim3(odtk::kTalFillThreads), 0,
+               static_cast<hipStream_t>(stream), fa);
+  ODTK_HIP_TRY(hipGetLastError());
+  if (n_max > 0) {
+    const unsigned blocks = static_cast<unsigned>((1ull * n_max * ODTK_ATSS_MAX_TOPK + odtk::kTalScatterThreads - 1) / odtk::kTalScatterThreads);
+    timed_launch(ODTK_KERNEL_TARGETS, odtk::tal_scatter_kernel, dim3(blocks, batch_size), dim3(odtk::kTalScatterThreads), 0,
+                 static_cast<hipStream_t>(stream), ta);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
   return ODTK_OK;
 }
 

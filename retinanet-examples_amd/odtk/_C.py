@@ -130,6 +130,8 @@ _SIGNATURES = {
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp]),
     'odtk_atss_assign_levels': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SnapLevel), ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
+    'odtk_tal_assign_levels': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SnapLevel),
+                                              ctypes.POINTER(LossLevel)] + [ctypes.c_int] * 6 + [_vp, _sz, _vp]),
     'odtk_retina_loss_forward': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 3 + [_vp, _vp]),
     'odtk_retina_loss_backward': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 3 +
                                   [_vp, _vp, _vp, _vp, _vp]),
@@ -773,6 +775,37 @@ def atss_assign_levels(targets, anchors_list, num_classes, sizes, strides, topk=
     out = _snap_targets(arr, b, a, num_classes, 4, sizes, strides, dev, want_cls_target)
     _enqueue(library().odtk_atss_assign_levels, 'atss_assign_levels', dev, b, targets.data_ptr(), n_max, n, arr, a,
              int(num_classes), int(topk))
+    return out
+
+
+def tal_assign_levels(targets, cls_heads, box_heads, anchors_list, num_classes, strides, topk=13, alpha=1, beta=6, want_cls_target=True):
+    """Task-aligned target assignment for every pyramid level of the batch (csrc/tal.hpp; three launches and a workspace).
+    cls_heads / box_heads: per level the logits [B, A * C, H, W] and deltas [B, A * 4, H, W] as the convolutions wrote them -- one
+    dtype out of float32 / bfloat16 / float16, NCHW or channels_last, no copy.  Results as `atss_assign_levels`."""
+    n = len(cls_heads)
+    if len(box_heads) != n:
+        raise RuntimeError('tal_assign_levels: need 1..%d levels with matching lists' % MAX_LEVELS)
+    sizes = [tuple(int(v) for v in c.shape[-2:]) if isinstance(c, torch.Tensor) and c.dim() == 4 else (0, 0) for c in cls_heads]
+    arr, keep, n, a = _snap_levels('tal_assign_levels', targets, anchors_list, sizes, strides)
+    if not 1 <= int(topk) <= ATSS_MAX_TOPK:
+        raise RuntimeError('tal_assign_levels: topk must be in 1..%d' % ATSS_MAX_TOPK)
+    if not (0 <= int(alpha) <= 4 and 1 <= int(beta) <= 8):
+        raise RuntimeError('tal_assign_levels: alpha must be in 0..4 and beta in 1..8')
+    b, n_max = targets.shape[0], targets.shape[1]
+    dev = targets.device
+    heads = (LossLevel * n)()
+    dtype = None
+    for hd, c, x, (h, w) in zip(heads, cls_heads, box_heads, sizes):
+        lay = _pair_layout(c, x, 'cls_head', 'box_head', 'tal_assign_levels: ')
+        if c.dtype not in _DTYPES or x.dtype != c.dtype or (dtype is not None and c.dtype != dtype):
+            raise RuntimeError('tal_assign_levels: heads must share one dtype out of float32 / bfloat16 / float16')
+        dtype = c.dtype
+        if tuple(c.shape) != (b, a * int(num_classes), h, w) or tuple(x.shape) != (b, a * 4, h, w) or c.device != dev or x.device != dev:
+            raise RuntimeError('tal_assign_levels: inconsistent shapes')
+        hd.cls, hd.box, hd.height, hd.width, hd.channels_last = c.data_ptr(), x.data_ptr(), h, w, lay
+    out = _snap_targets(arr, b, a, num_classes, 4, sizes, strides, dev, want_cls_target)
+    _enqueue(library().odtk_tal_assign_levels, 'tal_assign_levels', dev, b, targets.data_ptr(), n_max, n, arr, heads, a,
+             int(num_classes), _DTYPES[dtype], int(topk), int(alpha), int(beta))
     return out
 
 

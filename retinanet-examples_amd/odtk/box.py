@@ -19,6 +19,8 @@ Differences, all deliberate:
     enqueue, with no host synchronisation (GPU only).
   * `atss_assign_levels` is an addition: ATSS target assignment next to the reference's fixed-IoU
     `snap_to_anchors` (HIP kernels for GPU tensors, pure torch otherwise).
+  * `tal_assign_levels` is an addition as well: task-aligned target assignment (TOOD), which ranks a box's candidate anchors by
+    what the network predicts at them (HIP kernels for GPU tensors, pure torch otherwise).
 """
 
 import math
@@ -323,6 +325,155 @@ def _atss_assign_torch(targets, sizes, strides, anchors_list, num_classes, topk,
     cls_t, box_t, depth_t = [], [], []
     for l, (h, w) in enumerate(sizes):
         a = anchors_list[l].shape[0]
+        cls_t.append(torch.stack([img[l][0] for img in per_image]) if want_cls_target and per_image else
+                     (targets.new_zeros((0, a, num_classes, h, w)) if want_cls_target else None))
+        box_t.append(torch.stack([img[l][1] for img in per_image]) if per_image else targets.new_zeros((0, a, 4, h, w)))
+        depth_t.append(torch.stack([img[l][2] for img in per_image]) if per_image else targets.new_zeros((0, a, 1, h, w)))
+    return cls_t, box_t, depth_t
+
+
+def _exp_cr(x):
+    """float32 exp rounded once from the double result: csrc/common.hpp exp_cr."""
+    return torch.exp(x.double()).float()
+
+
+def _tal_image(boxes, cls_heads, box_heads, strides, anchors_list, num_classes, topk, alpha, beta, want_cls_target):
+    """Task-aligned assignment for the valid rows [N, 5] of one image, pure torch, in the steps of csrc/tal.hpp.  cls_heads /
+    box_heads: per level float32 [A * C, H, W] / [A * 4, H, W] -> per level (cls, box, depth)."""
+    dev = boxes.device
+    n = boxes.shape[0]
+    sizes = [tuple(c.shape[-2:]) for c in cls_heads]
+    counts = [anchors.shape[0] * h * w for (h, w), anchors in zip(sizes, anchors_list)]
+    owner = torch.full((sum(counts),), -1, dtype=torch.long, device=dev)
+    xyxy = torch.cat([boxes[:, :2], boxes[:, :2] + boxes[:, 2:4] - 1], 1)
+    classes = boxes[:, 4]
+    if n:
+        x1, y1, x2, y2 = (xyxy[:, i, None, None, None] for i in range(4))                             # [N, 1, 1, 1]
+        area = (x2 - x1 + 1) * (y2 - y1 + 1)
+        margin = torch.tensor(0.01, dtype=torch.float32, device=dev)
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        metric, overlap, candidate = [], [], []
+        for (h, w), s, anchors, cls_head, box_head in zip(sizes, strides, anchors_list, cls_heads, box_heads):
+            s = float(s)
+            a = anchors.shape[0]
+            anchors = anchors.to(device=dev, dtype=torch.float32)
+            # 2. candidates: the cell centre more than 0.01 inside the box on all four sides
+            px = torch.arange(w, device=dev, dtype=torch.float32) * s + 0.5 * s + 0.5
+            py = torch.arange(h, device=dev, dtype=torch.float32) * s + 0.5 * s + 0.5
+            inside = ((px[None, None, None, :] - x1 > margin) & (py[None, None, :, None] - y1 > margin) &
+                      (x2 - px[None, None, None, :] > margin) & (y2 - py[None, None, :, None] > margin))  # [N, 1, H, W]
+            # 3. the score of the row's class
+            logit = cls_head.reshape(a, num_classes, h, w)[:, classes.long()].permute(1, 0, 2, 3)       # [N, A, H, W]
+            score = 1.0 / (1.0 + _exp_cr(-logit))
+            # 4. the predicted box (delta2box without the clamp)
+            d = box_head.reshape(a, 4, h, w)
+            fx = torch.arange(w, device=dev, dtype=torch.float32)[None, None, :] * s
+            fy = torch.arange(h, device=dev, dtype=torch.float32)[None, :, None] * s
+            ax1, ay1 = fx + anchors[:, 0, None, None], fy + anchors[:, 1, None, None]                   # [A, 1 | H, W | 1]
+            ax2, ay2 = fx + anchors[:, 2, None, None], fy + anchors[:, 3, None, None]
+            aw, ah = ax2 - ax1 + 1, ay2 - ay1 + 1
+            cx, cy = ax1 + 0.5 * aw, ay1 + 0.5 * ah
+            pcx, pcy = d[:, 0] * aw + cx, d[:, 1] * ah + cy
+            pw, ph = _exp_cr(d[:, 2]) * aw, _exp_cr(d[:, 3]) * ah
+            p1x, p1y, p2x, p2y = pcx - 0.5 * pw, pcy - 0.5 * ph, pcx + 0.5 * pw - 1, pcy + 0.5 * ph - 1
+            # 5. the overlap (torch.min / torch.max propagate NaN, like tmin_nan / tmax_nan)
+            p_area = (p2x - p1x + 1) * (p2y - p1y + 1)
+            iw = torch.min(p2x[None], x2.expand(n, a, h, w)) - torch.max(p1x[None], x1.expand(n, a, h, w)) + 1
+            ih = torch.min(p2y[None], y2.expand(n, a, h, w)) - torch.max(p1y[None], y1.expand(n, a, h, w)) + 1
+            iw, ih = torch.where(iw < 0, zero, iw), torch.where(ih < 0, zero, ih)
+            inter = iw * ih
+            u = inter / (p_area[None] + area - inter)
+            # 6. the metric
+            m = torch.ones_like(u)
+            for _ in range(alpha):
+                m = m * score
+            for _ in range(beta):
+                m = m * u
+            metric.append(m.reshape(n, -1))
+            overlap.append(u.reshape(n, -1))
+            candidate.append(inside.expand(n, a, h, w).reshape(n, -1))
+        metric, overlap, candidate = torch.cat(metric, 1), torch.cat(overlap, 1), torch.cat(candidate, 1)
+        # 7. per row the topk largest metrics (a stable descending sort: ties to the lower global index); NaN never, 0 eligible
+        eligible = candidate & ~torch.isnan(metric)
+        ranked, order = torch.sort(torch.where(eligible, metric + 0.0, torch.full_like(metric, -1.0)), dim=1, descending=True, stable=True)
+        ranked, order = ranked[:, :topk], order[:, :topk]
+        # 8. a contested anchor goes to the largest overlap, the earliest row on a tie
+        best = torch.zeros(owner.shape[0], dtype=torch.float32, device=dev)
+        for g in range(n):
+            idx = order[g][ranked[g] >= 0]
+            ov = overlap[g][idx]
+            take = (owner[idx] < 0) | (ov > best[idx])
+            owner[idx[take]] = g
+            best[idx[take]] = ov[take]
+    # 9. outputs in [A, *, H, W] order
+    out, first = [], 0
+    for (h, w), s, anchors, count in zip(sizes, strides, anchors_list, counts):
+        a = anchors.shape[0]
+        mine = owner[first:first + count]
+        first += count
+        hit = (mine >= 0).nonzero().view(-1)
+        box_target = torch.zeros((count, 4), dtype=torch.float32, device=dev)
+        depth = torch.zeros(count, dtype=torch.float32, device=dev)
+        cls_target = torch.zeros((count, num_classes), dtype=torch.float32, device=dev) if want_cls_target else None
+        if hit.numel():
+            cell = _cell_anchors(anchors, [w * float(s), h * float(s)], float(s), torch.float32, dev)
+            box_target[hit] = box2delta(xyxy[mine[hit]], cell[hit])
+            depth[hit] = classes[mine[hit]] + 1
+            if want_cls_target:
+                cls_target[hit, classes[mine[hit]].long()] = 1
+        if want_cls_target:
+            cls_target = cls_target.view(a, h, w, num_classes).permute(0, 3, 1, 2).contiguous()
+        out.append((cls_target, box_target.view(a, h, w, 4).permute(0, 3, 1, 2).contiguous(), depth.view(a, 1, h, w)))
+    return out
+
+
+def tal_assign_levels(targets, cls_heads, box_heads, strides, anchors_list, num_classes, topk=13, alpha=1, beta=6,
+                      want_cls_target=True):
+    """Task-aligned target assignment (TOOD, Feng et al., ICCV 2021; the assigner of PP-YOLOE and YOLOv8) for every image and
+    pyramid level: the assigner that looks at what the network predicts, axis-aligned boxes only.  The candidates of a box are
+    the anchors whose cell centre lies inside it; each gets the metric s^alpha * u^beta -- s the class score the network gives the
+    box's class there, u the IoU of the box it predicts there with the ground truth --, the box takes its `topk` best over all
+    levels, and an anchor taken by several boxes goes to the largest u.  The exact definition is in csrc/tal.hpp.
+    A box that contains no cell centre gets no positive anchor at all.
+
+    targets [B, N, 5] = (x, y, w, h, class), rows whose class is not a whole number in 0..num_classes-1 are padding; cls_heads /
+    box_heads: per level the logits [B, A * C, H, W] and deltas [B, A * 4, H, W] -- pass them detached; alpha in 0..4 and beta in
+    1..8 are whole numbers.  GPU tensors go to the HIP kernels as the convolutions wrote them (float32 / bfloat16 / float16, NCHW or
+    channels_last, no copy); any other tensor takes the pure-torch branch, which follows the same definition.
+    -> lists (cls_targets [B, A, C, H, W] | Nones, box_targets [B, A, 4, H, W], depths [B, A, 1, H, W]); depth is class + 1
+    or 0 (there is no ignore band)."""
+    topk, alpha, beta = int(topk), int(alpha), int(beta)
+    if not 1 <= topk <= _C.ATSS_MAX_TOPK:
+        raise ValueError('tal_assign_levels: topk must be in 1..%d' % _C.ATSS_MAX_TOPK)
+    if not 0 <= alpha <= 4:
+        raise ValueError('tal_assign_levels: alpha must be in 0..4')
+    if not 1 <= beta <= 8:
+        raise ValueError('tal_assign_levels: beta must be in 1..8')
+    if len(cls_heads) > MAX_LEVELS_PER_CALL:
+        raise ValueError('tal_assign_levels: at most %d levels (a box ranks its candidates over all of them, so the call cannot '
+                         'be split)' % MAX_LEVELS_PER_CALL)
+    if not (len(cls_heads) == len(box_heads) == len(strides) == len(anchors_list)) or not cls_heads:
+        raise ValueError('tal_assign_levels: one class head, box head, stride and anchor table per level')
+    targets = targets.float()
+    if targets.is_cuda:
+        pairs = [_pair(c.detach(), b.detach()) for c, b in zip(cls_heads, box_heads)]
+        return _C.tal_assign_levels(targets.contiguous(), [p[0] for p in pairs], [p[1] for p in pairs], anchors_list, num_classes,
+                                    [int(s) for s in strides], topk, alpha, beta, want_cls_target)
+    return _tal_assign_torch(targets, cls_heads, box_heads, strides, anchors_list, num_classes, topk, alpha, beta, want_cls_target)
+
+
+def _tal_assign_torch(targets, cls_heads, box_heads, strides, anchors_list, num_classes, topk, alpha, beta, want_cls_target):
+    """The pure-torch branch of tal_assign_levels (any device); 16-bit heads are widened to float32, which is exact."""
+    cls_heads, box_heads = [c.detach().float() for c in cls_heads], [b.detach().float() for b in box_heads]
+    per_image = []
+    for i, t in enumerate(targets):
+        c = t[:, 4]
+        valid = (c >= 0) & (c < num_classes) & (c == torch.floor(c))
+        per_image.append(_tal_image(t[valid], [h[i] for h in cls_heads], [h[i] for h in box_heads], strides, anchors_list, num_classes,
+                                    topk, alpha, beta, want_cls_target))
+    cls_t, box_t, depth_t = [], [], []
+    for l, head in enumerate(cls_heads):
+        a, (h, w) = anchors_list[l].shape[0], head.shape[-2:]
         cls_t.append(torch.stack([img[l][0] for img in per_image]) if want_cls_target and per_image else
                      (targets.new_zeros((0, a, num_classes, h, w)) if want_cls_target else None))
         box_t.append(torch.stack([img[l][1] for img in per_image]) if per_image else targets.new_zeros((0, a, 4, h, w)))

@@ -22,6 +22,10 @@ What differs from the reference, and why:
   * `--assigner {iou,atss}` (train) with `--atss-topk` is new: ATSS target assignment (odtk/box.py:atss_assign_levels, two HIP
     launches) instead of the reference's fixed `--anchor-ious` rule; axis-aligned boxes only.  Never stored in a checkpoint: a
     resumed run has to be given the flag again.
+  * `--assigner tal` (train) with `--tal-topk`, `--tal-alpha` and `--tal-beta` is new as well: task-aligned target assignment (TOOD;
+    odtk/box.py:tal_assign_levels, three HIP launches).  A box takes as positives the `--tal-topk` anchors inside it with the largest
+    score^alpha * IoU^beta of what the network predicts there; with `--cls-loss qfl|vfl --box-loss giou` it is the TOOD-style
+    recipe.  Axis-aligned boxes only.  Never stored in a checkpoint: give the flags again when resuming.
   * `--box-voting value` and `--tta flip` (infer; train: its validation passes) are new: box voting behind the suppression
     (odtk/box.py:box_vote, one HIP launch: every kept box becomes the score-weighted mean of its class's candidates that overlap it
     by at least `value`) and test-time augmentation by the horizontal flip (the network also runs on the mirrored batch, one
@@ -134,10 +138,16 @@ TRAIN_FLAGS = [
     _flag('--absolute-angle', bool, text='regress the absolute angle instead of -45..45 degrees'),
     # not flags of the reference: absent from the namespace unless given (read with getattr)
     _flag('--assigner', str, argparse.SUPPRESS, 'how ground truth becomes training targets: iou = the fixed --anchor-ious thresholds '
-          '(default), atss = adaptive training sample selection (not with --rotated-bbox).  Not stored in the checkpoint: give it '
-          'again when resuming', choices=['iou', 'atss']),
+          '(default), atss = adaptive training sample selection, tal = task-aligned assignment by the predicted score and IoU (both '
+          'not with --rotated-bbox).  Not stored in the checkpoint: give it again when resuming', choices=['iou', 'atss', 'tal']),
     _flag('--atss-topk', int, argparse.SUPPRESS, 'nearest cells per box and pyramid level that ATSS considers, 1..16 (default 9; '
           'needs --assigner atss)', metavar='num'),
+    _flag('--tal-topk', int, argparse.SUPPRESS, 'anchors a box takes as positives under task-aligned assignment, 1..16 (default 13; '
+          'needs --assigner tal; give it again when resuming)', metavar='num'),
+    _flag('--tal-alpha', int, argparse.SUPPRESS, 'exponent of the class score in the task-aligned metric, a whole number in 0..4 '
+          '(default 1; needs --assigner tal; give it again when resuming)', metavar='n'),
+    _flag('--tal-beta', int, argparse.SUPPRESS, 'exponent of the IoU in the task-aligned metric, a whole number in 1..8 (default 6; '
+          'needs --assigner tal; give it again when resuming)', metavar='n'),
     _flag('--box-loss', str, argparse.SUPPRESS, 'what the box regression is trained with: smooth-l1 on the four deltas (default), or an '
           'iou / giou / diou loss on the boxes they decode to (not with --rotated-bbox).  Not stored in the checkpoint: give it again '
           'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou']),
@@ -216,6 +226,13 @@ def parse(args):
         parser.error('--atss-topk must be in 1..16')
     if getattr(parsed, 'assigner', 'iou') == 'atss' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--assigner atss is not available with --rotated-bbox')
+    for flag, low, high in (('tal_topk', 1, 16), ('tal_alpha', 0, 4), ('tal_beta', 1, 8)):
+        if hasattr(parsed, flag) and getattr(parsed, 'assigner', 'iou') != 'tal':
+            parser.error('--%s needs --assigner tal' % flag.replace('_', '-'))
+        if hasattr(parsed, flag) and not low <= getattr(parsed, flag) <= high:
+            parser.error('--%s must be in %d..%d' % (flag.replace('_', '-'), low, high))
+    if getattr(parsed, 'assigner', 'iou') == 'tal' and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--assigner tal is not available with --rotated-bbox')
     if hasattr(parsed, 'box_loss_weight'):
         if getattr(parsed, 'box_loss', 'smooth-l1') == 'smooth-l1':
             parser.error('--box-loss-weight needs --box-loss iou, giou or diou')
@@ -314,8 +331,9 @@ def worker(rank, args, world, spawned=False):
                 raise RuntimeError("--tile must be a multiple of the model's stride, {}".format(model.stride))
     if args.command == 'train':
         model.assigner, model.atss_topk = getattr(args, 'assigner', 'iou'), getattr(args, 'atss_topk', 9)
-        if model.assigner == 'atss' and args.rotated_bbox:
-            raise RuntimeError('--assigner atss is not available for a model with rotated boxes')
+        model.tal_topk, model.tal_alpha, model.tal_beta = getattr(args, 'tal_topk', 13), getattr(args, 'tal_alpha', 1), getattr(args, 'tal_beta', 6)
+        if model.assigner in ('atss', 'tal') and args.rotated_bbox:
+            raise RuntimeError('--assigner {} is not available for a model with rotated boxes'.format(model.assigner))
         model.box_loss = getattr(args, 'box_loss', 'smooth-l1').replace('-', '_')
         model.box_loss_weight = getattr(args, 'box_loss_weight', 1.0)
         if model.box_loss != 'smooth_l1' and args.rotated_bbox:

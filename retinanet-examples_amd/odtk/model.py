@@ -98,9 +98,12 @@ class Model(nn.Module):
         self.tile = None
         # how ground truth becomes training targets: 'iou' (the reference's fixed thresholds, `anchor_ious`) or 'atss' (adaptive
         # training sample selection over the `atss_topk` nearest cells per level, odtk/box.py:atss_assign_levels; axis-aligned
-        # boxes only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
+        # boxes only), or 'tal' (task-aligned assignment: per box the `tal_topk` candidate anchors with the largest
+        # score^`tal_alpha` * IoU^`tal_beta` of what the network predicts there, odtk/box.py:tal_assign_levels; axis-aligned boxes
+        # only).  Run-time options like `soft_nms`: not constructor arguments, never written into checkpoints
         self.assigner = 'iou'
         self.atss_topk = 9
+        self.tal_topk, self.tal_alpha, self.tal_beta = 13, 1, 6
         # what the box regression is trained with: 'smooth_l1' (the reference's loss on the four deltas) or 'iou' | 'giou' | 'diou' on
         # the boxes the deltas decode to (odtk/loss.py:box_iou_loss, csrc/box_iou_loss.hpp; axis-aligned boxes only), times
         # `box_loss_weight` (those three only).  Run-time options like `assigner`: never written into checkpoints
@@ -420,8 +423,8 @@ class Model(nn.Module):
         count; `fused_pyramid_loss` is called only while `box_loss` is 'smooth_l1', for its box sum -- its classification half goes
         unused, as its box half does under an IoU-family `box_loss`."""
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
-        if self.assigner not in ('iou', 'atss'):
-            raise ValueError("Model.assigner must be 'iou' or 'atss', not {!r}".format(self.assigner))
+        if self.assigner not in ('iou', 'atss', 'tal'):
+            raise ValueError("Model.assigner must be 'iou', 'atss' or 'tal', not {!r}".format(self.assigner))
         iou_kind = None
         if self.box_loss != 'smooth_l1':
             if self.box_loss not in BOX_LOSS_KINDS:
@@ -451,6 +454,18 @@ class Model(nn.Module):
             atss = box_ops.atss_assign_levels(targets, [tuple(c.shape[-2:]) for c in cls_heads], strides,
                                               [self.level_anchors(s) for s in strides], self.classes, self.atss_topk,
                                               want_cls_target=not fused)
+        elif self.assigner == 'tal':
+            if self.rotated_bbox:
+                raise ValueError("Model.assigner = 'tal' is not available for rotated boxes")
+            if len(cls_heads) > box_ops.MAX_LEVELS_PER_CALL:
+                raise ValueError("Model.assigner = 'tal' takes at most {} pyramid levels (a box ranks its candidates over all of "
+                                 'them, so the call cannot be split), not {}'.format(box_ops.MAX_LEVELS_PER_CALL, len(cls_heads)))
+            strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+            fused = self.fused_loss and cls_heads[0].is_cuda
+            # the assignment reads the heads as constants (detached); from here on both paths consume it exactly as ATSS's
+            atss = box_ops.tal_assign_levels(targets, [c.detach() for c in cls_heads], [b.detach() for b in box_heads], strides,
+                                             [self.level_anchors(s) for s in strides], self.classes, self.tal_topk, self.tal_alpha,
+                                             self.tal_beta, want_cls_target=not fused)
         if self.fused_loss and cls_heads[0].is_cuda:
             # targets of every level (ONE HIP launch for all of them; the class map is implied by depth and not even built), then focal
             # + smooth-L1 + masks + sums of ALL levels in one HIP pass -- and one more in backward (csrc/loss.hpp)
