@@ -741,6 +741,52 @@ int odtk_box_iou_loss_levels_backward(int n_levels, const odtk_loss_level_t *lev
                                       int num_anchors, int dtype, int kind, const float *grad_sums, void *stream);
 
 /*
+ * odtk_rotated_box_loss_levels_forward / _backward -- ProbIoU (arXiv 2106.06072) or KLD (arXiv 2106.01883) box-regression loss on
+ * the Gaussians of ROTATED boxes, at the foreground anchors of ALL pyramid levels of the batch: the opt-in alternative to the
+ * smooth-L1 sum on the six deltas (Model.box_loss, `odtk train --rotated-bbox --box-loss probiou|kld`).  No reference equivalent;
+ * the definition -- the contract -- restated in torch in odtk/loss.py:rotated_box_loss:
+ *   one foreground anchor (depth > 0) of anchor slot a, (aw, ah) = (x2 - x1 + 1, y2 - y1 + 1) of the level's AXIS anchor table,
+ *   p = the six predicted deltas (head dtype -> float32), t = the six target deltas, (t4, t5) the box's (sin, cos); both boxes
+ *   decoded relative to the anchor centre:
+ *     CLIP = log(1000 / 16);  pw' = min(p2, CLIP), ph' = min(p3, CLIP)       (predictions only; gradient 0 beyond the clip)
+ *     centre (p0 aw, p1 ah);  w = exp(pw') aw,  h = exp(ph') ah              target: the same from t, unclipped
+ *     q = p4^2 + p5^2 + 1e-12;  cc = p5^2 / q,  ss = p4^2 / q,  sc = p4 p5 / q       (target: the same from t4, t5)
+ *     a = (w^2 cc + h^2 ss) / 12     b = (w^2 ss + h^2 cc) / 12     c = -(w^2 - h^2) sc / 12
+ *   [[a, c], [c, b]]: the covariance of the uniform distribution on the rotated rectangle, width axis (cos, -sin), height axis
+ *   (sin, cos) as in odtk/box.py:rotate_boxes.  Index 1 the prediction, 2 the target; (dx, dy) = centre(P) - centre(T):
+ *     ODTK_ROTATED_BOX_LOSS_PROBIOU: A = a1 + a2, B = b1 + b2, C = c1 + c2, D = A B - C^2
+ *         BD = (B dx^2 + A dy^2 - 2 C dx dy) / (4 D) + 0.5 ln(36 D / (w h tw th))
+ *         BD' = min(max(BD, 0), 100)     L = sqrt(1 - exp(-BD') + 1e-7)                     (gradient 0 where clamped)
+ *     ODTK_ROTATED_BOX_LOSS_KLD:     d2 = (tw th / 12)^2
+ *         K = 0.5 [(b2 a1 + a2 b1 - 2 c2 c1) / d2 + (b2 dx^2 + a2 dy^2 - 2 c2 dx dy) / d2 - 2] + (t2 + t3 - pw' - ph')
+ *         K' = max(K, 0)                 L = 1 - 1 / (1 + ln(1 + K'))                       (gradient 0 where clamped)
+ * min / max hand a NaN on: a NaN delta at a foreground anchor gives a NaN sum.  The loss does not depend on the length of
+ * (p4, p5): its gradient on the pair is tangential and scales with 1 / sqrt(q); for w = h the angle gradient is 0.
+ * The level descriptor of the smooth-L1 entry points is reused: `cls` / `dcls` are ignored and may be NULL, box has 6 parameters
+ * per anchor.  `anchors`: HOST array of n_levels pointers to HOST float[4 * num_anchors], the axis tables (only the sizes are used).
+ *   forward:  sums = DEVICE double[n_levels][2] = (sum of L over the level's foreground anchors, their number), overwritten;
+ *             float64 in one fixed order through the workspace (two-phase query as everywhere): no atomics, the same bits on every run.
+ *   backward: grad_sums = DEVICE float32[n_levels] (NULL = zeros), read on the device; levels[l].dbox receives grad_sums[l] dL/dp
+ *             for all six deltas at the foreground cells and +0 everywhere else -- every element is written -- in the dtype and
+ *             layout of box, rounded once at the store.
+ * Cells that are not foreground are never read from box.  Arithmetic: the float32 deltas widened, IEEE double per anchor (BD and K
+ * are small differences of O(1) terms; csrc/rotated_box_loss.hpp).  Everything is checked on the host
+ * before anything touches HIP.  ODTK_ERR_INVALID: a null pointer, n_levels outside 1..ODTK_MAX_LEVELS, num_anchors outside
+ * 1..ODTK_MAX_ANCHORS, batch_size < 1, a non-positive size, an undefined kind, an anchor whose width or height is not finite and
+ * > 0, a level with batch * A * 6 * H * W >= 2^31, a misaligned pointer (channels_last: a cell is three pieces of 8 bytes for fp32
+ * heads, of 4 for 16-bit ones), a workspace that is too small.  Another dtype is ODTK_ERR_UNSUPPORTED.  One launch per direction
+ * over one lane per anchor cell (csrc/rotated_box_loss.hpp), timed under ODTK_KERNEL_LOSS; the forward's second launch under
+ * ODTK_KERNEL_LOSS_REDUCE.
+ */
+#define ODTK_ROTATED_BOX_LOSS_PROBIOU  1
+#define ODTK_ROTATED_BOX_LOSS_KLD      2
+int odtk_rotated_box_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                         int num_anchors, int dtype, int kind, double *sums, void *workspace, size_t workspace_size,
+                                         void *stream);
+int odtk_rotated_box_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                          int num_anchors, int dtype, int kind, const float *grad_sums, void *stream);
+
+/*
  * odtk_quality_loss_levels_forward / _backward -- Quality Focal Loss (GFL, arXiv 2006.04388 eq. 4) or Varifocal Loss (arXiv
  * 2008.13367 eq. 2, as mmdetection implements it) over the class logits of ALL pyramid levels of the batch: the opt-in
  * alternatives to the focal sum of odtk_retina_loss_* (Model.cls_loss, `odtk train --cls-loss`), axis-aligned boxes only.  No

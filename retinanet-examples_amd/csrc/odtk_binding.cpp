@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images`, `merge_tile_candidates` and `tal_assign_levels`.  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images`, `merge_tile_candidates`, `tal_assign_levels` and `rotated_box_loss_levels_forward` / `_backward`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -386,6 +386,94 @@ std::vector<std::vector<std::optional<torch::Tensor>>> tal_assign_levels(torch::
   return out;
 }
 
+// ProbIoU / KLD box losses of rotated boxes (odtk_rotated_box_loss_levels_*: no reference equivalent), the signatures of
+// odtk/_C.py:rotated_box_loss_levels_forward / _backward.  The heads are taken as the convolutions wrote them.
+struct RotatedLossLevels {
+  std::vector<odtk_loss_level_t> levels;
+  std::vector<const float *> tables;
+  int batch = 0, num_anchors = 0, dtype = -1, kind = 0;
+};
+
+RotatedLossLevels rotated_loss_levels(const char *what, const std::vector<torch::Tensor> &box_heads, const std::vector<torch::Tensor> &depths,
+                                      const std::vector<torch::Tensor> &box_targets, const std::vector<std::vector<float>> &anchors,
+                                      const std::string &kind, const std::vector<torch::Tensor> *grads) {
+  const size_t n = box_heads.size();
+  TORCH_CHECK(n >= 1 && n <= ODTK_MAX_LEVELS && depths.size() == n && box_targets.size() == n && anchors.size() == n, what, ": need 1..",
+              ODTK_MAX_LEVELS, " levels with matching lists");
+  TORCH_CHECK(kind == "probiou" || kind == "kld", what, ": kind must be 'probiou' or 'kld', not '", kind, "'");
+  RotatedLossLevels out;
+  out.kind = kind == "probiou" ? ODTK_ROTATED_BOX_LOSS_PROBIOU : ODTK_ROTATED_BOX_LOSS_KLD;
+  out.levels.resize(n);
+  out.tables.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto &head = box_heads[i], &depth = depths[i], &target = box_targets[i];
+    TORCH_CHECK(head.is_cuda() && depth.is_cuda() && target.is_cuda(), what, ": tensors must be on the GPU");
+    TORCH_CHECK(head.dim() == 4 && depth.dim() == 5 && target.dim() == 5, what, ": box heads must be [B, A*6, H, W], depth [B, A, 1, H, W], "
+                "box_target [B, A, 6, H, W]");
+    const auto st = head.scalar_type();
+    const int dt = st == torch::kFloat32 ? ODTK_F32 : st == torch::kBFloat16 ? ODTK_BF16 : st == torch::kFloat16 ? ODTK_F16 : -1;
+    TORCH_CHECK(dt >= 0, what, ": box heads must be float32 / bfloat16 / float16");
+    const bool nchw = head.is_contiguous(), nhwc = head.is_contiguous(at::MemoryFormat::ChannelsLast);
+    TORCH_CHECK(nchw || nhwc, what, ": box heads must be dense NCHW or channels_last");
+    const int64_t b = head.size(0), h = head.size(2), w = head.size(3), a = target.size(1);
+    TORCH_CHECK(head.size(1) == 6 * a && depth.sizes() == torch::IntArrayRef({b, a, 1, h, w}) &&
+                target.sizes() == torch::IntArrayRef({b, a, 6, h, w}), what, ": inconsistent shapes");
+    TORCH_CHECK(depth.scalar_type() == torch::kFloat32 && target.scalar_type() == torch::kFloat32 && depth.is_contiguous() &&
+                target.is_contiguous(), what, ": depth and box_target must be contiguous float32");
+    if (i == 0) { out.batch = static_cast<int>(b); out.num_anchors = static_cast<int>(a); out.dtype = dt; }
+    TORCH_CHECK(out.batch == b && out.num_anchors == a && out.dtype == dt, what, ": every level must share batch, anchors and dtype");
+    TORCH_CHECK(static_cast<int64_t>(anchors[i].size()) == 4 * a, what, ": every level needs an [A, 4] anchor table");
+    out.tables[i] = anchors[i].data();
+    out.levels[i] = odtk_loss_level_t{nullptr, head.data_ptr(), static_cast<const float *>(depth.data_ptr()),
+                                      static_cast<const float *>(target.data_ptr()), nullptr, grads ? (*grads)[i].data_ptr() : nullptr,
+                                      static_cast<int32_t>(h), static_cast<int32_t>(w), nchw ? 0 : 1, 0};
+  }
+  return out;
+}
+
+torch::Tensor rotated_box_loss_levels_forward(std::vector<torch::Tensor> box_heads, std::vector<torch::Tensor> depths,
+                                              std::vector<torch::Tensor> box_targets, std::vector<std::vector<float>> anchors,
+                                              std::string kind) {
+  const RotatedLossLevels lv = rotated_loss_levels("rotated_box_loss_levels_forward", box_heads, depths, box_targets, anchors, kind, nullptr);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(box_heads[0].device());
+  auto sums = torch::empty({static_cast<int64_t>(lv.levels.size()), 2}, box_heads[0].options().dtype(torch::kFloat64));
+  void *stream = current_stream(box_heads[0]);
+  {
+    pybind11::gil_scoped_release nogil;
+    with_scratch(box_heads[0], "rotated_box_loss_levels_forward", [&](void *ws, size_t size) {
+      return odtk_rotated_box_loss_levels_forward(static_cast<int>(lv.levels.size()), lv.levels.data(), lv.tables.data(), lv.batch,
+                                                  lv.num_anchors, lv.dtype, lv.kind, static_cast<double *>(sums.data_ptr()), ws, size,
+                                                  ws ? stream : nullptr);
+    });
+  }
+  return sums;
+}
+
+std::vector<torch::Tensor> rotated_box_loss_levels_backward(std::vector<torch::Tensor> box_heads, std::vector<torch::Tensor> depths,
+                                                            std::vector<torch::Tensor> box_targets, std::vector<std::vector<float>> anchors,
+                                                            std::string kind, std::optional<torch::Tensor> grad_sums) {
+  std::vector<torch::Tensor> dbox;
+  for (const auto &head : box_heads) {
+    dbox.push_back(torch::empty_like(head));
+    TORCH_CHECK(dbox.back().strides() == head.strides(), "rotated_box_loss_levels_backward: could not allocate gradients in the heads' layout");
+  }
+  const RotatedLossLevels lv = rotated_loss_levels("rotated_box_loss_levels_backward", box_heads, depths, box_targets, anchors, kind, &dbox);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(box_heads[0].device());
+  torch::Tensor g;
+  if (grad_sums) {
+    g = grad_sums->detach().to(box_heads[0].device(), torch::kFloat32).reshape({static_cast<int64_t>(lv.levels.size())}).contiguous();
+  }
+  void *stream = current_stream(box_heads[0]);
+  {
+    pybind11::gil_scoped_release nogil;
+    checked(odtk_rotated_box_loss_levels_backward(static_cast<int>(lv.levels.size()), lv.levels.data(), lv.tables.data(), lv.batch,
+                                                  lv.num_anchors, lv.dtype, lv.kind, grad_sums ? static_cast<const float *>(g.data_ptr()) : nullptr,
+                                                  stream),
+            "rotated_box_loss_levels_backward");
+  }
+  return dbox;
+}
+
 struct Engine {};   // csrc/engine.h: the TensorRT engine class -- not available on MI355X (BASELINE.json north_star)
 
 }  // namespace
@@ -426,6 +514,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tal_assign_levels", &tal_assign_levels, py::arg("targets"), py::arg("cls_heads"), py::arg("box_heads"), py::arg("anchors_list"),
         py::arg("num_classes"), py::arg("strides"), py::arg("topk") = 13, py::arg("alpha") = 1, py::arg("beta") = 6,
         py::arg("want_cls_target") = true);
+  m.def("rotated_box_loss_levels_forward", &rotated_box_loss_levels_forward, py::arg("box_heads"), py::arg("depths"), py::arg("box_targets"),
+        py::arg("anchors_list"), py::arg("kind"));
+  m.def("rotated_box_loss_levels_backward", &rotated_box_loss_levels_backward, py::arg("box_heads"), py::arg("depths"),
+        py::arg("box_targets"), py::arg("anchors_list"), py::arg("kind"), py::arg("grad_sums") = py::none());
   m.def("version", [] { return std::string(odtk_version()); });
   // sizes of the ABI structs THIS module was compiled against: a module older than include/odtk_hip.h passes arrays of the
   // wrong stride (tests/test_compiled_binding.py compares them with the ctypes mirror on every CPU run)

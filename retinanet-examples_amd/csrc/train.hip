@@ -1,6 +1,6 @@
 // train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels, odtk_tal_assign_levels) and the focal + smooth-L1 loss: launch shapes,
 // odtk_debug_loss_*, odtk_retina_loss_*; the IoU-family box losses (odtk_box_iou_loss_levels_*); the quality / varifocal
-// classification losses (odtk_quality_loss_levels_*).
+// classification losses (odtk_quality_loss_levels_*); the Gaussian box losses of rotated boxes (odtk_rotated_box_loss_levels_*).
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -12,6 +12,7 @@
 #include "loss.hpp"
 #include "box_iou_loss.hpp"
 #include "quality_loss.hpp"
+#include "rotated_box_loss.hpp"
 
 namespace {
 
@@ -182,13 +183,17 @@ int retina_loss_launch(bool backward, const void *cls, const void *box, const fl
                                    nullptr, false, stream);
 }
 
-// The kernel arguments of odtk_box_iou_loss_levels_* (csrc/box_iou_loss.hpp) from the ABI's level table; everything the entry
-// points promise to check is checked here, on the host.  `pointers`: false for the workspace query, which looks at no data pointer.
+// The kernel arguments of odtk_box_iou_loss_levels_* (csrc/box_iou_loss.hpp; nb = 4 box parameters per anchor) and of
+// odtk_rotated_box_loss_levels_* (csrc/rotated_box_loss.hpp; nb = 6) from the ABI's level table; everything the entry points
+// promise to check is checked here, on the host.  `pointers`: false for the workspace query, which looks at no data pointer.
 int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_levels, const odtk_loss_level_t *levels,
-                 const float *const *anchors, int batch, int A, int dtype, int kind, const float *g, unsigned *total_blocks) {
+                 const float *const *anchors, int batch, int A, int dtype, int kind, const float *g, unsigned *total_blocks,
+                 unsigned nb = 4) {
   if (n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || !levels || !anchors || batch < 1 || A < 1 || A > ODTK_MAX_ANCHORS)
     return ODTK_ERR_INVALID;
-  if (kind != ODTK_BOX_LOSS_IOU && kind != ODTK_BOX_LOSS_GIOU && kind != ODTK_BOX_LOSS_DIOU) return ODTK_ERR_INVALID;
+  if (nb == 4 ? (kind != ODTK_BOX_LOSS_IOU && kind != ODTK_BOX_LOSS_GIOU && kind != ODTK_BOX_LOSS_DIOU)
+              : (kind != ODTK_ROTATED_BOX_LOSS_PROBIOU && kind != ODTK_ROTATED_BOX_LOSS_KLD))
+    return ODTK_ERR_INVALID;
   if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
   std::memset(&ba, 0, sizeof ba);
   ba.n_levels = n_levels;
@@ -200,7 +205,7 @@ int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_level
     odtk::BoxIouLevel &bl = ba.lv[l];
     if (lv.height <= 0 || lv.width <= 0 || (lv.channels_last != 0 && lv.channels_last != 1) || !anchors[l]) return ODTK_ERR_INVALID;
     const unsigned long long cells = 1ull * batch * A * lv.height * lv.width;
-    if (4 * cells >= (1ull << 31)) return ODTK_ERR_INVALID;     // the kernels index the deltas with 32 bits
+    if (nb * cells >= (1ull << 31)) return ODTK_ERR_INVALID;    // the kernels index the deltas with 32 bits
     for (int i = 0; i < A; ++i) {
       const float *an = anchors[l] + 4 * i;
       const float aw = an[2] - an[0] + 1.0f, ah = an[3] - an[1] + 1.0f;
@@ -210,8 +215,10 @@ int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_level
     }
     if (pointers) {
       if (!lv.box || !lv.depth || !lv.box_target || (backward && !lv.dbox)) return ODTK_ERR_INVALID;
-      // channels_last: one 16- / 8-byte vector per cell; otherwise the element's own alignment
-      const uintptr_t mask = lv.channels_last ? (dtype == ODTK_F32 ? 15u : 7u) : (dtype == ODTK_F32 ? 3u : 1u);
+      // channels_last: one 16- / 8-byte vector per cell of four, three 8- / 4-byte pieces per cell of six; otherwise the
+      // element's own alignment
+      const uintptr_t vec = nb == 4 ? (dtype == ODTK_F32 ? 15u : 7u) : (dtype == ODTK_F32 ? 7u : 3u);
+      const uintptr_t mask = lv.channels_last ? vec : (dtype == ODTK_F32 ? 3u : 1u);
       if ((reinterpret_cast<uintptr_t>(lv.box) | (backward ? reinterpret_cast<uintptr_t>(lv.dbox) : 0u)) & mask) return ODTK_ERR_INVALID;
       if ((reinterpret_cast<uintptr_t>(lv.depth) | reinterpret_cast<uintptr_t>(lv.box_target)) & 3u) return ODTK_ERR_INVALID;
     }
@@ -727,6 +734,52 @@ int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *lev
   if (rc != ODTK_OK) return rc;
   if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
   quality_dispatch<true>(dtype, qa, total, static_cast<hipStream_t>(stream));
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_rotated_box_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                         int num_anchors, int dtype, int kind, double *sums, void *workspace, size_t workspace_size,
+                                         void *stream) {
+  odtk::BoxIouArgs ba;
+  unsigned total = 0;
+  const int rc = box_iou_fill(ba, false, workspace != nullptr, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, nullptr,
+                              &total, 6);
+  if (rc != ODTK_OK) return rc;
+  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
+  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
+  if (!sums || workspace_size < need || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u))
+    return ODTK_ERR_INVALID;
+  ba.partial = static_cast<double *>(workspace);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    timed_launch(ODTK_KERNEL_LOSS, odtk::rotated_box_loss_forward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
+                 static_cast<hipStream_t>(stream), ba);
+  });
+  ODTK_HIP_TRY(hipGetLastError());
+  odtk::BoxIouReduceArgs ra;
+  std::memset(&ra, 0, sizeof ra);
+  ra.partial = ba.partial;
+  ra.sums = sums;
+  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = ba.block_begin[l];
+  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::box_iou_reduce_kernel, dim3(n_levels), dim3(odtk::kBoxIouThreads), 0,
+               static_cast<hipStream_t>(stream), ra);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+int odtk_rotated_box_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
+                                          int num_anchors, int dtype, int kind, const float *grad_sums, void *stream) {
+  odtk::BoxIouArgs ba;
+  unsigned total = 0;
+  const int rc = box_iou_fill(ba, true, true, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, grad_sums, &total, 6);
+  if (rc != ODTK_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    timed_launch(ODTK_KERNEL_LOSS, odtk::rotated_box_loss_backward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
+                 static_cast<hipStream_t>(stream), ba);
+  });
   ODTK_HIP_TRY(hipGetLastError());
   return ODTK_OK;
 }

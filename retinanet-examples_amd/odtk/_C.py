@@ -37,6 +37,8 @@ SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 ATSS_MAX_TOPK = 16
 BOX_LOSS_IOU, BOX_LOSS_GIOU, BOX_LOSS_DIOU = 1, 2, 3
 BOX_LOSS_KINDS = {'iou': BOX_LOSS_IOU, 'giou': BOX_LOSS_GIOU, 'diou': BOX_LOSS_DIOU}
+ROTATED_BOX_LOSS_PROBIOU, ROTATED_BOX_LOSS_KLD = 1, 2
+ROTATED_BOX_LOSS_KINDS = {'probiou': ROTATED_BOX_LOSS_PROBIOU, 'kld': ROTATED_BOX_LOSS_KLD}
 CLS_LOSS_QFL, CLS_LOSS_VFL = 1, 2
 CLS_LOSS_KINDS = {'qfl': CLS_LOSS_QFL, 'vfl': CLS_LOSS_VFL}
 
@@ -145,6 +147,10 @@ _SIGNATURES = {
                                          [ctypes.c_int] * 4 + [_vp, _vp, _sz, _vp]),
     'odtk_box_iou_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
                                           [ctypes.c_int] * 4 + [_vp, _vp]),
+    'odtk_rotated_box_loss_levels_forward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                             [ctypes.c_int] * 4 + [_vp, _vp, _sz, _vp]),
+    'odtk_rotated_box_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
+                                              [ctypes.c_int] * 4 + [_vp, _vp]),
     'odtk_quality_loss_levels_forward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
                                          [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [_vp, _vp, _sz, _vp]),
     'odtk_quality_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
@@ -885,14 +891,15 @@ def retina_loss_levels_backward(cls_heads, box_heads, depths, box_targets, alpha
     return dcls, dbox
 
 
-def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, grads=None):
-    """Validation and level table shared by the IoU-family box losses -> (descriptors, anchor pointers, the ctypes arrays they
-    point into, levels, batch, anchors, dtype enum, kind enum)."""
+def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, grads=None, nb=4, kinds=BOX_LOSS_KINDS):
+    """Validation and level table shared by the IoU-family box losses (nb = 4 parameters per anchor) and the Gaussian losses of
+    rotated boxes (nb = 6, kinds = ROTATED_BOX_LOSS_KINDS) -> (descriptors, anchor pointers, the ctypes arrays they point into,
+    levels, batch, anchors, dtype enum, kind enum)."""
     n = len(box_heads)
     if not (n == len(depths) == len(box_targets) == len(anchors_list)) or n == 0 or n > MAX_LEVELS:
         raise RuntimeError('%s: need 1..%d levels with matching lists' % (what, MAX_LEVELS))
-    if kind not in BOX_LOSS_KINDS:
-        raise RuntimeError("%s: kind must be 'iou', 'giou' or 'diou', not %r" % (what, kind))
+    if kind not in kinds:
+        raise RuntimeError("%s: kind must be %s, not %r" % (what, "'iou', 'giou' or 'diou'" if nb == 4 else "'probiou' or 'kld'", kind))
     arr = (LossLevel * n)()
     tables = (_fp * n)()
     keep, geo = [], None
@@ -900,8 +907,8 @@ def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, gr
         if not (head.is_cuda and depth.is_cuda and target.is_cuda):
             raise RuntimeError('%s: tensors must be on the GPU' % what)
         if head.dim() != 4 or depth.dim() != 5 or target.dim() != 5 or head.dtype not in _DTYPES:
-            raise RuntimeError('%s: box heads must be [B, A*4, H, W] float32 / bfloat16 / float16, depth [B, A, 1, H, W], '
-                               'box_target [B, A, 4, H, W]' % what)
+            raise RuntimeError('%s: box heads must be [B, A*%d, H, W] float32 / bfloat16 / float16, depth [B, A, 1, H, W], '
+                               'box_target [B, A, %d, H, W]' % (what, nb, nb))
         b, ch, h, w = head.shape
         a = target.shape[1]
         if head.is_contiguous():
@@ -910,7 +917,7 @@ def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, gr
             lay = 1
         else:
             raise RuntimeError('%s: box heads must be dense NCHW or channels_last' % what)
-        if ch != 4 * a or tuple(depth.shape) != (b, a, 1, h, w) or tuple(target.shape) != (b, a, 4, h, w):
+        if ch != nb * a or tuple(depth.shape) != (b, a, 1, h, w) or tuple(target.shape) != (b, a, nb, h, w):
             raise RuntimeError('%s: inconsistent shapes' % what)
         if depth.dtype != torch.float32 or target.dtype != torch.float32 or not depth.is_contiguous() or not target.is_contiguous():
             raise RuntimeError('%s: depth and box_target must be contiguous float32' % what)
@@ -927,7 +934,7 @@ def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, gr
         arr[i].height, arr[i].width, arr[i].channels_last = h, w, lay
         if grads is not None:
             arr[i].dbox = grads[i].data_ptr()
-    return arr, tables, keep, n, geo[0], geo[1], geo[2], BOX_LOSS_KINDS[kind]
+    return arr, tables, keep, n, geo[0], geo[1], geo[2], kinds[kind]
 
 
 def box_iou_loss_levels_forward(box_heads, depths, box_targets, anchors_list, kind):
@@ -955,6 +962,36 @@ def box_iou_loss_levels_backward(box_heads, depths, box_targets, anchors_list, k
                                                               anchors_list, kind, dbox)
     g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
     _launch(library().odtk_box_iou_loss_levels_backward, 'box_iou_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
+            g.data_ptr() if g is not None else None)
+    return dbox
+
+
+def rotated_box_loss_levels_forward(box_heads, depths, box_targets, anchors_list, kind):
+    """ProbIoU / KLD box loss ('probiou' | 'kld') on the Gaussians of rotated boxes, at the foreground anchors of all pyramid
+    levels (csrc/rotated_box_loss.hpp; the definition: odtk/loss.py:rotated_box_loss) -> float64 CUDA tensor [L, 2] = per level
+    (sum of the losses, #foreground).  box_heads [B, A*6, H, W], box_targets [B, A, 6, H, W]; anchors_list: per level the AXIS
+    table [A, 4] of the (axis, rotated) anchor pair.  Two launches, no atomics: the same bits on every run."""
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('rotated_box_loss_levels_forward', box_heads, depths, box_targets,
+                                                              anchors_list, kind, None, 6, ROTATED_BOX_LOSS_KINDS)
+    dev = box_heads[0].device
+    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    _enqueue(library().odtk_rotated_box_loss_levels_forward, 'rotated_box_loss_levels_forward', dev, n, arr, tables, b, a, dtype, code,
+             sums.data_ptr())
+    return sums
+
+
+def rotated_box_loss_levels_backward(box_heads, depths, box_targets, anchors_list, kind, grad_sums):
+    """Gradients of sum_l grad_sums[l] * box_sum[l] w.r.t. every box head (all six deltas), in the heads' dtype and layout, ONE
+    launch.  grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
+    dev = box_heads[0].device
+    dbox = [torch.empty_like(t) for t in box_heads]
+    for g, t in zip(dbox, box_heads):
+        if g.stride() != t.stride():
+            raise RuntimeError('rotated_box_loss_levels_backward: could not allocate gradients in the heads\' layout')
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('rotated_box_loss_levels_backward', box_heads, depths, box_targets,
+                                                              anchors_list, kind, dbox, 6, ROTATED_BOX_LOSS_KINDS)
+    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+    _launch(library().odtk_rotated_box_loss_levels_backward, 'rotated_box_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
             g.data_ptr() if g is not None else None)
     return dbox
 

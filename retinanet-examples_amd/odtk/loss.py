@@ -13,6 +13,10 @@ implementation it is tested against (tests/test_gpu_loss.py) and as the CPU path
 smooth-L1 box loss (`Model.box_loss`): the definition in torch -- the CPU path and the tests' ground truth -- and
 `fused_pyramid_box_iou_loss`, its HIP form over all pyramid levels (csrc/box_iou_loss.hpp).
 
+`rotated_box_loss` (ProbIoU / KLD on the Gaussians of the rotated boxes the six deltas decode to; no reference equivalent) is the
+same for rotated models (`Model.box_loss = 'probiou' | 'kld'`): the definition in torch and `fused_pyramid_rotated_box_loss`, its
+HIP form (csrc/rotated_box_loss.hpp).
+
 `quality_focal_loss` (GFL) and `varifocal_loss` (VarifocalNet) are the opt-in alternatives to the focal loss (`Model.cls_loss`;
 no reference equivalent): the class score is trained towards a soft target -- at a foreground anchor, for the assigned class,
 `box_quality`, the IoU of the predicted and the assigned box, a constant of the loss; 0 everywhere else (`quality_target`).  The
@@ -91,6 +95,64 @@ def anchor_wh(anchors):
     """[A, 4] anchor table (x1, y1, x2, y2) -> [A, 2] = (x2 - x1 + 1, y2 - y1 + 1), what `box_iou_loss` decodes with."""
     anchors = torch.as_tensor(anchors, dtype=torch.float32).reshape(-1, 4)
     return torch.stack([anchors[:, 2] - anchors[:, 0] + 1, anchors[:, 3] - anchors[:, 1] + 1], 1)
+
+
+ROTATED_BOX_LOSS_KINDS = ('probiou', 'kld')
+ROTATED_DIRECTION_EPS = 1e-12
+PROBIOU_EPS = 1e-7
+PROBIOU_MAX_DISTANCE = 100.0
+
+
+def rotated_box_loss(pred, target, anchor_sizes, kind):
+    """ProbIoU / KLD loss of the Gaussians of the rotated boxes that predicted and target deltas decode to; per anchor.
+
+    pred, target [B, A, 6, H, W] deltas (dx, dy, dw, dh, sin, cos); anchor_sizes [A, 2] = (x2 - x1 + 1, y2 - y1 + 1) of the
+    level's AXIS anchor table (`anchor_wh(generate_anchors_rotated(...)[0])`); kind 'probiou' | 'kld' -> [B, A, H, W].  Both
+    boxes are decoded relative to the anchor centre (the cell position cancels), the predicted log-sizes clipped at
+    BBOX_XFORM_CLIP (no gradient beyond it):
+        centre (d0 aw, d1 ah), w = exp(d2) aw, h = exp(d3) ah
+        q = d4^2 + d5^2 + 1e-12;  cc = d5^2 / q, ss = d4^2 / q, sc = d4 d5 / q                     (no atan2, no sqrt)
+        a = (w^2 cc + h^2 ss) / 12    b = (w^2 ss + h^2 cc) / 12    c = -(w^2 - h^2) sc / 12
+    [[a, c], [c, b]] is the covariance of the uniform distribution on the rotated rectangle in the convention of
+    odtk/box.py:rotate_boxes -- width axis (cos, -sin), height axis (sin, cos); three times it is the covariance of the four
+    corners.  With 1 the prediction, 2 the target and (dx, dy) = centre(P) - centre(T):
+        probiou: A = a1 + a2, B = b1 + b2, C = c1 + c2, D = A B - C^2
+                 BD = (B dx^2 + A dy^2 - 2 C dx dy) / (4 D) + 0.5 ln(36 D / (w h tw th)), clamped to [0, 100]
+                 L = sqrt(1 - exp(-BD) + 1e-7)                                         (arXiv 2106.06072)
+        kld:     d2 = (tw th / 12)^2
+                 K = 0.5 [(b2 a1 + a2 b1 - 2 c2 c1) / d2 + (b2 dx^2 + a2 dy^2 - 2 c2 dx dy) / d2 - 2] + ln(tw th / (w h)), clamped at 0
+                 L = 1 - 1 / (1 + ln(1 + K))                                           (KL(N_pred || N_target), arXiv 2106.01883)
+    The clamps hand a NaN on and have no gradient where they bind.  Direction norm: the loss does not depend on the length of
+    (d4, d5), as the decode's atan2(sin, cos) does not; its gradient on the pair is tangential and scales with 1 / sqrt(q), and
+    nothing here pulls the length towards 1.  For w = h the covariance is isotropic and the angle gradient vanishes: a square box
+    is not charged for an angle nobody can see.  The arithmetic runs in pred's dtype (float64 in: the tests' ground truth)."""
+    if kind not in ROTATED_BOX_LOSS_KINDS:
+        raise ValueError("rotated_box_loss: kind must be 'probiou' or 'kld', not {!r}".format(kind))
+    sizes = torch.as_tensor(anchor_sizes, dtype=pred.dtype, device=pred.device)
+    aw, ah = sizes[:, 0].view(1, -1, 1, 1), sizes[:, 1].view(1, -1, 1, 1)
+
+    def gauss(d, clip):
+        lw, lh = (d[:, :, 2].clamp(max=BBOX_XFORM_CLIP), d[:, :, 3].clamp(max=BBOX_XFORM_CLIP)) if clip else (d[:, :, 2], d[:, :, 3])
+        w, h = lw.exp() * aw, lh.exp() * ah
+        q = d[:, :, 4] * d[:, :, 4] + d[:, :, 5] * d[:, :, 5] + ROTATED_DIRECTION_EPS
+        cc, ss, sc = d[:, :, 5] * d[:, :, 5] / q, d[:, :, 4] * d[:, :, 4] / q, d[:, :, 4] * d[:, :, 5] / q
+        w2, h2 = w * w, h * h
+        return d[:, :, 0] * aw, d[:, :, 1] * ah, w, h, (w2 * cc + h2 * ss) / 12, (w2 * ss + h2 * cc) / 12, -(w2 - h2) * sc / 12, lw, lh
+
+    pcx, pcy, pw, ph, a1, b1, c1, plw, plh = gauss(pred, True)
+    tcx, tcy, tw, th, a2, b2, c2, tlw, tlh = gauss(target.to(pred.dtype), False)
+    dx, dy = pcx - tcx, pcy - tcy
+    if kind == 'probiou':
+        A, B, C = a1 + a2, b1 + b2, c1 + c2
+        D = A * B - C * C
+        distance = (B * dx * dx + A * dy * dy - 2 * C * dx * dy) / (4 * D) + 0.5 * torch.log(36 * D / (pw * ph * tw * th))
+        return torch.sqrt(1 - torch.exp(-distance.clamp(min=0, max=PROBIOU_MAX_DISTANCE)) + PROBIOU_EPS)
+    sd = tw * th / 12
+    inv = 1 / (sd * sd)
+    trace = b2 * a1 + a2 * b1 - 2 * c2 * c1
+    mahalanobis = b2 * dx * dx + a2 * dy * dy - 2 * c2 * dx * dy
+    divergence = 0.5 * (trace * inv + mahalanobis * inv - 2) + (tlw + tlh - plw - plh)
+    return 1 - 1 / (1 + torch.log1p(divergence.clamp(min=0)))
 
 
 CLS_LOSS_KINDS = ('qfl', 'vfl')
@@ -289,6 +351,54 @@ def fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, kin
     tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
     return _FusedPyramidBoxIouLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
                                          *[t.contiguous() for t in box_targets])
+
+
+class _FusedPyramidRotatedBoxLoss(torch.autograd.Function):
+    """(box_heads...) of ALL levels -> (box_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward."""
+
+    @staticmethod
+    def forward(ctx, n, kind, anchors_list, *tensors):
+        from . import _C
+        sums = _C.rotated_box_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], anchors_list, kind).float()
+        ctx.save_for_backward(*tensors)
+        ctx.meta = (n, kind, anchors_list)
+        box_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.mark_non_differentiable(foreground)
+        return box_sums, foreground
+
+    @staticmethod
+    def backward(ctx, grad_box_sums, _grad_foreground):
+        from . import _C
+        n, kind, anchors_list = ctx.meta
+        t = ctx.saved_tensors
+        dbox = _C.rotated_box_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], anchors_list, kind, grad_box_sums)
+        return (None, None, None) + tuple(dbox) + (None,) * (2 * n)
+
+
+def fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, anchors_list, kind):
+    """`rotated_box_loss` masked by `depth > 0` and summed, for every pyramid level at once: per-level (box_sums [L], foreground
+    [L]) from the HIP pass of csrc/rotated_box_loss.hpp.  box_heads [B, A*6, H, W] as the convolutions wrote them (float32 /
+    bfloat16 / float16, NCHW or channels_last); depths [B, A, 1, H, W] and box_targets [B, A, 6, H, W] float32 from rotated target
+    assignment; anchors_list: per level the AXIS table [A, 4] -- the [0] of the (axis, rotated) pair of generate_anchors_rotated;
+    the pair itself is accepted too.  Equals, and differentiates like, per level
+
+        (rotated_box_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(axis), kind) * (depth[:, :, 0] > 0)).sum()
+
+    The gradient on a level's (sin, cos) pair is tangential (see `rotated_box_loss`): the loss never changes the pair's length."""
+    from . import _C
+    if kind not in ROTATED_BOX_LOSS_KINDS:
+        raise ValueError("fused_pyramid_rotated_box_loss: kind must be 'probiou' or 'kld', not {!r}".format(kind))
+    if len(box_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
+        groups = [fused_pyramid_rotated_box_loss(box_heads[i:i + _C.MAX_LEVELS], depths[i:i + _C.MAX_LEVELS],
+                                                 box_targets[i:i + _C.MAX_LEVELS], anchors_list[i:i + _C.MAX_LEVELS], kind)
+                  for i in range(0, len(box_heads), _C.MAX_LEVELS)]
+        return tuple(torch.cat(parts) for parts in zip(*groups))
+    heads = [t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) else t.contiguous() for t in box_heads]
+    n = len(heads)
+    axis = [a[0] if isinstance(a, (tuple, list)) and len(a) == 2 and isinstance(a[0], torch.Tensor) else a for a in anchors_list]
+    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in axis)
+    return _FusedPyramidRotatedBoxLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
+                                             *[t.contiguous() for t in box_targets])
 
 
 class _FusedPyramidQualityLoss(torch.autograd.Function):

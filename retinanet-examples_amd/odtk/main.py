@@ -46,6 +46,11 @@ What differs from the reference, and why:
     predicts there and the box it was assigned (odtk/loss.py:quality_focal_loss / varifocal_loss; a HIP pass over the logits that
     computes the target in place, csrc/quality_loss.hpp) -- instead of the reference's focal loss on a one-hot target.  Inference
     is unchanged.  Axis-aligned boxes only.  Never stored in a checkpoint: a resumed run has to be given the flag again.
+  * `--rotated-bbox --box-loss {probiou,kld}` (train) is new: rotated boxes are trained with the ProbIoU or the KLD loss on the
+    Gaussians of the boxes the six deltas decode to (odtk/loss.py:rotated_box_loss; a HIP pass of its own over the foreground
+    anchors, csrc/rotated_box_loss.hpp) instead of the reference's smooth-L1 on (dx, dy, dw, dh, sin, cos), times
+    `--box-loss-weight`.  The loss sees the (sin, cos) pair only through its direction and charges a square box nothing for its
+    angle.  Rotated boxes only; `iou`, `giou` and `diou` stay axis-aligned only.  Never stored in a checkpoint.
 """
 import argparse
 import os
@@ -59,6 +64,7 @@ import torch.multiprocessing
 from . import infer, train
 from .model import Model
 
+ROTATED_BOX_LOSSES = ('probiou', 'kld')                # the --box-loss values that need --rotated-bbox (odtk/loss.py)
 
 def _flag(name, kind=None, default=None, text='', **extra):
     """One row of the flag tables below: (name, argparse keyword arguments)."""
@@ -149,10 +155,11 @@ TRAIN_FLAGS = [
     _flag('--tal-beta', int, argparse.SUPPRESS, 'exponent of the IoU in the task-aligned metric, a whole number in 1..8 (default 6; '
           'needs --assigner tal; give it again when resuming)', metavar='n'),
     _flag('--box-loss', str, argparse.SUPPRESS, 'what the box regression is trained with: smooth-l1 on the four deltas (default), or an '
-          'iou / giou / diou loss on the boxes they decode to (not with --rotated-bbox).  Not stored in the checkpoint: give it again '
-          'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou']),
+          'iou / giou / diou loss on the boxes they decode to (not with --rotated-bbox), or a probiou / kld loss on the Gaussians of the '
+          'rotated boxes the six deltas decode to (only with --rotated-bbox).  Not stored in the checkpoint: give it again '
+          'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou', 'probiou', 'kld']),
     _flag('--box-loss-weight', float, argparse.SUPPRESS, 'factor on the box loss, finite and > 0 (default 1; needs --box-loss iou, '
-          'giou or diou)', metavar='value'),
+          'giou, diou, probiou or kld)', metavar='value'),
     _flag('--cls-loss', str, argparse.SUPPRESS, 'what the class scores are trained with: focal on the one-hot target (default), or the '
           'quality focal (qfl) / varifocal (vfl) loss on the IoU of the predicted and the assigned box (not with --rotated-bbox).  Not '
           'stored in the checkpoint: give it again when resuming', choices=['focal', 'qfl', 'vfl']),
@@ -235,10 +242,13 @@ def parse(args):
         parser.error('--assigner tal is not available with --rotated-bbox')
     if hasattr(parsed, 'box_loss_weight'):
         if getattr(parsed, 'box_loss', 'smooth-l1') == 'smooth-l1':
-            parser.error('--box-loss-weight needs --box-loss iou, giou or diou')
+            parser.error('--box-loss-weight needs --box-loss iou, giou, diou, probiou or kld')
         if not 0 < parsed.box_loss_weight < float('inf'):                         # (a NaN fails both comparisons)
             parser.error('--box-loss-weight must be finite and > 0')
-    if getattr(parsed, 'box_loss', 'smooth-l1') != 'smooth-l1' and getattr(parsed, 'rotated_bbox', False):
+    if getattr(parsed, 'box_loss', 'smooth-l1') in ROTATED_BOX_LOSSES:
+        if not getattr(parsed, 'rotated_bbox', False):
+            parser.error('--box-loss {} needs --rotated-bbox'.format(parsed.box_loss))
+    elif getattr(parsed, 'box_loss', 'smooth-l1') != 'smooth-l1' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--box-loss {} is not available with --rotated-bbox'.format(parsed.box_loss))
     if getattr(parsed, 'cls_loss', 'focal') != 'focal' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--cls-loss {} is not available with --rotated-bbox'.format(parsed.cls_loss))
@@ -336,7 +346,10 @@ def worker(rank, args, world, spawned=False):
             raise RuntimeError('--assigner {} is not available for a model with rotated boxes'.format(model.assigner))
         model.box_loss = getattr(args, 'box_loss', 'smooth-l1').replace('-', '_')
         model.box_loss_weight = getattr(args, 'box_loss_weight', 1.0)
-        if model.box_loss != 'smooth_l1' and args.rotated_bbox:
+        if model.box_loss in ROTATED_BOX_LOSSES:
+            if not model.rotated_bbox:
+                raise RuntimeError('--box-loss {} needs a model with rotated boxes (--rotated-bbox)'.format(args.box_loss))
+        elif model.box_loss != 'smooth_l1' and args.rotated_bbox:
             raise RuntimeError('--box-loss {} is not available for a model with rotated boxes'.format(args.box_loss))
         model.cls_loss = getattr(args, 'cls_loss', 'focal')
         if model.cls_loss != 'focal' and args.rotated_bbox:

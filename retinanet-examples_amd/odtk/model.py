@@ -27,9 +27,9 @@ import torch.nn as nn
 
 from . import backbones as backbones_mod
 from . import box as box_ops
-from .loss import (BOX_LOSS_KINDS, CLS_LOSS_KINDS, FocalLoss, SmoothL1Loss, anchor_wh, box_iou_loss, box_quality,
-                   fused_pyramid_box_iou_loss, fused_pyramid_loss, fused_pyramid_quality_loss, quality_focal_loss, quality_target,
-                   varifocal_loss)
+from .loss import (BOX_LOSS_KINDS, CLS_LOSS_KINDS, ROTATED_BOX_LOSS_KINDS, FocalLoss, SmoothL1Loss, anchor_wh, box_iou_loss, box_quality,
+                   fused_pyramid_box_iou_loss, fused_pyramid_loss, fused_pyramid_quality_loss, fused_pyramid_rotated_box_loss,
+                   quality_focal_loss, quality_target, rotated_box_loss, varifocal_loss)
 
 DEFAULT_RATIOS = [1.0, 2.0, 0.5]
 DEFAULT_SCALES = [4 * 2 ** (i / 3) for i in range(3)]
@@ -105,8 +105,10 @@ class Model(nn.Module):
         self.atss_topk = 9
         self.tal_topk, self.tal_alpha, self.tal_beta = 13, 1, 6
         # what the box regression is trained with: 'smooth_l1' (the reference's loss on the four deltas) or 'iou' | 'giou' | 'diou' on
-        # the boxes the deltas decode to (odtk/loss.py:box_iou_loss, csrc/box_iou_loss.hpp; axis-aligned boxes only), times
-        # `box_loss_weight` (those three only).  Run-time options like `assigner`: never written into checkpoints
+        # the boxes the deltas decode to (odtk/loss.py:box_iou_loss, csrc/box_iou_loss.hpp; axis-aligned boxes only), or 'probiou' |
+        # 'kld' on the Gaussians of the rotated boxes the six deltas decode to (odtk/loss.py:rotated_box_loss,
+        # csrc/rotated_box_loss.hpp; `rotated_bbox` models only), times `box_loss_weight` (every kind but 'smooth_l1').  Run-time
+        # options like `assigner`: never written into checkpoints
         self.box_loss = 'smooth_l1'
         self.box_loss_weight = 1.0
         # what the class scores are trained with: 'focal' (the reference's loss on a one-hot target) or 'qfl' | 'vfl', the quality
@@ -421,20 +423,27 @@ class Model(nn.Module):
         `cls_loss = 'qfl' | 'vfl'` replaces the focal term by the quality focal / varifocal loss on the soft target (odtk/loss.py),
         normalised in the same way.  On the fused path the quality pass then supplies the classification sums and the foreground
         count; `fused_pyramid_loss` is called only while `box_loss` is 'smooth_l1', for its box sum -- its classification half goes
-        unused, as its box half does under an IoU-family `box_loss`."""
+        unused, as its box half does under an IoU-family `box_loss`.  `box_loss = 'probiou' | 'kld'` (rotated models) replaces the
+        smooth-L1 term on the six deltas in the same way, by `rotated_box_loss` / `fused_pyramid_rotated_box_loss`."""
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
         if self.assigner not in ('iou', 'atss', 'tal'):
             raise ValueError("Model.assigner must be 'iou', 'atss' or 'tal', not {!r}".format(self.assigner))
-        iou_kind = None
+        iou_kind, gauss_kind = None, None
         if self.box_loss != 'smooth_l1':
-            if self.box_loss not in BOX_LOSS_KINDS:
-                raise ValueError("Model.box_loss must be 'smooth_l1', 'iou', 'giou' or 'diou', not {!r}".format(self.box_loss))
-            if self.rotated_bbox:
+            if self.box_loss not in BOX_LOSS_KINDS + ROTATED_BOX_LOSS_KINDS:
+                raise ValueError("Model.box_loss must be 'smooth_l1', 'iou', 'giou' or 'diou' (axis-aligned boxes), 'probiou' or 'kld' "
+                                 '(rotated boxes), not {!r}'.format(self.box_loss))
+            if self.box_loss in BOX_LOSS_KINDS and self.rotated_bbox:
                 raise ValueError('Model.box_loss = {!r} is not available for rotated boxes'.format(self.box_loss))
+            if self.box_loss in ROTATED_BOX_LOSS_KINDS and not self.rotated_bbox:
+                raise ValueError('Model.box_loss = {!r} needs a model of rotated boxes (rotated_bbox=True)'.format(self.box_loss))
             weight = self.box_loss_weight
             if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (math.isfinite(weight) and weight > 0):
                 raise ValueError('Model.box_loss_weight must be finite and > 0, not {!r}'.format(weight))
-            iou_kind = self.box_loss
+            if self.rotated_bbox:
+                gauss_kind = self.box_loss
+            else:
+                iou_kind = self.box_loss
         quality_kind = None
         if self.cls_loss != 'focal':
             if self.cls_loss not in CLS_LOSS_KINDS:
@@ -509,6 +518,12 @@ class Model(nn.Module):
                 box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, [self.level_anchors(s) for s in strides],
                                                          iou_kind)
                 return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
+            if gauss_kind is not None:
+                # rotated boxes: the same arrangement with the Gaussian losses (csrc/rotated_box_loss.hpp), on the axis tables
+                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+                box_sums, _ = fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, [self.level_anchors(s)[0] for s in strides],
+                                                             gauss_kind)
+                return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
             return cls_sums.sum() / foreground, box_sums.sum() / foreground
         for level, (cls_head, box_head) in enumerate(zip(cls_heads, box_heads)):
             stride = x.shape[-1] / cls_head.shape[-1]
@@ -530,8 +545,13 @@ class Model(nn.Module):
                 box_loss = box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)), iou_kind)
                 box_total = box_total + (box_loss * (depth[:, :, 0] > 0).float()).sum()
                 continue
+            if gauss_kind is not None:
+                box_loss = rotated_box_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)[0]),
+                                            gauss_kind)
+                box_total = box_total + (box_loss * (depth[:, :, 0] > 0).float()).sum()
+                continue
             box_loss = self.box_criterion(box_head.view_as(box_target).float(), box_target)
             box_total = box_total + (box_loss * (depth > 0).expand_as(box_target).float()).sum()
-        if iou_kind is not None:
+        if iou_kind is not None or gauss_kind is not None:
             return cls_total / foreground, self.box_loss_weight * box_total / foreground
         return cls_total / foreground, box_total / foreground
