@@ -525,6 +525,27 @@ int odtk_gemm_init(const char *hipblaslt_path);
 size_t odtk_gemm_plan_export(char *text, size_t capacity);
 int odtk_gemm_plan_import(const char *text);
 int odtk_gemm_plan_pin_misses(void);
+/*
+ * For tests and tools: what makes the selection observable and forcible (tests/test_gpu_gemm_solutions.py).  None of them launches
+ * anything or changes how a call selects.
+ * odtk_debug_gemm_candidates -- the solutions a plan for the problem chooses from: the heuristic's candidates (up to 16) whose
+ * state is success and whose workspace fits `workspace_size`, as solution indices in heuristic order.  Returns their number and
+ * writes at most `capacity` of them (indices may be NULL when capacity is 0); 0 when the library offers nothing.  Built by the
+ * code the planner itself uses.  ODTK_ERR_INVALID: m, n or k < 1, capacity < 0, NULL indices with capacity > 0;
+ * ODTK_ERR_UNSUPPORTED: another dtype (both decided before the library is touched), or hipBLASLt cannot be bound;
+ * ODTK_ERR_HIP: no device (the library's handle needs one).
+ * odtk_gemm_plan_clear -- destroys every cached plan, forgets every imported line and zeroes the miss count: an import of one
+ * line followed by one call then runs that problem on the named solution.
+ * odtk_gemm_last_solution -- the solution index the most recent odtk_gemm_bias_act of the process ran (-1: none yet) and, in
+ * *origin (may be NULL), how its plan was made.  The GEMM's counterpart of odtk_conv_last_plan in include/odtk_conv.h.
+ */
+#define ODTK_GEMM_ORIGIN_TIMED   0   /* the fastest candidate by the stopwatch                          */
+#define ODTK_GEMM_ORIGIN_PINNED  1   /* named by an imported line                                       */
+#define ODTK_GEMM_ORIGIN_CAPTURE 2   /* first usable candidate: first seen while a stream was captured  */
+int odtk_debug_gemm_candidates(size_t m, int n, int k, int dtype, int relu, int residual, size_t workspace_size,
+                               int *indices, int capacity);
+void odtk_gemm_plan_clear(void);
+int odtk_gemm_last_solution(int *origin);
 int odtk_gemm_bias_act(void *y, const void *x, const void *w, const float *bias, const void *residual,
                        size_t m, int n, int k, int dtype, int relu,
                        void *workspace, size_t workspace_size, void *stream);

@@ -230,6 +230,21 @@ int odtk_gemm_init(const char *hipblaslt_path) { return odtk::lt::init(hipblaslt
 size_t odtk_gemm_plan_export(char *text, size_t capacity) { return odtk::lt::plan_export(text, capacity); }
 int odtk_gemm_plan_import(const char *text) { return odtk::lt::plan_import(text); }
 int odtk_gemm_plan_pin_misses(void) { return odtk::lt::pin_misses(); }
+void odtk_gemm_plan_clear(void) { odtk::lt::plan_clear(); }
+
+int odtk_gemm_last_solution(int *origin) {
+  std::lock_guard<std::mutex> lock(odtk::lt::mutex());
+  if (origin) *origin = odtk::lt::last_solution()[1];
+  return odtk::lt::last_solution()[0];
+}
+
+int odtk_debug_gemm_candidates(size_t m, int n, int k, int dtype, int relu, int residual, size_t workspace_size, int *indices,
+                               int capacity) {
+  if (m == 0 || n <= 0 || k <= 0 || capacity < 0 || (capacity > 0 && !indices)) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  return odtk::lt::candidates(m, static_cast<uint32_t>(n), static_cast<uint32_t>(k), dtype, relu, residual, workspace_size,
+                              indices, capacity);
+}
 
 int odtk_gemm_bias_act(void *y, const void *x, const void *w, const float *bias, const void *residual, size_t m,
                        int n, int k, int dtype, int relu, void *workspace, size_t workspace_size, void *stream) {

@@ -90,6 +90,7 @@ struct Plan {
   hipblasLtMatmulAlgo_t algo;
   size_t workspace = 0;
   bool tuned = true;     // false: chosen without timing (first seen while the stream was being captured)
+  int origin = ODTK_GEMM_ORIGIN_TIMED;   // how the algorithm was chosen (odtk_gemm_last_solution)
 };
 using Key = std::tuple<int, uint64_t, uint32_t, uint32_t, int, int, int>;   // device, m, n, k, dtype, relu, residual
 
@@ -116,14 +117,18 @@ inline int algo_index(const hipblasLtMatmulAlgo_t &algo) {
   std::memcpy(&idx, algo.data, sizeof idx);
   return idx;
 }
+// What the most recent gemm_bias_act of the process ran (odtk_gemm_last_solution): {solution index, origin}; index -1 before the first.
+inline int *last_solution() {
+  static int last[2] = {-1, ODTK_GEMM_ORIGIN_TIMED};
+  return last;
+}
 
-// Build the descriptors and choose the algorithm: ask the heuristic for its candidates and TIME them on
-// the caller's stream with the caller's buffers (the result in `y` is recomputed by the real call right
-// after).  The default pick is tuned for square LLM shapes; these are tall-skinny (m up to 512 000, k and
-// n 64..2048) and the measured best is often not the first.  One-off cost per shape, a few ms.
-inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float *bias, const void *residual,
-                     uint64_t m, uint32_t n, uint32_t k, int dtype, int relu, void *workspace, size_t workspace_size,
-                     hipStream_t stream) {
+// The descriptors of a problem and the heuristic's candidates for it that a plan may take (state success, workspace within
+// `workspace_size`), in heuristic order.  Host only: nothing is launched.  make_plan and the candidate query
+// (odtk_debug_gemm_candidates) both come through here, so what the query lists is what a plan chooses from.  On an error the
+// caller destroys what `p` holds.
+inline int describe(Plan *p, std::vector<hipblasLtMatmulHeuristicResult_t> *usable, const float *bias, uint64_t m, uint32_t n,
+                    uint32_t k, int dtype, int relu, size_t workspace_size) {
   Api &a = api();
   const hipDataType t = dtype == ODTK_BF16 ? HIP_R_16BF : (dtype == ODTK_F16 ? HIP_R_16F : HIP_R_32F);
   if (a.DescCreate(&p->desc, HIPBLAS_COMPUTE_32F, HIP_R_32F) != HIPBLAS_STATUS_SUCCESS) return ODTK_ERR_HIP;
@@ -150,6 +155,33 @@ inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float
   const hipblasStatus_t st = a.Heuristic(a.handle, p->desc, p->a, p->b, p->c, p->c, pref, kAsk, found.data(), &n_found);
   a.PrefDestroy(pref);
   if (st != HIPBLAS_STATUS_SUCCESS || n_found <= 0) return ODTK_ERR_UNSUPPORTED;
+  usable->clear();
+  for (int i = 0; i < n_found; ++i)
+    if (found[i].state == HIPBLAS_STATUS_SUCCESS && found[i].workspaceSize <= workspace_size) usable->push_back(found[i]);
+  return ODTK_OK;
+}
+inline void destroy(Plan *p) {
+  Api &a = api();
+  if (p->a) a.LayoutDestroy(p->a);
+  if (p->b) a.LayoutDestroy(p->b);
+  if (p->c) a.LayoutDestroy(p->c);
+  if (p->desc) a.DescDestroy(p->desc);
+  p->a = p->b = p->c = nullptr;
+  p->desc = nullptr;
+}
+
+// Build the descriptors and choose the algorithm: ask the heuristic for its candidates and TIME them on
+// the caller's stream with the caller's buffers (the result in `y` is recomputed by the real call right
+// after).  The default pick is tuned for square LLM shapes; these are tall-skinny (m up to 512 000, k and
+// n 64..2048) and the measured best is often not the first.  One-off cost per shape, a few ms.
+inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float *bias, const void *residual,
+                     uint64_t m, uint32_t n, uint32_t k, int dtype, int relu, void *workspace, size_t workspace_size,
+                     hipStream_t stream) {
+  Api &a = api();
+  std::vector<hipblasLtMatmulHeuristicResult_t> found;
+  const int rc = describe(p, &found, bias, m, n, k, dtype, relu, workspace_size);
+  if (rc != ODTK_OK) return rc;
+  const int n_found = static_cast<int>(found.size());                    // every one of them usable (describe)
 
   const float alpha = 1.0f, beta = residual ? 1.0f : 0.0f;
   const void *c_ptr = residual ? residual : y;
@@ -157,10 +189,10 @@ inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float
     const auto pin = pinned().find(PinKey{m, n, k, dtype, relu ? 1 : 0, residual ? 1 : 0});
     if (pin != pinned().end()) {                                         // an imported plan names the solution: no stopwatch
       for (int i = 0; i < n_found; ++i) {
-        if (found[i].state != HIPBLAS_STATUS_SUCCESS || found[i].workspaceSize > workspace_size) continue;
         if (algo_index(found[i].algo) != pin->second) continue;
         p->algo = found[i].algo;
         p->workspace = found[i].workspaceSize;
+        p->origin = ODTK_GEMM_ORIGIN_PINNED;
         return ODTK_OK;
       }
       ++pin_misses();                                                    // (another library build: time the candidates as usual)
@@ -172,21 +204,18 @@ inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(stream, &capturing);
   if (capturing != hipStreamCaptureStatusNone) {
-    for (int i = 0; i < n_found; ++i) {
-      if (found[i].state != HIPBLAS_STATUS_SUCCESS || found[i].workspaceSize > workspace_size) continue;
-      p->algo = found[i].algo;
-      p->workspace = found[i].workspaceSize;
-      p->tuned = false;
-      return ODTK_OK;
-    }
-    return ODTK_ERR_UNSUPPORTED;
+    if (n_found == 0) return ODTK_ERR_UNSUPPORTED;
+    p->algo = found[0].algo;
+    p->workspace = found[0].workspaceSize;
+    p->tuned = false;
+    p->origin = ODTK_GEMM_ORIGIN_CAPTURE;
+    return ODTK_OK;
   }
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return ODTK_ERR_HIP;
   float best_ms = 1e30f;
   int best = -1;
   for (int i = 0; i < n_found; ++i) {
-    if (found[i].state != HIPBLAS_STATUS_SUCCESS || found[i].workspaceSize > workspace_size) continue;
     auto run = [&]() {
       return a.Matmul(a.handle, p->desc, &alpha, w, p->a, x, p->b, &beta, c_ptr, p->c, y, p->c, &found[i].algo,
                       workspace, workspace_size, stream);
@@ -206,7 +235,31 @@ inline int make_plan(Plan *p, void *y, const void *x, const void *w, const float
   if (best < 0) return ODTK_ERR_UNSUPPORTED;
   p->algo = found[best].algo;
   p->workspace = found[best].workspaceSize;
+  p->origin = ODTK_GEMM_ORIGIN_TIMED;
   return ODTK_OK;
+}
+
+// The solution indices make_plan would choose from for the problem, in heuristic order -> their number; at most `capacity` of
+// them are written.  Host only.
+inline int candidates(uint64_t m, uint32_t n, uint32_t k, int dtype, int relu, int residual, size_t workspace_size, int *indices,
+                      int capacity) {
+  (void)residual;                                                        // beta * C is no part of the descriptors: same candidates
+  int n_devices = 0;                                                     // the library's handle needs a device: say so, do not let it abort
+  if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return ODTK_ERR_HIP;
+  if (!api().ok) {
+    const int rc = init(nullptr);
+    if (rc != ODTK_OK) return rc;
+  }
+  std::lock_guard<std::mutex> lock(mutex());
+  static const float no_bias = 0.0f;                                     // a non-null bias pointer, as in every real call; never read
+  Plan p;
+  std::vector<hipblasLtMatmulHeuristicResult_t> found;
+  const int rc = describe(&p, &found, &no_bias, m, n, k, dtype, relu, workspace_size);
+  destroy(&p);
+  if (rc == ODTK_ERR_UNSUPPORTED) return 0;
+  if (rc != ODTK_OK) return rc;
+  for (size_t i = 0; i < found.size() && indices && static_cast<int>(i) < capacity; ++i) indices[i] = algo_index(found[i].algo);
+  return static_cast<int>(found.size());
 }
 
 inline int gemm_bias_act(void *y, const void *x, const void *w, const float *bias, const void *residual,
@@ -226,8 +279,7 @@ inline int gemm_bias_act(void *y, const void *x, const void *w, const float *bia
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &capturing);
     if (capturing == hipStreamCaptureStatusNone) {
-      Api &a = api();
-      a.LayoutDestroy(it->second.a); a.LayoutDestroy(it->second.b); a.LayoutDestroy(it->second.c); a.DescDestroy(it->second.desc);
+      destroy(&it->second);
       plans().erase(it);
       it = plans().end();
     }
@@ -236,11 +288,7 @@ inline int gemm_bias_act(void *y, const void *x, const void *w, const float *bia
     Plan p;
     const int rc = make_plan(&p, y, x, w, bias, residual, m, n, k, dtype, relu, workspace, workspace_size, stream);
     if (rc != ODTK_OK) {                           // nothing half-built stays behind
-      Api &a = api();
-      if (p.a) a.LayoutDestroy(p.a);
-      if (p.b) a.LayoutDestroy(p.b);
-      if (p.c) a.LayoutDestroy(p.c);
-      if (p.desc) a.DescDestroy(p.desc);
+      destroy(&p);
       return rc;
     }
     it = plans().emplace(key, p).first;
@@ -251,7 +299,19 @@ inline int gemm_bias_act(void *y, const void *x, const void *w, const float *bia
   const float alpha = 1.0f, beta = residual ? 1.0f : 0.0f;
   const hipblasStatus_t st = a.Matmul(a.handle, p.desc, &alpha, w, p.a, x, p.b, &beta, residual ? residual : y, p.c, y,
                                       p.c, &p.algo, workspace, workspace_size, stream);
+  last_solution()[0] = algo_index(p.algo);
+  last_solution()[1] = p.origin;
   return st == HIPBLAS_STATUS_SUCCESS ? ODTK_OK : ODTK_ERR_HIP;
+}
+
+// For tests and tools: forget every cached plan (with its layouts and descriptor), every imported pin and the miss count, so that
+// plan_import of one line followed by one call forces that solution for that problem.
+inline void plan_clear() {
+  std::lock_guard<std::mutex> lock(mutex());
+  for (auto &kv : plans()) destroy(&kv.second);
+  plans().clear();
+  pinned().clear();
+  pin_misses() = 0;
 }
 
 // "gemm m n k dtype relu residual solution-index" per tuned problem (any device).  Returns the bytes the text needs (NUL included);

@@ -195,6 +195,10 @@ _SIGNATURES = {
     'odtk_gemm_plan_export': (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
     'odtk_gemm_plan_import': (ctypes.c_int, [ctypes.c_char_p]),
     'odtk_gemm_plan_pin_misses': (ctypes.c_int, []),
+    'odtk_debug_gemm_candidates': (ctypes.c_int, [ctypes.c_size_t] + [ctypes.c_int] * 5 + [ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.c_int]),
+    'odtk_gemm_plan_clear': (None, []),
+    'odtk_gemm_last_solution': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     'odtk_gemm_bias_act': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
@@ -1453,6 +1457,32 @@ def library_plans_import(text):
 
 def gemm_plan_pin_misses():
     return library().odtk_gemm_plan_pin_misses()
+
+
+GEMM_ORIGINS = ('timed', 'pinned', 'capture')          # include/odtk_hip.h: ODTK_GEMM_ORIGIN_*
+
+
+def gemm_candidates(m, n, k, dtype, relu, residual, workspace_size=32 << 20):
+    """Debug: the hipBLASLt solution indices a plan for the problem chooses from, in heuristic order (host only, nothing is
+    launched).  `dtype` is a torch dtype; the default workspace is the 32 MiB `gemm_bias_act` passes."""
+    if not gemm_available():
+        raise RuntimeError('gemm_candidates: hipBLASLt could not be bound (odtk_gemm_init failed)')
+    out = (ctypes.c_int * 16)()
+    n_found = _check(library().odtk_debug_gemm_candidates(m, n, k, _DTYPES[dtype], 1 if relu else 0, 1 if residual else 0,
+                                                          workspace_size, out, 16), 'gemm_candidates')
+    return list(out[:min(n_found, 16)])
+
+
+def gemm_plan_clear():
+    """Debug: forget every cached GEMM plan, every imported `gemm` line and the miss count."""
+    library().odtk_gemm_plan_clear()
+
+
+def gemm_last_solution():
+    """-> (solution index of the most recent gemm_bias_act of the process, or -1; 'timed' | 'pinned' | 'capture')."""
+    origin = ctypes.c_int(0)
+    index = library().odtk_gemm_last_solution(ctypes.byref(origin))
+    return index, GEMM_ORIGINS[origin.value]
 
 
 def loss_tuning(which, fp32_heads, threads, blocks_per_cu, unroll, box_blocks):

@@ -167,6 +167,39 @@ def test_new_entry_points_validate_before_touching_the_device():
     assert lib.odtk_prefilter_thresholds(4096, 720, _C.F32, 0.05, 8192, None) == _C.ERR_UNSUPPORTED
 
 
+def test_gemm_selection_hooks_validate_on_the_host_and_need_a_device_for_the_rest():
+    """odtk_debug_gemm_candidates / odtk_gemm_plan_clear / odtk_gemm_last_solution: declared, exported, arguments checked before
+    the library is touched.  The candidate query itself needs hipBLASLt's handle, hence a device: without one it returns
+    ODTK_ERR_HIP instead of letting the library abort; with one, NULL indices and capacity 0 give the count."""
+    lib = _C.library()
+    header = open(os.path.join(ROOT, 'include', 'odtk_hip.h')).read()
+    for name in ('odtk_debug_gemm_candidates', 'odtk_gemm_plan_clear', 'odtk_gemm_last_solution'):
+        assert re.search(r'\b%s\s*\(' % name, header) and name in _C.exported_symbols() and hasattr(lib, name)
+    ws = 32 << 20
+    assert lib.odtk_debug_gemm_candidates(231, 256, 64, 9, 1, 0, ws, None, 0) == _C.ERR_UNSUPPORTED
+    assert lib.odtk_debug_gemm_candidates(231, 0, 64, _C.BF16, 1, 0, ws, None, 0) == _C.ERR_INVALID
+    assert lib.odtk_debug_gemm_candidates(231, 256, -1, _C.BF16, 1, 0, ws, None, 0) == _C.ERR_INVALID
+    assert lib.odtk_debug_gemm_candidates(0, 256, 64, _C.BF16, 1, 0, ws, None, 0) == _C.ERR_INVALID
+    assert lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, ws, None, 4) == _C.ERR_INVALID          # NULL with capacity > 0
+    assert lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, ws, (ctypes.c_int * 4)(), -1) == _C.ERR_INVALID
+    if torch.cuda.is_available():
+        assert _C.gemm_available()
+        count = lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, ws, None, 0)
+        assert 0 < count <= 16
+        two = (ctypes.c_int * 3)(-1, -1, -7)
+        assert lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, ws, two, 2) == count         # the count, not what was written
+        assert two[2] == -7 and two[0] >= 0 and (count < 2 or two[1] >= 0)
+        assert _C.gemm_candidates(231, 256, 64, torch.bfloat16, True, False)[:2] == list(two[:min(count, 2)])
+        assert lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, 0, None, 0) <= count           # no workspace: no more of them
+    else:
+        assert lib.odtk_debug_gemm_candidates(231, 256, 64, _C.BF16, 1, 0, ws, None, 0) == _C.ERR_HIP
+    assert _C.gemm_last_solution()[1] in _C.GEMM_ORIGINS and lib.odtk_gemm_last_solution(None) == _C.gemm_last_solution()[0]
+    if not torch.cuda.is_available():           # (with a device the process may hold other tests' plans and pins: left alone here,
+        assert lib.odtk_gemm_plan_import(b'gemm 231 256 64 1 1 0 5\nconv 1 2 3\n') == 1      # tests/test_gpu_gemm_solutions.py clears)
+        _C.gemm_plan_clear()
+        assert _C.gemm_plan_pin_misses() == 0 and lib.odtk_gemm_plan_export(None, 0) == 1
+
+
 def test_target_assignment_entry_points_validate_before_touching_the_device():
     """odtk_snap_to_anchors / _levels / _rotated_levels refuse on the host what their kernels cannot index or were never given:
     a level of more than 2^31 - 1 anchor cells (the kernels hold the cell index in an int), 0 or more than ODTK_MAX_LEVELS levels,
