@@ -255,10 +255,7 @@ __global__ __launch_bounds__(kAtssThreads) void atss_assign_kernel(const AtssArg
   __shared__ int s_pos[kAtssRound];                           // row of the round -> its place among the valid ones, or -1
   __shared__ int s_n;
 
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < a.n_levels && blockIdx.x >= a.block_begin[i]) l = i;
+  const int l = level_of<ODTK_MAX_LEVELS>(a.block_begin, a.n_levels);
   const AtssLevel &lv = a.lv[l];
   const int b = blockIdx.y;
   const float *tg = a.targets + static_cast<size_t>(b) * a.n_max * 5;

@@ -20,42 +20,23 @@
 // does through smooth-L1; cells that are not foreground are never read from the head.
 // Arithmetic: IEEE float32 per anchor, ocml expf, the gradient in closed form (reverse mode by hand, below).
 //
-// Shape: two launches for all levels (the level table and the anchor SIZES travel in the kernel arguments), both over one lane
-// per anchor cell -- ~1 % of the lanes have work; the launches are bound by the depth read (forward) and the gradient write.
+// Shape: cell_loss.hpp's kernels with the policy BoxIouLoss (below) -- two launches for all levels (the level table and the anchor
+// SIZES travel in the kernel arguments), both over one lane per anchor cell -- ~1 % of the lanes have work; the launches are
+// bound by the depth read (forward) and the gradient write.
 //   forward : lanes in depth's order (image, anchor, pixel): the depth read is coalesced; a foreground lane gathers its 4 + 4
 //             deltas (NHWC: one vector of the head; NCHW: four planes).  Wave sum in double, one pair (sum, fg) per workgroup into
-//             the workspace, then box_iou_reduce_kernel adds the pairs of a level up in a fixed order.  No atomics.
+//             the workspace, then level_pair_reduce_kernel adds the pairs of a level up in a fixed order.  No atomics.
 //   backward: lanes in the order d(deltas) lies in memory -- NCHW: (image, anchor, pixel), four plane stores of consecutive
 //             elements per wave; NHWC: (image, pixel, anchor), ONE 16- / 8-byte vector per lane, a wave's stores one run.
 // Measured: DESIGN.md (tools/box_iou_loss_probe.py, profiles/r11_box_iou_loss_probe.txt).
 #pragma once
 
-#include "loss.hpp"   // store_elem, store_vec4, box_grad_value, block_sum; element types; fastdiv
+#include "cell_loss.hpp"   // CellLossLevel, the kernels that take BoxIouLoss; loss.hpp: store_vec4, box_grad_value, element types
 
 namespace odtk {
 
-constexpr int kBoxIouThreads = 256;
 constexpr float kBoxIouClip = 4.135166556742356f;     // log(1000 / 16): Detectron's BBOX_XFORM_CLIP
 constexpr float kBoxIouEps = 1e-7f;
-
-struct BoxIouLevel {
-  const void *box;          // [B, A*4, H, W] predicted deltas, element type T
-  const float *depth;       // [B, A, 1, H, W]
-  const float *box_target;  // [B, A, 4, H, W]
-  void *dbox;               // backward: gradient, dtype / layout of box
-  const float *g;           // backward: device scalar d(out)/d(box_sum) of this level (null: 0)
-  uint32_t hw, cells;       // H*W, B*A*H*W (4 * cells < 2^31: host)
-  uint32_t channels_last, pad_;
-  FastDiv by_hw, by_anchors;
-  float aw[ODTK_MAX_ANCHORS], ah[ODTK_MAX_ANCHORS];
-};
-
-struct BoxIouArgs {
-  BoxIouLevel lv[ODTK_MAX_LEVELS];
-  uint32_t block_begin[ODTK_MAX_LEVELS + 1];
-  double *partial;          // forward: [gridDim.x][2] = (sum, fg) per workgroup
-  uint32_t n_levels, num_anchors, kind, pad_;
-};
 
 // min / max that hand a NaN of either side on (fminf / fmaxf drop it)
 __device__ __forceinline__ float nan_min(float a, float b) { return (a < b || a != a) ? a : b; }
@@ -118,7 +99,7 @@ __device__ __forceinline__ float box_iou_term(const float *p, const float *t, fl
 
 // the four deltas of cell (image, anchor `an`, pixel) with ia = image * A + an: NHWC one vector, NCHW four planes
 template <typename T>
-__device__ __forceinline__ void box_iou_load(const BoxIouLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
+__device__ __forceinline__ void box_iou_load(const CellLossLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
   const uint32_t plane = ia * 4u * L.hw + pix;
 #pragma unroll
   for (uint32_t k = 0; k < 4; ++k) t[k] = L.box_target[plane + k * L.hw];
@@ -140,93 +121,21 @@ __device__ __forceinline__ void box_iou_load(const BoxIouLevel &L, uint32_t A, u
   }
 }
 
-__device__ __forceinline__ int box_iou_level_of(const BoxIouArgs &a) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < static_cast<int>(a.n_levels) && blockIdx.x >= a.block_begin[i]) l = i;
-  return l;
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBoxIouThreads) void box_iou_loss_forward_kernel(const BoxIouArgs a) {
-  __shared__ double s_red[kBoxIouThreads / kWave];
-  const int l = box_iou_level_of(a);
-  const BoxIouLevel &L = a.lv[l];
-  const uint32_t cell = (blockIdx.x - a.block_begin[l]) * kBoxIouThreads + threadIdx.x;   // (image * A + an) * hw + pix
-  double loss = 0.0, fg = 0.0;
-  if (cell < L.cells && L.depth[cell] > 0.0f) {
-    uint32_t pix, an;
-    const uint32_t ia = fastdivmod(cell, L.by_hw, &pix);
-    fastdivmod(ia, L.by_anchors, &an);
-    float p[4], t[4];
-    box_iou_load<T>(L, a.num_anchors, ia, an, pix, p, t);
-    loss = box_iou_term<false>(p, t, L.aw[an], L.ah[an], a.kind, nullptr);
-    fg = 1.0;
-  }
-  const double s = block_sum(loss, s_red);
-  const double f = block_sum(fg, s_red);
-  if (threadIdx.x == 0) {
-    a.partial[2 * static_cast<size_t>(blockIdx.x)] = s;
-    a.partial[2 * static_cast<size_t>(blockIdx.x) + 1] = f;
-  }
-}
-
-// Workgroup l adds up the pairs of level l: thread t takes workgroups t, t + 256, ... in order, then the wave / block tree.
-struct BoxIouReduceArgs {
-  const double *partial;
-  double *sums;                                // [n_levels][2] = (box_sum, fg)
-  uint32_t block_begin[ODTK_MAX_LEVELS + 1];
-};
-
-__global__ __launch_bounds__(kBoxIouThreads) void box_iou_reduce_kernel(const BoxIouReduceArgs a) {
-  __shared__ double s_red[kBoxIouThreads / kWave];
-  const uint32_t l = blockIdx.x, b1 = a.block_begin[l + 1];
-  double s = 0.0, f = 0.0;
-  for (uint32_t b = a.block_begin[l] + threadIdx.x; b < b1; b += kBoxIouThreads) {
-    s += a.partial[2 * static_cast<size_t>(b)];
-    f += a.partial[2 * static_cast<size_t>(b) + 1];
-  }
-  s = block_sum(s, s_red);
-  f = block_sum(f, s_red);
-  if (threadIdx.x == 0) {
-    a.sums[2 * l] = s;
-    a.sums[2 * l + 1] = f;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBoxIouThreads) void box_iou_loss_backward_kernel(const BoxIouArgs a) {
-  const int l = box_iou_level_of(a);
-  const BoxIouLevel &L = a.lv[l];
-  const uint32_t cell = (blockIdx.x - a.block_begin[l]) * kBoxIouThreads + threadIdx.x;
-  if (cell >= L.cells) return;
-  const uint32_t A = a.num_anchors;
-  uint32_t ia, an, pix;
-  if (L.channels_last) {                                   // (launch-uniform per workgroup) cell = (image * hw + pix) * A + an
-    const uint32_t ip = fastdivmod(cell, L.by_anchors, &an);
-    const uint32_t img = fastdivmod(ip, L.by_hw, &pix);
-    ia = img * A + an;
-  } else {                                                 // cell = (image * A + an) * hw + pix
-    ia = fastdivmod(cell, L.by_hw, &pix);
-    fastdivmod(ia, L.by_anchors, &an);
-  }
-  float out[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (L.depth[ia * L.hw + pix] > 0.0f) {
-    const float g = L.g ? *L.g : 0.0f;
-    float p[4], t[4], grad[4];
+// The IoU family as cell_loss.hpp's kernels see it.
+struct BoxIouLoss {
+  static constexpr uint32_t kParams = 4;
+  using Grad = float;
+  template <typename T>
+  static __device__ __forceinline__ void load(const CellLossLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
     box_iou_load<T>(L, A, ia, an, pix, p, t);
-    box_iou_term<true>(p, t, L.aw[an], L.ah[an], a.kind, grad);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = box_grad_value(g, grad[k]);
   }
-  if (L.channels_last) {
-    store_vec4<T>(L.dbox, cell, out);
-  } else {
-    const uint32_t plane = ia * 4u * L.hw + pix;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) store_elem<T>(L.dbox, plane + k * L.hw, out[k]);
+  template <bool kGrad>
+  static __device__ __forceinline__ float term(const float *p, const float *t, float aw, float ah, uint32_t kind, float *grad) {
+    return box_iou_term<kGrad>(p, t, aw, ah, kind, grad);
   }
-}
+  static __device__ __forceinline__ float grad_value(float g, float grad) { return box_grad_value(g, grad); }
+  template <typename T>
+  static __device__ __forceinline__ void store_cell(void *base, uint32_t cell, const float *v) { store_vec4<T>(base, cell, v); }   // ONE 16- / 8-byte vector
+};
 
 }  // namespace odtk

@@ -35,6 +35,20 @@ __device__ __forceinline__ float key_score(uint64_t k) { return ordered_to_float
 __device__ __forceinline__ uint32_t key_index(uint64_t k) { return ~static_cast<uint32_t>(k); }
 
 // ---------------------------------------------------------------------------------------
+// One launch over several levels: the workgroups of entry l are [block_begin[l], block_begin[l + 1]).
+// -> the entry of this workgroup, the last i < n with blockIdx.x >= block_begin[i].  kMax compares, not a search and
+// not indexed: the table stays in the kernel's scalar arguments.
+// ---------------------------------------------------------------------------------------
+template <int kMax, typename N>
+__device__ __forceinline__ int level_of(const uint32_t (&block_begin)[kMax + 1], const N &n) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < kMax; ++i)
+    if (i < static_cast<int>(n) && blockIdx.x >= block_begin[i]) l = i;
+  return l;
+}
+
+// ---------------------------------------------------------------------------------------
 // wave64 helpers
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }

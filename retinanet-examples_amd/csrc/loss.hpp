@@ -516,10 +516,7 @@ struct LossLevelsArgs {
 template <typename T, bool kBackward, int kUnroll, int kForm>
 __global__ __launch_bounds__(kLossMaxThreads) void retina_loss_kernel(const LossLevelsArgs a) {
   __shared__ double s_red[kLossMaxThreads / kWave];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < a.n_levels && blockIdx.x >= a.block_begin[i]) l = i;
+  const int l = level_of<ODTK_MAX_LEVELS>(a.block_begin, a.n_levels);
   retina_loss_block<T, kBackward, kUnroll, kForm>(a.lv[l], blockIdx.x - a.block_begin[l], a.block_begin[l + 1] - a.block_begin[l], s_red);
 }
 

@@ -27,19 +27,19 @@
 // box_iou_term<false> in place -- no quality map, no target tensor, no extra launch; backward recomputes q the same way.  With
 // gamma = 2 every other vector without a logit beyond kPlainMax takes focal_plain with one weight for the launch.  Class counts
 // that are no multiple of the vector, levels whose H*W is not, and the n % kPer tail go element by element with carries.
-// Forward: per-workgroup (cls_sum, fg) into the workspace, then box_iou_reduce_kernel adds a level's pairs up in a fixed order.
+// Forward: per-workgroup (cls_sum, fg) into the workspace, then level_pair_reduce_kernel adds a level's pairs up in a fixed order.
 // The foreground count is taken where the walk meets class 0 of an anchor (every anchor has exactly one such element).
 // No atomics, no scratch.  Measured: DESIGN.md (tools/quality_loss_probe.py, profiles/r12_quality_loss_probe.txt).
 #pragma once
 
-#include "box_iou_loss.hpp"   // box_iou_load, box_iou_term, BoxIouLevel, box_iou_reduce_kernel; loss.hpp: focal_term, focal_plain, ...
+#include "box_iou_loss.hpp"   // box_iou_load, box_iou_term; cell_loss.hpp: CellLossLevel, store_block_pair, level_pair_reduce_kernel; loss.hpp: focal_term, ...
 
 namespace odtk {
 
 constexpr int kQualityThreads = 256;
 
 struct QualityLevel {
-  BoxIouLevel b;            // box, depth, box_target, g (backward: device scalar d(out)/d(cls_sum)), hw, channels_last, by_hw,
+  CellLossLevel b;           // box, depth, box_target, g (backward: device scalar d(out)/d(cls_sum)), hw, channels_last, by_hw,
                             // by_anchors, the anchor sizes; dbox is never written and stays null
   const void *cls;          // [B, A*C, H, W] logits, element type T, layout of box
   void *dcls;               // backward: gradient, dtype / layout of cls
@@ -59,7 +59,7 @@ struct QualityArgs {
 template <typename T>
 __device__ __forceinline__ float quality_at(const QualityLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix) {
   float p[4], t[4];
-  box_iou_load<T>(L.b, A, ia, an, pix, p, t);
+  box_iou_load<T>(L.b, A, ia, an, pix, p, t);                     // what BoxIouLoss::load / ::term forward to
   return 1.0f - box_iou_term<false>(p, t, L.b.aw[an], L.b.ah[an], ODTK_BOX_LOSS_IOU, nullptr);
 }
 
@@ -290,10 +290,7 @@ __device__ __forceinline__ double quality_stream(const QualityLevel &L, const Qu
 template <typename T, bool kBackward, int kUnroll>
 __global__ __launch_bounds__(kQualityThreads) void quality_loss_kernel(const QualityArgs a) {
   __shared__ double s_red[kQualityThreads / kWave];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < static_cast<int>(a.n_levels) && blockIdx.x >= a.block_begin[i]) l = i;
+  const int l = level_of<ODTK_MAX_LEVELS>(a.block_begin, a.n_levels);
   const QualityLevel &L = a.lv[l];
   const uint32_t block = blockIdx.x - a.block_begin[l], n_blocks = a.block_begin[l + 1] - a.block_begin[l];
   const bool g2 = a.gamma == 2.0f;                         // launch-uniform
@@ -303,14 +300,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_loss_kernel(const Qua
                                   : quality_stream<T, kBackward, false, true, kUnroll>(L, a, block, n_blocks, &fg);
   else acc = g2 ? quality_stream<T, kBackward, true, false, kUnroll>(L, a, block, n_blocks, &fg)
                 : quality_stream<T, kBackward, false, false, kUnroll>(L, a, block, n_blocks, &fg);
-  if constexpr (!kBackward) {
-    const double s = block_sum(acc, s_red);
-    const double f = block_sum(fg, s_red);
-    if (threadIdx.x == 0) {
-      a.partial[2 * static_cast<size_t>(blockIdx.x)] = s;
-      a.partial[2 * static_cast<size_t>(blockIdx.x) + 1] = f;
-    }
-  }
+  if constexpr (!kBackward) store_block_pair(acc, fg, s_red, a.partial);
 }
 
 }  // namespace odtk

@@ -33,8 +33,8 @@
 // (cx, cy, w, h, a, b, c), the kind's scalar loss with its partials by (dx, dy, a1, b1, c1, w, h), one common chain to the deltas.
 // Nothing here forms D^2: d(BD)/dD is written as (1/2 - t1) / D.
 //
-// Shape: that of box_iou_loss.hpp, whose argument structs (with six parameters per anchor), level lookup and reduce kernel are
-// used as they are -- two launches for all levels, one lane per anchor cell, ~1 % of the lanes with work.
+// Shape: cell_loss.hpp's kernels with the policy RotatedBoxLoss (below; six parameters per anchor) -- two launches for all levels
+// and the fixed-order sum, one lane per anchor cell, ~1 % of the lanes with work.
 //   forward : lanes in depth's order (image, anchor, pixel); a foreground lane gathers its 6 + 6 deltas.
 //   backward: lanes in the order d(deltas) lies in memory -- NCHW: (image, anchor, pixel), six plane stores; NHWC: (image, pixel,
 //             anchor), the cell's 24 (fp32) or 12 (16-bit) bytes as THREE 8- / 4-byte pieces per lane (a cell is 8- / 4-byte
@@ -42,7 +42,7 @@
 // Measured: DESIGN.md (tools/rotated_box_loss_probe.py).
 #pragma once
 
-#include "box_iou_loss.hpp"   // BoxIouArgs / BoxIouLevel, box_iou_level_of, box_iou_reduce_kernel, kBoxIouThreads
+#include "box_iou_loss.hpp"   // nan_min / nan_max in float; cell_loss.hpp: CellLossLevel, the kernels that take RotatedBoxLoss
 
 namespace odtk {
 
@@ -156,7 +156,7 @@ __device__ __forceinline__ double rotated_box_term(const float *pf, const float 
 
 // the six deltas of cell (image, anchor `an`, pixel) with ia = image * A + an: NHWC three 8- / 4-byte pieces, NCHW six planes
 template <typename T>
-__device__ __forceinline__ void rotated_box_load(const BoxIouLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
+__device__ __forceinline__ void rotated_box_load(const CellLossLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
   const uint32_t plane = ia * 6u * L.hw + pix;
 #pragma unroll
   for (uint32_t k = 0; k < 6; ++k) t[k] = L.box_target[plane + k * L.hw];
@@ -202,63 +202,22 @@ __device__ __forceinline__ void store_vec6(void *base, uint32_t cell, const floa
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBoxIouThreads) void rotated_box_loss_forward_kernel(const BoxIouArgs a) {
-  __shared__ double s_red[kBoxIouThreads / kWave];
-  const int l = box_iou_level_of(a);
-  const BoxIouLevel &L = a.lv[l];
-  const uint32_t cell = (blockIdx.x - a.block_begin[l]) * kBoxIouThreads + threadIdx.x;   // (image * A + an) * hw + pix
-  double loss = 0.0, fg = 0.0;
-  if (cell < L.cells && L.depth[cell] > 0.0f) {
-    uint32_t pix, an;
-    const uint32_t ia = fastdivmod(cell, L.by_hw, &pix);
-    fastdivmod(ia, L.by_anchors, &an);
-    float p[6], t[6];
-    rotated_box_load<T>(L, a.num_anchors, ia, an, pix, p, t);
-    loss = rotated_box_term<false>(p, t, L.aw[an], L.ah[an], a.kind, nullptr);
-    fg = 1.0;
-  }
-  const double s = block_sum(loss, s_red);
-  const double f = block_sum(fg, s_red);
-  if (threadIdx.x == 0) {
-    a.partial[2 * static_cast<size_t>(blockIdx.x)] = s;
-    a.partial[2 * static_cast<size_t>(blockIdx.x) + 1] = f;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBoxIouThreads) void rotated_box_loss_backward_kernel(const BoxIouArgs a) {
-  const int l = box_iou_level_of(a);
-  const BoxIouLevel &L = a.lv[l];
-  const uint32_t cell = (blockIdx.x - a.block_begin[l]) * kBoxIouThreads + threadIdx.x;
-  if (cell >= L.cells) return;
-  const uint32_t A = a.num_anchors;
-  uint32_t ia, an, pix;
-  if (L.channels_last) {                                   // (launch-uniform per workgroup) cell = (image * hw + pix) * A + an
-    const uint32_t ip = fastdivmod(cell, L.by_anchors, &an);
-    const uint32_t img = fastdivmod(ip, L.by_hw, &pix);
-    ia = img * A + an;
-  } else {                                                 // cell = (image * A + an) * hw + pix
-    ia = fastdivmod(cell, L.by_hw, &pix);
-    fastdivmod(ia, L.by_anchors, &an);
-  }
-  float out[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if (L.depth[ia * L.hw + pix] > 0.0f) {
-    const double g = L.g ? *L.g : 0.0f;
-    float p[6], t[6];
-    double grad[6];
+// The Gaussian family as cell_loss.hpp's kernels see it.
+struct RotatedBoxLoss {
+  static constexpr uint32_t kParams = 6;
+  using Grad = double;
+  template <typename T>
+  static __device__ __forceinline__ void load(const CellLossLevel &L, uint32_t A, uint32_t ia, uint32_t an, uint32_t pix, float *p, float *t) {
     rotated_box_load<T>(L, A, ia, an, pix, p, t);
-    rotated_box_term<true>(p, t, L.aw[an], L.ah[an], a.kind, grad);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) out[k] = static_cast<float>(g * grad[k] + 0.0);   // the product in double, one rounding; a zero always +0
   }
-  if (L.channels_last) {
-    store_vec6<T>(L.dbox, cell, out);
-  } else {
-    const uint32_t plane = ia * 6u * L.hw + pix;
-#pragma unroll
-    for (uint32_t k = 0; k < 6; ++k) store_elem<T>(L.dbox, plane + k * L.hw, out[k]);
+  template <bool kGrad>
+  static __device__ __forceinline__ double term(const float *p, const float *t, float aw, float ah, uint32_t kind, double *grad) {
+    return rotated_box_term<kGrad>(p, t, aw, ah, kind, grad);
   }
-}
+  // the product in double, one rounding; a zero always +0
+  static __device__ __forceinline__ float grad_value(float g, double grad) { return static_cast<float>(static_cast<double>(g) * grad + 0.0); }
+  template <typename T>
+  static __device__ __forceinline__ void store_cell(void *base, uint32_t cell, const float *v) { store_vec6<T>(base, cell, v); }   // THREE 8- / 4-byte pieces
+};
 
 }  // namespace odtk

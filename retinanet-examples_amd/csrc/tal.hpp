@@ -274,10 +274,7 @@ __global__ __launch_bounds__(kTalThreads) void tal_select_kernel(const TalArgs a
 }
 
 __global__ __launch_bounds__(kTalFillThreads) void tal_fill_kernel(const TalFillArgs a) {
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < kTalFillSegments; ++i)
-    if (i < a.n_segments && blockIdx.x >= a.block_begin[i]) s = i;
+  const int s = level_of<kTalFillSegments>(a.block_begin, a.n_segments);
   float *p = a.ptr[s];
   const unsigned long long n = a.count[s];
   const uint32_t blk = blockIdx.x - a.block_begin[s], blocks = a.block_begin[s + 1] - a.block_begin[s];

@@ -138,10 +138,7 @@ struct SnapLevelsArgs {
 static_assert(sizeof(SnapLevelsArgs) <= 4096, "kernel arguments travel by value");
 
 __global__ __launch_bounds__(kSnapThreads) void snap_to_anchors_levels_kernel(const SnapLevelsArgs a) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < a.n_levels && blockIdx.x >= a.block_begin[i]) l = i;
+  const int l = level_of<ODTK_MAX_LEVELS>(a.block_begin, a.n_levels);
   snap_to_anchors_block(a.lv[l], static_cast<int>(blockIdx.x - a.block_begin[l]));
 }
 
@@ -185,10 +182,7 @@ __global__ __launch_bounds__(kSnapThreads) void snap_to_anchors_rotated_levels_k
   __shared__ float2 s_clip[(kSnapThreads / kWave) * kClipSlotsPerWave];
   float2 *clip = s_clip + (threadIdx.x >> 6) * kClipSlotsPerWave + (threadIdx.x & 63);
 
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < ODTK_MAX_LEVELS; ++i)
-    if (i < args.n_levels && blockIdx.x >= args.block_begin[i]) l = i;
+  const int l = level_of<ODTK_MAX_LEVELS>(args.block_begin, args.n_levels);
   const SnapRotArgs &a = args.lv[l];
   const int block_in_level = static_cast<int>(blockIdx.x - args.block_begin[l]);
   const int b = blockIdx.y;

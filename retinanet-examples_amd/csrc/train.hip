@@ -10,7 +10,7 @@
 #include "atss.hpp"
 #include "tal.hpp"
 #include "loss.hpp"
-#include "box_iou_loss.hpp"
+#include "box_iou_loss.hpp"   // (all three over cell_loss.hpp)
 #include "quality_loss.hpp"
 #include "rotated_box_loss.hpp"
 
@@ -186,7 +186,7 @@ int retina_loss_launch(bool backward, const void *cls, const void *box, const fl
 // The kernel arguments of odtk_box_iou_loss_levels_* (csrc/box_iou_loss.hpp; nb = 4 box parameters per anchor) and of
 // odtk_rotated_box_loss_levels_* (csrc/rotated_box_loss.hpp; nb = 6) from the ABI's level table; everything the entry points
 // promise to check is checked here, on the host.  `pointers`: false for the workspace query, which looks at no data pointer.
-int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_levels, const odtk_loss_level_t *levels,
+int box_iou_fill(odtk::CellLossArgs &ba, bool backward, bool pointers, int n_levels, const odtk_loss_level_t *levels,
                  const float *const *anchors, int batch, int A, int dtype, int kind, const float *g, unsigned *total_blocks,
                  unsigned nb = 4) {
   if (n_levels <= 0 || n_levels > ODTK_MAX_LEVELS || !levels || !anchors || batch < 1 || A < 1 || A > ODTK_MAX_ANCHORS)
@@ -202,7 +202,7 @@ int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_level
   unsigned long long total = 0;
   for (int l = 0; l < n_levels; ++l) {
     const odtk_loss_level_t &lv = levels[l];
-    odtk::BoxIouLevel &bl = ba.lv[l];
+    odtk::CellLossLevel &bl = ba.lv[l];
     if (lv.height <= 0 || lv.width <= 0 || (lv.channels_last != 0 && lv.channels_last != 1) || !anchors[l]) return ODTK_ERR_INVALID;
     const unsigned long long cells = 1ull * batch * A * lv.height * lv.width;
     if (nb * cells >= (1ull << 31)) return ODTK_ERR_INVALID;    // the kernels index the deltas with 32 bits
@@ -231,7 +231,7 @@ int box_iou_fill(odtk::BoxIouArgs &ba, bool backward, bool pointers, int n_level
     bl.by_hw = odtk::fastdiv_make(bl.hw);
     bl.by_anchors = odtk::fastdiv_make(A);
     ba.block_begin[l] = static_cast<uint32_t>(total);
-    total += (cells + odtk::kBoxIouThreads - 1) / odtk::kBoxIouThreads;
+    total += (cells + odtk::kCellLossThreads - 1) / odtk::kCellLossThreads;
   }
   for (int l = n_levels; l <= ODTK_MAX_LEVELS; ++l) ba.block_begin[l] = static_cast<uint32_t>(total);
   *total_blocks = static_cast<unsigned>(total);                   // <= 6 * 2^29 / 256
@@ -247,7 +247,7 @@ int quality_fill(odtk::QualityArgs &qa, bool backward, bool pointers, int n_leve
                  unsigned *total_blocks) {
   if (kind != ODTK_CLS_LOSS_QFL && kind != ODTK_CLS_LOSS_VFL) return ODTK_ERR_INVALID;
   if (!std::isfinite(gamma) || gamma < 1.0f || !std::isfinite(alpha) || alpha < 0.0f || C < 1) return ODTK_ERR_INVALID;
-  odtk::BoxIouArgs ba;
+  odtk::CellLossArgs ba;
   unsigned box_blocks = 0;
   const int rc = box_iou_fill(ba, false, pointers, n_levels, levels, anchors, batch, A, dtype, ODTK_BOX_LOSS_IOU, nullptr, &box_blocks);
   if (rc != ODTK_OK) return rc;
@@ -290,6 +290,53 @@ void quality_dispatch(int dtype, const odtk::QualityArgs &qa, unsigned total, hi
   if (dtype == ODTK_F32) timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::F32, kBackward, 2>, grid, block, 0, stream, qa);
   else if (dtype == ODTK_BF16) timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::BF16, kBackward, 1>, grid, block, 0, stream, qa);
   else timed_launch(ODTK_KERNEL_LOSS, odtk::quality_loss_kernel<odtk::F16, kBackward, 1>, grid, block, 0, stream, qa);
+}
+
+// The walk of a per-cell box loss (csrc/cell_loss.hpp) with the policy `Loss`: one lane per anchor cell, either direction.
+template <typename Loss, bool kBackward>
+void box_loss_dispatch(int dtype, const odtk::CellLossArgs &ba, unsigned total, hipStream_t stream) {
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if constexpr (kBackward)
+      timed_launch(ODTK_KERNEL_LOSS, odtk::cell_loss_backward_kernel<T, Loss>, dim3(total), dim3(odtk::kCellLossThreads), 0, stream, ba);
+    else
+      timed_launch(ODTK_KERNEL_LOSS, odtk::cell_loss_forward_kernel<T, Loss>, dim3(total), dim3(odtk::kCellLossThreads), 0, stream, ba);
+  });
+}
+
+// The forward of odtk_{box_iou,rotated_box,quality}_loss_levels_*: `rc` and `args` are what the family's validator (box_iou_fill /
+// quality_fill) returned and filled for a walk of `total` workgroups.  Two-phase: without a workspace, the bytes the workgroups'
+// pairs need; with one, walk(stream) and then the fixed-order sum of every level's pairs into `sums`.
+template <typename Args, typename Walk>
+int cell_loss_levels_forward(int rc, Args &args, unsigned total, int n_levels, double *sums, void *workspace, size_t workspace_size,
+                             int too_small,   // ODTK_ERR_INVALID for the box losses: their code predates the use of ODTK_ERR_WORKSPACE and is ABI
+                             hipStream_t stream, Walk walk) {
+  if (rc != ODTK_OK) return rc;
+  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
+  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
+  if (workspace_size < need) return too_small;
+  if (!sums || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u)) return ODTK_ERR_INVALID;
+  args.partial = static_cast<double *>(workspace);
+  walk(stream);
+  ODTK_HIP_TRY(hipGetLastError());
+  odtk::LevelPairReduceArgs ra;
+  std::memset(&ra, 0, sizeof ra);
+  ra.partial = args.partial;
+  ra.sums = sums;
+  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = args.block_begin[l];
+  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::level_pair_reduce_kernel, dim3(n_levels), dim3(odtk::kCellLossThreads), 0, stream, ra);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+// The backward of the same entry points: the validator's verdict, the upstream gradients' alignment, one launch.
+template <typename Walk>
+int cell_loss_levels_backward(int rc, const float *grad_sums, Walk walk) {
+  if (rc != ODTK_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
+  walk();
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
 }
 
 }  // namespace
@@ -656,46 +703,19 @@ int odtk_retina_loss_levels_backward(int n_levels, const odtk_loss_level_t *leve
 int odtk_box_iou_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                      int num_anchors, int dtype, int kind, double *sums, void *workspace, size_t workspace_size,
                                      void *stream) {
-  odtk::BoxIouArgs ba;
+  odtk::CellLossArgs ba;
   unsigned total = 0;
   const int rc = box_iou_fill(ba, false, workspace != nullptr, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, nullptr, &total);
-  if (rc != ODTK_OK) return rc;
-  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
-  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
-  if (!sums || workspace_size < need || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u))
-    return ODTK_ERR_INVALID;
-  ba.partial = static_cast<double *>(workspace);
-  dispatch_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    timed_launch(ODTK_KERNEL_LOSS, odtk::box_iou_loss_forward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
-                 static_cast<hipStream_t>(stream), ba);
-  });
-  ODTK_HIP_TRY(hipGetLastError());
-  odtk::BoxIouReduceArgs ra;
-  std::memset(&ra, 0, sizeof ra);
-  ra.partial = ba.partial;
-  ra.sums = sums;
-  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = ba.block_begin[l];
-  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::box_iou_reduce_kernel, dim3(n_levels), dim3(odtk::kBoxIouThreads), 0,
-               static_cast<hipStream_t>(stream), ra);
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_forward(rc, ba, total, n_levels, sums, workspace, workspace_size, ODTK_ERR_INVALID, static_cast<hipStream_t>(stream),
+                                  [&](hipStream_t s) { box_loss_dispatch<odtk::BoxIouLoss, false>(dtype, ba, total, s); });
 }
 
 int odtk_box_iou_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                       int num_anchors, int dtype, int kind, const float *grad_sums, void *stream) {
-  odtk::BoxIouArgs ba;
+  odtk::CellLossArgs ba;
   unsigned total = 0;
   const int rc = box_iou_fill(ba, true, true, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, grad_sums, &total);
-  if (rc != ODTK_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
-  dispatch_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    timed_launch(ODTK_KERNEL_LOSS, odtk::box_iou_loss_backward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
-                 static_cast<hipStream_t>(stream), ba);
-  });
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_backward(rc, grad_sums, [&] { box_loss_dispatch<odtk::BoxIouLoss, true>(dtype, ba, total, static_cast<hipStream_t>(stream)); });
 }
 
 int odtk_quality_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
@@ -705,23 +725,8 @@ int odtk_quality_loss_levels_forward(int n_levels, const odtk_loss_level_t *leve
   unsigned total = 0;
   const int rc = quality_fill(qa, false, workspace != nullptr, n_levels, levels, anchors, batch_size, num_anchors, num_classes, dtype,
                               kind, alpha, gamma, nullptr, &total);
-  if (rc != ODTK_OK) return rc;
-  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
-  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
-  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
-  if (!sums || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u)) return ODTK_ERR_INVALID;
-  qa.partial = static_cast<double *>(workspace);
-  quality_dispatch<false>(dtype, qa, total, static_cast<hipStream_t>(stream));
-  ODTK_HIP_TRY(hipGetLastError());
-  odtk::BoxIouReduceArgs ra;
-  std::memset(&ra, 0, sizeof ra);
-  ra.partial = qa.partial;
-  ra.sums = sums;
-  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = qa.block_begin[l];
-  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::box_iou_reduce_kernel, dim3(n_levels), dim3(odtk::kBoxIouThreads), 0,
-               static_cast<hipStream_t>(stream), ra);
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_forward(rc, qa, total, n_levels, sums, workspace, workspace_size, ODTK_ERR_WORKSPACE, static_cast<hipStream_t>(stream),
+                                  [&](hipStream_t s) { quality_dispatch<false>(dtype, qa, total, s); });
 }
 
 int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
@@ -731,57 +736,26 @@ int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *lev
   unsigned total = 0;
   const int rc = quality_fill(qa, true, true, n_levels, levels, anchors, batch_size, num_anchors, num_classes, dtype, kind, alpha, gamma,
                               grad_sums, &total);
-  if (rc != ODTK_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
-  quality_dispatch<true>(dtype, qa, total, static_cast<hipStream_t>(stream));
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_backward(rc, grad_sums, [&] { quality_dispatch<true>(dtype, qa, total, static_cast<hipStream_t>(stream)); });
 }
 
 int odtk_rotated_box_loss_levels_forward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                          int num_anchors, int dtype, int kind, double *sums, void *workspace, size_t workspace_size,
                                          void *stream) {
-  odtk::BoxIouArgs ba;
+  odtk::CellLossArgs ba;
   unsigned total = 0;
   const int rc = box_iou_fill(ba, false, workspace != nullptr, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, nullptr,
                               &total, 6);
-  if (rc != ODTK_OK) return rc;
-  const size_t need = align_up(static_cast<size_t>(total) * 2 * sizeof(double));
-  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
-  if (!sums || workspace_size < need || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums)) & 7u))
-    return ODTK_ERR_INVALID;
-  ba.partial = static_cast<double *>(workspace);
-  dispatch_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    timed_launch(ODTK_KERNEL_LOSS, odtk::rotated_box_loss_forward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
-                 static_cast<hipStream_t>(stream), ba);
-  });
-  ODTK_HIP_TRY(hipGetLastError());
-  odtk::BoxIouReduceArgs ra;
-  std::memset(&ra, 0, sizeof ra);
-  ra.partial = ba.partial;
-  ra.sums = sums;
-  for (int l = 0; l <= ODTK_MAX_LEVELS; ++l) ra.block_begin[l] = ba.block_begin[l];
-  timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::box_iou_reduce_kernel, dim3(n_levels), dim3(odtk::kBoxIouThreads), 0,
-               static_cast<hipStream_t>(stream), ra);
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_forward(rc, ba, total, n_levels, sums, workspace, workspace_size, ODTK_ERR_INVALID, static_cast<hipStream_t>(stream),
+                                  [&](hipStream_t s) { box_loss_dispatch<odtk::RotatedBoxLoss, false>(dtype, ba, total, s); });
 }
 
 int odtk_rotated_box_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                           int num_anchors, int dtype, int kind, const float *grad_sums, void *stream) {
-  odtk::BoxIouArgs ba;
+  odtk::CellLossArgs ba;
   unsigned total = 0;
   const int rc = box_iou_fill(ba, true, true, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, grad_sums, &total, 6);
-  if (rc != ODTK_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
-  dispatch_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    timed_launch(ODTK_KERNEL_LOSS, odtk::rotated_box_loss_backward_kernel<T>, dim3(total), dim3(odtk::kBoxIouThreads), 0,
-                 static_cast<hipStream_t>(stream), ba);
-  });
-  ODTK_HIP_TRY(hipGetLastError());
-  return ODTK_OK;
+  return cell_loss_levels_backward(rc, grad_sums, [&] { box_loss_dispatch<odtk::RotatedBoxLoss, true>(dtype, ba, total, static_cast<hipStream_t>(stream)); });
 }
 
 }  // extern "C"

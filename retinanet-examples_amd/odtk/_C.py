@@ -878,17 +878,10 @@ def retina_loss_levels_backward(cls_heads, box_heads, depths, box_targets, alpha
     """Gradients of sum_l (g_cls[l] * cls_sum[l] + g_box[l] * box_sum[l]) w.r.t. every head, ONE launch.
     grad_*: float32 CUDA vectors [L] (or None = zeros), read on the device."""
     dev = cls_heads[0].device
-    dcls = [torch.empty_like(t) for t in cls_heads]
-    dbox = [torch.empty_like(t) for t in box_heads]
-    for g, t in zip(dcls + dbox, list(cls_heads) + list(box_heads)):
-        if g.stride() != t.stride():
-            raise RuntimeError('retina_loss_levels_backward: could not allocate gradients in the heads\' layout')
+    dcls = _head_grads('retina_loss_levels_backward', cls_heads)
+    dbox = _head_grads('retina_loss_levels_backward', box_heads)
     arr, n, (b, a, c, nb, dtype) = _loss_levels(cls_heads, box_heads, depths, box_targets, (dcls, dbox))
-
-    def vec(g):
-        return None if g is None else g.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-
-    g_cls, g_box = vec(grad_cls_sums), vec(grad_box_sums)
+    g_cls, g_box = _grad_vector(grad_cls_sums, n, dev), _grad_vector(grad_box_sums, n, dev)
     _launch(library().odtk_retina_loss_levels_backward, 'retina_loss_levels_backward', dev, n, arr, b, a, c, nb, dtype,
             float(alpha), float(gamma), float(beta), g_cls.data_ptr() if g_cls is not None else None,
             g_box.data_ptr() if g_box is not None else None)
@@ -941,33 +934,57 @@ def _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, gr
     return arr, tables, keep, n, geo[0], geo[1], geo[2], kinds[kind]
 
 
+def _head_grads(what, heads):
+    """Uninitialised gradients of `heads` in the heads' own layout (the kernels write every element)."""
+    grads = [torch.empty_like(t) for t in heads]
+    for g, t in zip(grads, heads):
+        if g.stride() != t.stride():
+            raise RuntimeError('%s: could not allocate gradients in the heads\' layout' % what)
+    return grads
+
+
+def _grad_vector(grad, n, dev):
+    """An upstream gradient per level -> float32 vector [n] on `dev`, read on the device; None stays None (= zeros)."""
+    return None if grad is None else grad.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+
+
+def _pair_sums_forward(what, dev, n, *args):
+    """Enqueue the forward entry point odtk_<what> (two launches through the workspace) -> float64 [n, 2] = per level (sum, #foreground)."""
+    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    _enqueue(getattr(library(), 'odtk_' + what), what, dev, n, *args, sums.data_ptr())
+    return sums
+
+
+def _pair_sums_backward(what, dev, n, grad_sums, *args):
+    g = _grad_vector(grad_sums, n, dev)
+    _launch(getattr(library(), 'odtk_' + what), what, dev, n, *args, g.data_ptr() if g is not None else None)
+
+
+def _box_loss_levels_forward(what, nb, kinds, box_heads, depths, box_targets, anchors_list, kind):
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, None, nb, kinds)
+    return _pair_sums_forward(what, box_heads[0].device, n, arr, tables, b, a, dtype, code)
+
+
+def _box_loss_levels_backward(what, nb, kinds, box_heads, depths, box_targets, anchors_list, kind, grad_sums):
+    dev = box_heads[0].device
+    dbox = _head_grads(what, box_heads)
+    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels(what, box_heads, depths, box_targets, anchors_list, kind, dbox, nb, kinds)
+    _pair_sums_backward(what, dev, n, grad_sums, arr, tables, b, a, dtype, code)
+    return dbox
+
+
 def box_iou_loss_levels_forward(box_heads, depths, box_targets, anchors_list, kind):
     """IoU / GIoU / DIoU box loss ('iou' | 'giou' | 'diou') at the foreground anchors of all pyramid levels (csrc/box_iou_loss.hpp)
     -> float64 CUDA tensor [L, 2] = per level (sum of the losses, #foreground).  anchors_list: per level [A, 4].  Two launches, no
     atomics: the same bits on every run."""
-    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('box_iou_loss_levels_forward', box_heads, depths, box_targets,
-                                                              anchors_list, kind)
-    dev = box_heads[0].device
-    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
-    _enqueue(library().odtk_box_iou_loss_levels_forward, 'box_iou_loss_levels_forward', dev, n, arr, tables, b, a, dtype, code,
-             sums.data_ptr())
-    return sums
+    return _box_loss_levels_forward('box_iou_loss_levels_forward', 4, BOX_LOSS_KINDS, box_heads, depths, box_targets, anchors_list, kind)
 
 
 def box_iou_loss_levels_backward(box_heads, depths, box_targets, anchors_list, kind, grad_sums):
     """Gradients of sum_l grad_sums[l] * box_sum[l] w.r.t. every box head, in the heads' dtype and layout, ONE launch.
     grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
-    dev = box_heads[0].device
-    dbox = [torch.empty_like(t) for t in box_heads]
-    for g, t in zip(dbox, box_heads):
-        if g.stride() != t.stride():
-            raise RuntimeError('box_iou_loss_levels_backward: could not allocate gradients in the heads\' layout')
-    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('box_iou_loss_levels_backward', box_heads, depths, box_targets,
-                                                              anchors_list, kind, dbox)
-    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-    _launch(library().odtk_box_iou_loss_levels_backward, 'box_iou_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
-            g.data_ptr() if g is not None else None)
-    return dbox
+    return _box_loss_levels_backward('box_iou_loss_levels_backward', 4, BOX_LOSS_KINDS, box_heads, depths, box_targets, anchors_list, kind,
+                                     grad_sums)
 
 
 def rotated_box_loss_levels_forward(box_heads, depths, box_targets, anchors_list, kind):
@@ -975,29 +992,15 @@ def rotated_box_loss_levels_forward(box_heads, depths, box_targets, anchors_list
     levels (csrc/rotated_box_loss.hpp; the definition: odtk/loss.py:rotated_box_loss) -> float64 CUDA tensor [L, 2] = per level
     (sum of the losses, #foreground).  box_heads [B, A*6, H, W], box_targets [B, A, 6, H, W]; anchors_list: per level the AXIS
     table [A, 4] of the (axis, rotated) anchor pair.  Two launches, no atomics: the same bits on every run."""
-    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('rotated_box_loss_levels_forward', box_heads, depths, box_targets,
-                                                              anchors_list, kind, None, 6, ROTATED_BOX_LOSS_KINDS)
-    dev = box_heads[0].device
-    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
-    _enqueue(library().odtk_rotated_box_loss_levels_forward, 'rotated_box_loss_levels_forward', dev, n, arr, tables, b, a, dtype, code,
-             sums.data_ptr())
-    return sums
+    return _box_loss_levels_forward('rotated_box_loss_levels_forward', 6, ROTATED_BOX_LOSS_KINDS, box_heads, depths, box_targets,
+                                    anchors_list, kind)
 
 
 def rotated_box_loss_levels_backward(box_heads, depths, box_targets, anchors_list, kind, grad_sums):
     """Gradients of sum_l grad_sums[l] * box_sum[l] w.r.t. every box head (all six deltas), in the heads' dtype and layout, ONE
     launch.  grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
-    dev = box_heads[0].device
-    dbox = [torch.empty_like(t) for t in box_heads]
-    for g, t in zip(dbox, box_heads):
-        if g.stride() != t.stride():
-            raise RuntimeError('rotated_box_loss_levels_backward: could not allocate gradients in the heads\' layout')
-    arr, tables, keep, n, b, a, dtype, code = _box_iou_levels('rotated_box_loss_levels_backward', box_heads, depths, box_targets,
-                                                              anchors_list, kind, dbox, 6, ROTATED_BOX_LOSS_KINDS)
-    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-    _launch(library().odtk_rotated_box_loss_levels_backward, 'rotated_box_loss_levels_backward', dev, n, arr, tables, b, a, dtype, code,
-            g.data_ptr() if g is not None else None)
-    return dbox
+    return _box_loss_levels_backward('rotated_box_loss_levels_backward', 6, ROTATED_BOX_LOSS_KINDS, box_heads, depths, box_targets,
+                                     anchors_list, kind, grad_sums)
 
 
 def _quality_levels(what, cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha, gamma, grads=None):
@@ -1033,28 +1036,19 @@ def quality_loss_levels_forward(cls_heads, box_heads, depths, box_targets, ancho
     the definition: odtk/loss.py) -> float64 CUDA tensor [L, 2] = per level (sum of the losses, #foreground).  The soft target --
     the IoU of the predicted and the assigned box at every foreground anchor -- is computed in the walk from box_heads / box_targets /
     anchors_list (per level [A, 4]).  Two launches, no atomics: the same bits on every run."""
-    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels('quality_loss_levels_forward', cls_heads, box_heads, depths, box_targets,
-                                                                 anchors_list, kind, alpha, gamma)
-    dev = cls_heads[0].device
-    sums = torch.empty((n, 2), dtype=torch.float64, device=dev)
-    _enqueue(library().odtk_quality_loss_levels_forward, 'quality_loss_levels_forward', dev, n, arr, tables, b, a, c, dtype, code,
-             float(alpha), float(gamma), sums.data_ptr())
-    return sums
+    what = 'quality_loss_levels_forward'
+    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels(what, cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha, gamma)
+    return _pair_sums_forward(what, cls_heads[0].device, n, arr, tables, b, a, c, dtype, code, float(alpha), float(gamma))
 
 
 def quality_loss_levels_backward(cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha, gamma, grad_sums):
     """Gradients of sum_l grad_sums[l] * cls_sum[l] w.r.t. every class head, in the heads' dtype and layout, ONE launch (the box
     heads get none: the quality is a constant of this loss).  grad_sums: float32 CUDA vector [L] (or None = zeros), read on the device."""
-    dev = cls_heads[0].device
-    dcls = [torch.empty_like(t) for t in cls_heads]
-    for g, t in zip(dcls, cls_heads):
-        if g.stride() != t.stride():
-            raise RuntimeError('quality_loss_levels_backward: could not allocate gradients in the heads\' layout')
-    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels('quality_loss_levels_backward', cls_heads, box_heads, depths, box_targets,
-                                                                 anchors_list, kind, alpha, gamma, dcls)
-    g = None if grad_sums is None else grad_sums.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-    _launch(library().odtk_quality_loss_levels_backward, 'quality_loss_levels_backward', dev, n, arr, tables, b, a, c, dtype, code,
-            float(alpha), float(gamma), g.data_ptr() if g is not None else None)
+    what, dev = 'quality_loss_levels_backward', cls_heads[0].device
+    dcls = _head_grads(what, cls_heads)
+    arr, tables, keep, n, b, a, c, dtype, code = _quality_levels(what, cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha,
+                                                                 gamma, dcls)
+    _pair_sums_backward(what, dev, n, grad_sums, arr, tables, b, a, c, dtype, code, float(alpha), float(gamma))
     return dcls
 
 

@@ -237,17 +237,37 @@ class _FusedLevelLoss(torch.autograd.Function):
         return dcls, dbox, None, None, None, None, None
 
 
+def _as_written(t):
+    return t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) else t.contiguous()
+
+
 def _as_written_pair(cls_head, box_head):
     """Head tensors go to the kernels as the convolutions wrote them; anything exotic is normalised once."""
-    pair = [cls_head, box_head]
-    for i, t in enumerate(pair):
-        if not (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)):
-            pair[i] = t.contiguous()
+    pair = [_as_written(cls_head), _as_written(box_head)]
     if pair[0].is_contiguous() != pair[1].is_contiguous() and pair[0].shape[2] * pair[0].shape[3] > 1:
         pair[1] = pair[1].contiguous() if pair[0].is_contiguous() else pair[1].contiguous(memory_format=torch.channels_last)
     if pair[1].dtype != pair[0].dtype:
         pair[1] = pair[1].to(pair[0].dtype)
     return pair
+
+
+def _in_level_groups(fn, lists, *rest):
+    """One launch covers _C.MAX_LEVELS levels (several backbones: 5 levels each) and no loss has state across levels: for more,
+    `fn(*lists, *rest)` on slices of the per-level lists, the per-level results concatenated.  None where one call covers them."""
+    from . import _C
+    m = _C.MAX_LEVELS
+    if len(lists[0]) <= m:
+        return None
+    groups = [fn(*[per_level[i:i + m] for per_level in lists], *rest) for i in range(0, len(lists[0]), m)]
+    return tuple(torch.cat(parts) for parts in zip(*groups))
+
+
+def _anchor_tables(anchors_list, pairs=False):
+    """Per level the [A, 4] anchor table as a tuple of floats: what an autograd node keeps instead of tensors.  pairs: a level may
+    be the (axis, rotated) pair of generate_anchors_rotated, of which the axis table counts."""
+    if pairs:
+        anchors_list = [a[0] if isinstance(a, (tuple, list)) and len(a) == 2 and isinstance(a[0], torch.Tensor) else a for a in anchors_list]
+    return tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
 
 
 class _FusedPyramidLoss(torch.autograd.Function):
@@ -283,12 +303,9 @@ class _FusedPyramidLoss(torch.autograd.Function):
 def fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, alpha=0.25, gamma=2.0, beta=0.11):
     """`fused_level_loss` for every pyramid level at once: per-level (cls_sums [L], box_sums [L], foreground [L]) from ONE
     HIP launch forward and ONE backward (a training step: two launches where the per-level form needs ten)."""
-    from . import _C
-    if len(cls_heads) > _C.MAX_LEVELS:              # several backbones: 5 levels each; one launch covers MAX_LEVELS
-        groups = [fused_pyramid_loss(cls_heads[i:i + _C.MAX_LEVELS], box_heads[i:i + _C.MAX_LEVELS], depths[i:i + _C.MAX_LEVELS],
-                                     box_targets[i:i + _C.MAX_LEVELS], alpha, gamma, beta)
-                  for i in range(0, len(cls_heads), _C.MAX_LEVELS)]
-        return tuple(torch.cat(parts) for parts in zip(*groups))
+    split = _in_level_groups(fused_pyramid_loss, (cls_heads, box_heads, depths, box_targets), alpha, gamma, beta)
+    if split is not None:
+        return split
     pairs = [_as_written_pair(c, b) for c, b in zip(cls_heads, box_heads)]
     n = len(pairs)
     return _FusedPyramidLoss.apply(n, alpha, gamma, beta, *[p[0] for p in pairs], *[p[1] for p in pairs],
@@ -309,26 +326,29 @@ def fused_level_loss(cls_head, box_head, depth, box_target, alpha=0.25, gamma=2.
     return _FusedLevelLoss.apply(pair[0], pair[1], depth.contiguous(), box_target.contiguous(), alpha, gamma, beta)
 
 
-class _FusedPyramidBoxIouLoss(torch.autograd.Function):
-    """(box_heads...) of ALL levels -> (box_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward."""
+class _FusedPyramidPairLoss(torch.autograd.Function):
+    """The per-cell losses of csrc/cell_loss.hpp: (heads..., depths..., box_targets...) of ALL levels -> (sums [L], foreground [L]);
+    two launches forward (walk + fixed-order sum), one backward.  `forward_fn` / `backward_fn`: the pair of odtk._C functions;
+    `tensors`: `groups` per-level lists of n tensors each, in the order the functions take them, followed there by `anchors_list`
+    and `hyper`; list `grad_group` (the heads the loss is a function of) receives the gradient."""
 
     @staticmethod
-    def forward(ctx, n, kind, anchors_list, *tensors):
-        from . import _C
-        sums = _C.box_iou_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], anchors_list, kind).float()
+    def forward(ctx, forward_fn, backward_fn, groups, grad_group, hyper, anchors_list, *tensors):
+        n = len(tensors) // groups
+        sums = forward_fn(*[tensors[k * n:(k + 1) * n] for k in range(groups)], anchors_list, *hyper).float()
         ctx.save_for_backward(*tensors)
-        ctx.meta = (n, kind, anchors_list)
-        box_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.meta = (backward_fn, groups, grad_group, hyper, anchors_list)
+        loss_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
         ctx.mark_non_differentiable(foreground)
-        return box_sums, foreground
+        return loss_sums, foreground
 
     @staticmethod
-    def backward(ctx, grad_box_sums, _grad_foreground):
-        from . import _C
-        n, kind, anchors_list = ctx.meta
+    def backward(ctx, grad_sums, _grad_foreground):
+        backward_fn, groups, grad_group, hyper, anchors_list = ctx.meta
         t = ctx.saved_tensors
-        dbox = _C.box_iou_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], anchors_list, kind, grad_box_sums)
-        return (None, None, None) + tuple(dbox) + (None,) * (2 * n)
+        n = len(t) // groups
+        grads = backward_fn(*[t[k * n:(k + 1) * n] for k in range(groups)], anchors_list, *hyper, grad_sums)
+        return (None,) * (6 + grad_group * n) + tuple(grads) + (None,) * ((groups - 1 - grad_group) * n)
 
 
 def fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, kind):
@@ -341,38 +361,12 @@ def fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, kin
     from . import _C
     if kind not in BOX_LOSS_KINDS:
         raise ValueError("fused_pyramid_box_iou_loss: kind must be 'iou', 'giou' or 'diou', not {!r}".format(kind))
-    if len(box_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
-        groups = [fused_pyramid_box_iou_loss(box_heads[i:i + _C.MAX_LEVELS], depths[i:i + _C.MAX_LEVELS], box_targets[i:i + _C.MAX_LEVELS],
-                                             anchors_list[i:i + _C.MAX_LEVELS], kind)
-                  for i in range(0, len(box_heads), _C.MAX_LEVELS)]
-        return tuple(torch.cat(parts) for parts in zip(*groups))
-    heads = [t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) else t.contiguous() for t in box_heads]
-    n = len(heads)
-    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
-    return _FusedPyramidBoxIouLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
-                                         *[t.contiguous() for t in box_targets])
-
-
-class _FusedPyramidRotatedBoxLoss(torch.autograd.Function):
-    """(box_heads...) of ALL levels -> (box_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward."""
-
-    @staticmethod
-    def forward(ctx, n, kind, anchors_list, *tensors):
-        from . import _C
-        sums = _C.rotated_box_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], anchors_list, kind).float()
-        ctx.save_for_backward(*tensors)
-        ctx.meta = (n, kind, anchors_list)
-        box_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
-        ctx.mark_non_differentiable(foreground)
-        return box_sums, foreground
-
-    @staticmethod
-    def backward(ctx, grad_box_sums, _grad_foreground):
-        from . import _C
-        n, kind, anchors_list = ctx.meta
-        t = ctx.saved_tensors
-        dbox = _C.rotated_box_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], anchors_list, kind, grad_box_sums)
-        return (None, None, None) + tuple(dbox) + (None,) * (2 * n)
+    split = _in_level_groups(fused_pyramid_box_iou_loss, (box_heads, depths, box_targets, anchors_list), kind)
+    if split is not None:
+        return split
+    return _FusedPyramidPairLoss.apply(_C.box_iou_loss_levels_forward, _C.box_iou_loss_levels_backward, 3, 0, (kind,),
+                                       _anchor_tables(anchors_list), *[_as_written(t) for t in box_heads],
+                                       *[d.contiguous() for d in depths], *[t.contiguous() for t in box_targets])
 
 
 def fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, anchors_list, kind):
@@ -388,42 +382,12 @@ def fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, anchors_list,
     from . import _C
     if kind not in ROTATED_BOX_LOSS_KINDS:
         raise ValueError("fused_pyramid_rotated_box_loss: kind must be 'probiou' or 'kld', not {!r}".format(kind))
-    if len(box_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
-        groups = [fused_pyramid_rotated_box_loss(box_heads[i:i + _C.MAX_LEVELS], depths[i:i + _C.MAX_LEVELS],
-                                                 box_targets[i:i + _C.MAX_LEVELS], anchors_list[i:i + _C.MAX_LEVELS], kind)
-                  for i in range(0, len(box_heads), _C.MAX_LEVELS)]
-        return tuple(torch.cat(parts) for parts in zip(*groups))
-    heads = [t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) else t.contiguous() for t in box_heads]
-    n = len(heads)
-    axis = [a[0] if isinstance(a, (tuple, list)) and len(a) == 2 and isinstance(a[0], torch.Tensor) else a for a in anchors_list]
-    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in axis)
-    return _FusedPyramidRotatedBoxLoss.apply(n, kind, tables, *heads, *[d.contiguous() for d in depths],
-                                             *[t.contiguous() for t in box_targets])
-
-
-class _FusedPyramidQualityLoss(torch.autograd.Function):
-    """(cls_heads...) of ALL levels -> (cls_sums [L], foreground [L]); two launches forward (walk + fixed-order sum), one backward.
-    The box heads are inputs without a gradient: the quality is a constant of this loss."""
-
-    @staticmethod
-    def forward(ctx, n, kind, alpha, gamma, anchors_list, *tensors):
-        from . import _C
-        sums = _C.quality_loss_levels_forward(tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n], tensors[3 * n:4 * n], anchors_list,
-                                              kind, alpha, gamma).float()
-        ctx.save_for_backward(*tensors)
-        ctx.meta = (n, kind, alpha, gamma, anchors_list)
-        cls_sums, foreground = sums[:, 0].contiguous(), sums[:, 1].contiguous()
-        ctx.mark_non_differentiable(foreground)
-        return cls_sums, foreground
-
-    @staticmethod
-    def backward(ctx, grad_cls_sums, _grad_foreground):
-        from . import _C
-        n, kind, alpha, gamma, anchors_list = ctx.meta
-        t = ctx.saved_tensors
-        dcls = _C.quality_loss_levels_backward(t[:n], t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n], anchors_list, kind, alpha, gamma,
-                                               grad_cls_sums)
-        return (None, None, None, None, None) + tuple(dcls) + (None,) * (3 * n)
+    split = _in_level_groups(fused_pyramid_rotated_box_loss, (box_heads, depths, box_targets, anchors_list), kind)
+    if split is not None:
+        return split
+    return _FusedPyramidPairLoss.apply(_C.rotated_box_loss_levels_forward, _C.rotated_box_loss_levels_backward, 3, 0, (kind,),
+                                       _anchor_tables(anchors_list, pairs=True), *[_as_written(t) for t in box_heads],
+                                       *[d.contiguous() for d in depths], *[t.contiguous() for t in box_targets])
 
 
 def fused_pyramid_quality_loss(cls_heads, box_heads, depths, box_targets, anchors_list, kind, alpha=0.75, gamma=2.0):
@@ -440,14 +404,10 @@ def fused_pyramid_quality_loss(cls_heads, box_heads, depths, box_targets, anchor
     from . import _C
     if kind not in CLS_LOSS_KINDS:
         raise ValueError("fused_pyramid_quality_loss: kind must be 'qfl' or 'vfl', not {!r}".format(kind))
-    if len(cls_heads) > _C.MAX_LEVELS:              # the loss has no state across levels: one launch covers MAX_LEVELS
-        m = _C.MAX_LEVELS
-        groups = [fused_pyramid_quality_loss(cls_heads[i:i + m], box_heads[i:i + m], depths[i:i + m], box_targets[i:i + m],
-                                             anchors_list[i:i + m], kind, alpha, gamma)
-                  for i in range(0, len(cls_heads), m)]
-        return tuple(torch.cat(parts) for parts in zip(*groups))
+    split = _in_level_groups(fused_pyramid_quality_loss, (cls_heads, box_heads, depths, box_targets, anchors_list), kind, alpha, gamma)
+    if split is not None:
+        return split
     pairs = [_as_written_pair(c, b.detach()) for c, b in zip(cls_heads, box_heads)]
-    n = len(pairs)
-    tables = tuple(tuple(float(v) for v in torch.as_tensor(a).reshape(-1).tolist()) for a in anchors_list)
-    return _FusedPyramidQualityLoss.apply(n, kind, float(alpha), float(gamma), tables, *[p[0] for p in pairs], *[p[1] for p in pairs],
-                                          *[d.contiguous() for d in depths], *[t.contiguous() for t in box_targets])
+    return _FusedPyramidPairLoss.apply(_C.quality_loss_levels_forward, _C.quality_loss_levels_backward, 4, 0,
+                                       (kind, float(alpha), float(gamma)), _anchor_tables(anchors_list), *[p[0] for p in pairs],
+                                       *[p[1] for p in pairs], *[d.contiguous() for d in depths], *[t.contiguous() for t in box_targets])

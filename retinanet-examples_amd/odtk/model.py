@@ -428,7 +428,7 @@ class Model(nn.Module):
         cls_total, box_total, foreground = 0.0, 0.0, 0.0
         if self.assigner not in ('iou', 'atss', 'tal'):
             raise ValueError("Model.assigner must be 'iou', 'atss' or 'tal', not {!r}".format(self.assigner))
-        iou_kind, gauss_kind = None, None
+        iou_kind, gauss_kind, weight = None, None, None     # weight: of every box loss except smooth-L1
         if self.box_loss != 'smooth_l1':
             if self.box_loss not in BOX_LOSS_KINDS + ROTATED_BOX_LOSS_KINDS:
                 raise ValueError("Model.box_loss must be 'smooth_l1', 'iou', 'giou' or 'diou' (axis-aligned boxes), 'probiou' or 'kld' "
@@ -451,90 +451,68 @@ class Model(nn.Module):
             if self.rotated_bbox:
                 raise ValueError('Model.cls_loss = {!r} is not available for rotated boxes'.format(self.cls_loss))
             quality_kind = self.cls_loss
+        if self.assigner != 'iou':
+            if self.rotated_bbox:
+                raise ValueError('Model.assigner = {!r} is not available for rotated boxes'.format(self.assigner))
+            if len(cls_heads) > box_ops.MAX_LEVELS_PER_CALL:
+                why = 'its threshold spans all of them' if self.assigner == 'atss' else 'a box ranks its candidates over all of them'
+                raise ValueError('Model.assigner = {!r} takes at most {} pyramid levels ({}, so the call cannot be split), not {}'.format(
+                    self.assigner, box_ops.MAX_LEVELS_PER_CALL, why, len(cls_heads)))
+        strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
+        sizes = [tuple(c.shape[-2:]) for c in cls_heads]
+        anchors_list = [self.level_anchors(s) for s in strides]          # rotated models: (axis, rotated) pairs
+        fused = self.fused_loss and cls_heads[0].is_cuda
         atss = None
         if self.assigner == 'atss':
-            if self.rotated_bbox:
-                raise ValueError("Model.assigner = 'atss' is not available for rotated boxes")
-            if len(cls_heads) > box_ops.MAX_LEVELS_PER_CALL:
-                raise ValueError("Model.assigner = 'atss' takes at most {} pyramid levels (its threshold spans all of them, so "
-                                 'the call cannot be split), not {}'.format(box_ops.MAX_LEVELS_PER_CALL, len(cls_heads)))
-            strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
-            fused = self.fused_loss and cls_heads[0].is_cuda
-            atss = box_ops.atss_assign_levels(targets, [tuple(c.shape[-2:]) for c in cls_heads], strides,
-                                              [self.level_anchors(s) for s in strides], self.classes, self.atss_topk,
-                                              want_cls_target=not fused)
+            atss = box_ops.atss_assign_levels(targets, sizes, strides, anchors_list, self.classes, self.atss_topk, want_cls_target=not fused)
         elif self.assigner == 'tal':
-            if self.rotated_bbox:
-                raise ValueError("Model.assigner = 'tal' is not available for rotated boxes")
-            if len(cls_heads) > box_ops.MAX_LEVELS_PER_CALL:
-                raise ValueError("Model.assigner = 'tal' takes at most {} pyramid levels (a box ranks its candidates over all of "
-                                 'them, so the call cannot be split), not {}'.format(box_ops.MAX_LEVELS_PER_CALL, len(cls_heads)))
-            strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
-            fused = self.fused_loss and cls_heads[0].is_cuda
             # the assignment reads the heads as constants (detached); from here on both paths consume it exactly as ATSS's
             atss = box_ops.tal_assign_levels(targets, [c.detach() for c in cls_heads], [b.detach() for b in box_heads], strides,
-                                             [self.level_anchors(s) for s in strides], self.classes, self.tal_topk, self.tal_alpha,
-                                             self.tal_beta, want_cls_target=not fused)
-        if self.fused_loss and cls_heads[0].is_cuda:
+                                             anchors_list, self.classes, self.tal_topk, self.tal_alpha, self.tal_beta,
+                                             want_cls_target=not fused)
+        if fused:
             # targets of every level (ONE HIP launch for all of them; the class map is implied by depth and not even built), then focal
             # + smooth-L1 + masks + sums of ALL levels in one HIP pass -- and one more in backward (csrc/loss.hpp)
             if atss is not None:
                 _, box_targets, depths = atss
             elif len(cls_heads) <= box_ops.MAX_LEVELS_PER_CALL:
-                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
                 assign = box_ops.snap_to_anchors_rotated_levels if self.rotated_bbox else box_ops.snap_to_anchors_levels
-                _, box_targets, depths = assign(
-                    targets, [tuple(c.shape[-2:]) for c in cls_heads], strides, [self.level_anchors(s) for s in strides],
-                    self.classes, self.anchor_ious, want_cls_target=False)
+                _, box_targets, depths = assign(targets, sizes, strides, anchors_list, self.classes, self.anchor_ious, want_cls_target=False)
             else:
                 depths, box_targets = [], []
-                for cls_head in cls_heads:
-                    stride = x.shape[-1] / cls_head.shape[-1]
-                    _, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:], False)
+                for stride, size in zip(strides, sizes):
+                    _, box_target, depth = self._extract_targets(targets, stride, size, False)
                     depths.append(depth)
                     box_targets.append(box_target)
+            # -> (cls_sums, box_sums, fg), each from the pass that owns it.  The quality pass (csrc/quality_loss.hpp) supplies the
+            # classification sums and the foreground count; the focal + smooth-L1 pass then runs only for its box sum (its
+            # classification half goes unused: autograd hands it a zero gradient) and, with an IoU-family box loss, not at all:
+            # nothing streams the logits twice.  The IoU-family and the Gaussian losses (csrc/box_iou_loss.hpp, csrc/
+            # rotated_box_loss.hpp: rotated boxes, on the axis tables) are passes of their own over the foreground anchors; the
+            # smooth-L1 sum of the focal pass then goes unused in the same way
             if quality_kind is not None:
-                # the quality pass (csrc/quality_loss.hpp) supplies the classification sums and the foreground count.  With an
-                # IoU-family box loss the focal + smooth-L1 pass is not called at all: nothing streams the logits twice.  With
-                # smooth-L1 it still runs for its box sum; its classification half goes unused (autograd hands it a zero
-                # gradient), as its box half does under `box_loss`
-                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
-                anchors_list = [self.level_anchors(s) for s in strides]
                 cls_sums, fg = fused_pyramid_quality_loss(cls_heads, box_heads, depths, box_targets, anchors_list, quality_kind)
-                foreground = fg.clamp(min=1).sum()
-                if iou_kind is not None:
-                    box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, iou_kind)
-                    return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
-                _, box_sums, _ = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
-                                                    self.cls_criterion.gamma, self.box_criterion.beta)
-                return cls_sums.sum() / foreground, box_sums.sum() / foreground
-            cls_sums, box_sums, fg = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
-                                                        self.cls_criterion.gamma, self.box_criterion.beta)
-            foreground = fg.clamp(min=1).sum()              # per level, as the reference clamps (model.py:196)
+            if quality_kind is None or iou_kind is None:
+                focal_sums, box_sums, focal_fg = fused_pyramid_loss(cls_heads, box_heads, depths, box_targets, self.cls_criterion.alpha,
+                                                                    self.cls_criterion.gamma, self.box_criterion.beta)
+                if quality_kind is None:
+                    cls_sums, fg = focal_sums, focal_fg
             if iou_kind is not None:
-                # the smooth-L1 sum of the pass above is not used (autograd hands it a zero gradient); the IoU-family loss is a
-                # pass of its own over the foreground anchors (csrc/box_iou_loss.hpp)
-                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
-                box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, [self.level_anchors(s) for s in strides],
-                                                         iou_kind)
-                return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
-            if gauss_kind is not None:
-                # rotated boxes: the same arrangement with the Gaussian losses (csrc/rotated_box_loss.hpp), on the axis tables
-                strides = [x.shape[-1] / c.shape[-1] for c in cls_heads]
-                box_sums, _ = fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, [self.level_anchors(s)[0] for s in strides],
-                                                             gauss_kind)
-                return cls_sums.sum() / foreground, self.box_loss_weight * box_sums.sum() / foreground
-            return cls_sums.sum() / foreground, box_sums.sum() / foreground
+                box_sums, _ = fused_pyramid_box_iou_loss(box_heads, depths, box_targets, anchors_list, iou_kind)
+            elif gauss_kind is not None:
+                box_sums, _ = fused_pyramid_rotated_box_loss(box_heads, depths, box_targets, [a[0] for a in anchors_list], gauss_kind)
+            foreground = fg.clamp(min=1).sum()              # per level, as the reference clamps (model.py:196)
+            box_total = box_sums.sum() if weight is None else weight * box_sums.sum()
+            return cls_sums.sum() / foreground, box_total / foreground
         for level, (cls_head, box_head) in enumerate(zip(cls_heads, box_heads)):
-            stride = x.shape[-1] / cls_head.shape[-1]
             if atss is not None:
                 cls_target, box_target, depth = (per_level[level] for per_level in atss)
             else:
-                cls_target, box_target, depth = self._extract_targets(targets, stride, cls_head.shape[-2:])
+                cls_target, box_target, depth = self._extract_targets(targets, strides[level], cls_head.shape[-2:])
             foreground = foreground + (depth > 0).sum().float().clamp(min=1)
             if quality_kind is not None:
                 # the soft target: the IoU of the predicted and the assigned box at the anchor's class, a constant of this loss
-                quality = box_quality(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride))).detach()
+                quality = box_quality(box_head.view_as(box_target).float(), box_target, anchor_wh(anchors_list[level])).detach()
                 soft = quality_target(depth, quality, cls_target.shape[2])
                 criterion = quality_focal_loss if quality_kind == 'qfl' else varifocal_loss
                 cls_loss = criterion(cls_head.view_as(cls_target).float(), soft)
@@ -542,16 +520,15 @@ class Model(nn.Module):
                 cls_loss = self.cls_criterion(cls_head.view_as(cls_target).float(), cls_target)
             cls_total = cls_total + (cls_loss * (depth >= 0).expand_as(cls_target).float()).sum()
             if iou_kind is not None:
-                box_loss = box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)), iou_kind)
-                box_total = box_total + (box_loss * (depth[:, :, 0] > 0).float()).sum()
-                continue
-            if gauss_kind is not None:
-                box_loss = rotated_box_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(self.level_anchors(stride)[0]),
-                                            gauss_kind)
-                box_total = box_total + (box_loss * (depth[:, :, 0] > 0).float()).sum()
-                continue
-            box_loss = self.box_criterion(box_head.view_as(box_target).float(), box_target)
-            box_total = box_total + (box_loss * (depth > 0).expand_as(box_target).float()).sum()
-        if iou_kind is not None or gauss_kind is not None:
-            return cls_total / foreground, self.box_loss_weight * box_total / foreground
+                box_loss = box_iou_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(anchors_list[level]), iou_kind)
+                mask = (depth[:, :, 0] > 0).float()
+            elif gauss_kind is not None:
+                box_loss = rotated_box_loss(box_head.view_as(box_target).float(), box_target, anchor_wh(anchors_list[level][0]), gauss_kind)
+                mask = (depth[:, :, 0] > 0).float()
+            else:
+                box_loss = self.box_criterion(box_head.view_as(box_target).float(), box_target)
+                mask = (depth > 0).expand_as(box_target).float()
+            box_total = box_total + (box_loss * mask).sum()
+        if weight is not None:
+            box_total = weight * box_total
         return cls_total / foreground, box_total / foreground
