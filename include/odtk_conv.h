@@ -66,6 +66,9 @@ int odtk_conv_plan_import(const char *text);
  * MIOpen + odtk_bias_act and the reference's PyTorch graph hand the NaN on.  A diverged checkpoint therefore shows up as
  * "no detections", not as NaN scores, on library-routed layers; `ODTK_CHECK_FINITE=1` makes the engine assert that its head
  * tensors are finite (odtk/fused.py).
+ * The library's own kernel for the head towers' 3x3 256 -> 256 layers (include/odtk_hip.h: odtk_tower_conv3x3, the engine's first
+ * choice where it applies) has the same two roundings but NOT this clamp: its epilogue is odtk_bias_act's, a NaN accumulator
+ * comes out as NaN with and without ReLU.  On finite inputs the two agree up to the order of the fp32 sums.
  */
 
 /* Instances linked for `dtype` (237 bf16, 228 fp16 with ROCm 7.2's archive); 0 for any other dtype. */

@@ -568,6 +568,31 @@ int odtk_bottleneck_seam(void *out, void *z, const void *y2, const void *skip, c
                          const float *b1, size_t m, int c_in, int c_mid, int c_next, int dtype, void *stream);
 
 /*
+ * odtk_tower_conv3x3 -- the 3x3 convolutions of the head towers as an own implicit-GEMM MFMA kernel (csrc/tower_conv.hpp):
+ *     y[b][i][j][n] = rne(act( rne( sum_{kh, kw, c} x[b][i + kh - 1][j + kw - 1][c] * w[n][kh][kw][c] ) + bias[n] ))
+ * stride 1, padding 1 (positions outside the image read as zero), fp32 sums in a fixed order (the same input gives the same bits
+ * on every launch; the order of the library's 256 x 256 x 32 instance, whose finite results it reproduces bit for bit), rne =
+ * round-to-nearest-even to `dtype`, act = ReLU if relu != 0: the two roundings of the convolution library's entry point (include/odtk_conv.h), whose
+ * drop-in this is -- except that a NaN sum comes out as NaN, as odtk_bias_act hands it on.
+ *   x [batch, height, width, c_in] and y [batch, height, width, c_out]: channels_last activations of `dtype` (ODTK_BF16 / ODTK_F16);
+ *   w [c_out, 3, 3, c_in] (a torch weight in channels_last memory format) and bias [c_out]: of `dtype` too.  All device, 16-byte
+ *   aligned; y must not be x.
+ * ODTK_ERR_INVALID: a null or misaligned pointer, y == x, an extent or channel count < 1.  ODTK_ERR_UNSUPPORTED: another dtype,
+ * c_in != 256 or c_out != 256, or batch * height * width >= 2^22 pixels (32-bit byte offsets).  No workspace, nothing allocated
+ * or uploaded: one launch, capturable in a hipGraph, timed under ODTK_KERNEL_TOWER_CONV.
+ * No reference equivalent as a kernel (the reference's heads are nn.Conv2d + ReLU: odtk/model.py:57-62).
+ */
+int odtk_tower_conv3x3(void *y, const void *x, const void *w, const void *bias, int batch_size, int height, int width, int c_in,
+                       int c_out, int dtype, int relu, void *stream);
+/* Debug / A-B: launch variant of odtk_tower_conv3x3, two bits.  Bit 0 (set by default): tile ids permuted so that the workgroups
+ * sharing an L2 (ids equal mod 8) own consecutive tiles, whose halo rows overlap; clear: workgroup k owns tile k (0 .. 2 % slower).
+ * Bit 1 (clear by default): the MFMA form.  Clear: v_mfma_f32_32x32x16 with the k grouping of the convolution library's
+ * 256 x 256 x 32 instance -- the result equals that instance's bit for bit; set: v_mfma_f32_16x16x32 over 32 consecutive k, 8 %
+ * faster, one output in 50 000 a bf16 step away (profiles/tower_conv_probe.txt).  Default 1.  -1 reads the current value; returns the
+ * previous one, ODTK_ERR_INVALID for any other argument.  Process-wide; never touches HIP. */
+int odtk_debug_tower_conv_variant(int variant);
+
+/*
  * odtk_snap_to_anchors -- fused training-target assignment for ONE pyramid level of the whole batch.
  * Replaces the reference's pure-torch snap_to_anchors (odtk/box.py:134-189, called per image and
  * level from odtk/model.py:167-184): IoU of every anchor against every ground-truth box (+1 pixel
@@ -867,7 +892,8 @@ int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *lev
 #define ODTK_KERNEL_LOSS_REDUCE 15 /* loss_reduce_kernel (second launch of the forward through a workspace)   */
 #define ODTK_KERNEL_ATSS_STATS 16 /* atss_stats_kernel (ATSS: candidates + threshold; its dense launch counts as ODTK_KERNEL_TARGETS) */
 #define ODTK_KERNEL_SEAM      17  /* bottleneck_seam_kernel (conv3 + skip + ReLU and the next conv1 in one pass)      */
-#define ODTK_KERNEL_COUNT     18
+#define ODTK_KERNEL_TOWER_CONV 18 /* tower_conv3x3_kernel (the head towers' 3x3 256 -> 256 convolution, implicit GEMM)        */
+#define ODTK_KERNEL_COUNT     19
 /* on: 0 = off, otherwise a bit mask of kernel ids (1 << ODTK_KERNEL_*), -1 = all.  An event pair
  * is a queue marker before and after the kernel: cheap for the 3 post-processing launches of a step,
  * measurably NOT free for the ~110 epilogue launches (about 10 % of an 8.7 ms step), so time those

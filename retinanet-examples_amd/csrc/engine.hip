@@ -1,12 +1,13 @@
 // engine.hip -- what the inference engine runs between convolutions: bias + activation epilogues, the max-pool, nearest
-// 2x upsampling, the pyramid canvas, the stem pack, the hipBLASLt GEMM (gemm_lt.hpp is included here only) and the bottleneck seam
-// (seam.hpp: two 1x1 convolutions of layer1 in one MFMA pass).
+// 2x upsampling, the pyramid canvas, the stem pack, the hipBLASLt GEMM (gemm_lt.hpp is included here only), the bottleneck seam
+// (seam.hpp: two 1x1 convolutions of layer1 in one MFMA pass) and the head towers' 3x3 convolution (tower_conv.hpp).
 #include <cstring>
 
 #include "runtime.hpp"
 #include "epilogue.hpp"
 #include "gemm_lt.hpp"
 #include "seam.hpp"
+#include "tower_conv.hpp"
 
 namespace {
 
@@ -87,9 +88,61 @@ int seam_launch(const void *y2, const void *skip, const void *w3, const float *b
   return ODTK_OK;
 }
 
+// odtk_debug_tower_conv_variant: bit 0 = tile ids permuted by L2, bit 1 = the 16x16x32 form (otherwise the 32x32x16 form, whose sums
+// follow the convolution library's instance)
+std::atomic<int> g_tower_variant{1};
+
+template <typename T, bool kRelu, int kForm>
+int tower_conv_launch(void *y, const void *x, const void *w, const void *bias, uint32_t m, uint32_t height, uint32_t width, bool remap,
+                      hipStream_t stream) {
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void *>(&odtk::tower_conv3x3_kernel<T, kRelu, kForm>), odtk::tower::kLdsBytes,
+                                   "tower_conv3x3_kernel LDS");
+  if (rc != ODTK_OK) return rc;
+  const uint32_t tiles = (m + odtk::tower::kTilePixels - 1) / odtk::tower::kTilePixels;
+  timed_launch(ODTK_KERNEL_TOWER_CONV, odtk::tower_conv3x3_kernel<T, kRelu, kForm>, dim3(tiles), dim3(odtk::tower::kThreads),
+               odtk::tower::kLdsBytes, stream, static_cast<const unsigned char *>(x), static_cast<const unsigned char *>(w),
+               static_cast<const uint16_t *>(bias), static_cast<unsigned char *>(y), m, height, width, odtk::fastdiv_make(width),
+               odtk::fastdiv_make(height * width), remap ? 1u : 0u);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+template <typename T>
+int tower_conv_typed(void *y, const void *x, const void *w, const void *bias, uint32_t m, uint32_t h, uint32_t wd, bool relu, int variant,
+                     hipStream_t s) {
+  const bool remap = variant & 1;
+  if (variant & 2) return relu ? tower_conv_launch<T, true, 0>(y, x, w, bias, m, h, wd, remap, s) : tower_conv_launch<T, false, 0>(y, x, w, bias, m, h, wd, remap, s);
+  return relu ? tower_conv_launch<T, true, 1>(y, x, w, bias, m, h, wd, remap, s) : tower_conv_launch<T, false, 1>(y, x, w, bias, m, h, wd, remap, s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int odtk_debug_tower_conv_variant(int variant) {
+  if (variant < -1 || variant > 3) return ODTK_ERR_INVALID;
+  return variant < 0 ? g_tower_variant.load() : g_tower_variant.exchange(variant);
+}
+
+int odtk_tower_conv3x3(void *y, const void *x, const void *w, const void *bias, int batch_size, int height, int width, int c_in, int c_out,
+                       int dtype, int relu, void *stream) {
+  if (!y || !x || !w || !bias || batch_size <= 0 || height <= 0 || width <= 0 || c_in <= 0 || c_out <= 0) return ODTK_ERR_INVALID;
+  if (y == x) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (c_in != static_cast<int>(odtk::tower::kChannels) || c_out != static_cast<int>(odtk::tower::kChannels)) return ODTK_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(bias)) & 15u)
+    return ODTK_ERR_INVALID;
+  // 32-bit byte offsets into x and y: a pixel is 512 bytes
+  const uint64_t m = static_cast<uint64_t>(batch_size) * static_cast<uint64_t>(height) * static_cast<uint64_t>(width);
+  if (m * odtk::tower::kPixelBytes >= (1ull << 31)) return ODTK_ERR_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int variant = g_tower_variant.load(std::memory_order_relaxed);
+  if (dtype == ODTK_BF16)
+    return tower_conv_typed<odtk::BF16>(y, x, w, bias, static_cast<uint32_t>(m), static_cast<uint32_t>(height), static_cast<uint32_t>(width),
+                                        relu != 0, variant, s);
+  return tower_conv_typed<odtk::F16>(y, x, w, bias, static_cast<uint32_t>(m), static_cast<uint32_t>(height), static_cast<uint32_t>(width),
+                                      relu != 0, variant, s);
+}
 
 int odtk_bottleneck_seam(void *out, void *z, const void *y2, const void *skip, const void *w3, const float *b3, const void *w1,
                          const float *b1, size_t m, int c_in, int c_mid, int c_next, int dtype, void *stream) {

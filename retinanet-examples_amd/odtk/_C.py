@@ -203,13 +203,15 @@ _SIGNATURES = {
                                           ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'odtk_bottleneck_seam': (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_size_t] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    'odtk_tower_conv3x3': (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7 + [ctypes.c_void_p]),
+    'odtk_debug_tower_conv_variant': (ctypes.c_int, [ctypes.c_int]),
     'odtk_profile_collect': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
 }
 
 KERNEL_NAMES = ('prefilter_scan_kernel', 'select_decode_kernel', 'nms_kernel', 'iou_pairs_kernel', 'bias_act_kernel',
                 'snap_to_anchors_kernel', 'gemm_bias_act', 'retina_loss_kernel', 'select_hist_kernel', 'select_filter_kernel',
                 'nms_first_round_kernel', 'rotated_sup_matrix_kernel', 'bias_act_maxpool_kernel', 'upsample_nearest2x_kernel',
-                'stem_pack_kernel', 'loss_reduce_kernel', 'atss_stats_kernel', 'bottleneck_seam_kernel')
+                'stem_pack_kernel', 'loss_reduce_kernel', 'atss_stats_kernel', 'bottleneck_seam_kernel', 'tower_conv3x3_kernel')
 # HBM bytes the epilogue entry points move, per kernel name, while `traffic_count` is on (bench.py's epilogue_roofline: the
 # algorithmic bytes of every call -- each element read once and written once, + the skip input -- divided by the kernel time)
 traffic_count = False
@@ -1332,6 +1334,30 @@ def bottleneck_seam(y2, skip, w3, b3, w1, b1):
             w3.data_ptr(), b3.data_ptr(), w1.data_ptr(), b1.data_ptr(), b * h * w, k, c, n, _DTYPES[y2.dtype])
     _count('bottleneck_seam_kernel', (y2.numel() + skip.numel() + out.numel() + z.numel()) * y2.element_size())
     return out, z
+
+
+def tower_conv3x3(x, weight, bias, relu=True):
+    """act(conv2d(x, weight, padding=1) + bias) of a channels_last bf16 / fp16 activation by the library's own implicit-GEMM MFMA
+    kernel (csrc/tower_conv.hpp; include/odtk_hip.h: odtk_tower_conv3x3): the head towers' 3x3, stride 1, 256 -> 256 convolutions.
+    x [B, 256, H, W] channels_last, weight [256, 256, 3, 3] channels_last, bias [256] of x.dtype.  Anything else raises."""
+    if not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError('tower_conv3x3: x must be a 4-d CUDA tensor of bfloat16/float16')
+    b, c, h, w = x.shape
+    n = weight.shape[0]
+    if (weight.dim() != 4 or tuple(weight.shape[1:]) != (c, 3, 3) or weight.dtype != x.dtype or weight.device != x.device
+            or not weight.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError('tower_conv3x3: weight must be a channels_last [Cout, %d, 3, 3] tensor of x.dtype' % c)
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('tower_conv3x3: x must be channels_last')
+    if bias.dtype != x.dtype or bias.numel() != n or bias.device != x.device or not bias.is_contiguous():
+        raise RuntimeError('tower_conv3x3: bias must be a dense vector of length Cout of x.dtype')
+    y = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if y.numel() == 0:
+        return y
+    _launch(library().odtk_tower_conv3x3, 'tower_conv3x3', x.device, y.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+            b, h, w, c, n, _DTYPES[x.dtype], 1 if relu else 0)
+    _count('tower_conv3x3_kernel', (x.numel() + y.numel()) * x.element_size())
+    return y
 
 
 # ---- libodtk_conv.so: k x k convolution with the bias + ReLU in its own epilogue (csrc/conv_ck.cpp) -----------------------------

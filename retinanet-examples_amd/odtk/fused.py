@@ -19,6 +19,9 @@ Measured on MI355X those passes cost more than the convolutions between them.  H
     read back by the GEMM that follows it (DESIGN.md section 5);
   * the head towers of the pyramid levels below P3 run as ONE convolution per layer over a packed canvas with zero gutters
     between the levels (`pyramid_canvas_layout`, `_canvas_towers`; DESIGN.md section 5) instead of one launch per level;
+  * the 3x3 256 -> 256 convolutions of the head towers on P3 and the first smoothing convolution run on the library's own
+    implicit-GEMM MFMA kernel (`odtk_tower_conv3x3`, csrc/tower_conv.hpp) instead of the convolution
+    library's instance: the same bits, 1.15x the rate;
   * the post-processing reads the raw head tensors in place (odtk.box.detect(..., logits=True)); in
     `forward` even the bias of the heads' LAST convolutions is not applied by a pass of its own: it is
     handed to the post-processing kernels (`cls_bias` / `box_bias`), which add it in fp32 to the few values
@@ -134,9 +137,22 @@ class _Conv(nn.Module):
       * 1x1: ONE hipBLASLt GEMM with the whole epilogue (`odtk_gemm_bias_act`);
       * k x k without a skip input, 16-bit: ONE composable_kernel implicit-GEMM convolution with bias + ReLU in its own
         epilogue (`odtk_conv_bias_act`, csrc/conv_ck.cpp) -- where the engine's plan pass measured it faster than
-      * the MIOpen convolution followed by the HIP epilogue pass `odtk_bias_act` (in place)."""
+      * the MIOpen convolution followed by the HIP epilogue pass `odtk_bias_act` (in place);
+      * 3x3, stride 1, padding 1, 256 -> 256, 16-bit, on a run of pixels long enough to fill the chip twice (the head towers on
+        P3, the first smoothing convolution) and routed to the convolution library: the library's own
+        implicit-GEMM kernel (`odtk_tower_conv3x3`, csrc/tower_conv.hpp) in the instance's place; the two routes above stay
+        measured, recorded and the fallback."""
 
     use_conv_library = True   # set False to A/B the whole engine against round 4's graph
+    # the own 3x3 kernel (FusedRetinaNet.tower_conv sets it per engine; ODTK_TOWER_CONV=0: the vendor routes only, as before)
+    tower_conv = os.environ.get('ODTK_TOWER_CONV', '1') != '0'
+    # ... from this many pixels on: P3 of the flagship shape (8 x 100 x 160 = 128 000 pixels, 500 of the kernel's 256-pixel tiles),
+    # where the kernel's median launch is 146 us against 169 us of the library's pinned 256 x 256 x 32 instance AND returns its bits
+    # (the kernel's MFMAs sum the same k in the same slots: 0 of 32.8 M outputs differ, profiles/tower_conv_probe.txt).  On the
+    # pyramid canvas (48 400 pixels) it is faster too, but the library runs a 64-deep instance there whose sums group differently
+    # (327 of 12.4 M outputs differ by a bf16 step, enough to re-order the benchmark's near-tied detections): left to the library.
+    # Shorter runs (P4, P5 alone) are slower: a tile's 36 K-tiles run one after the other whatever the shape
+    tower_min_pixels = 100000
     # 'auto': every undecided k x k shape is measured both ways by the plan pass (a stopwatch: the routes -- and with them the
     # engine's bits, the library epilogue adds its bias in the activation dtype -- can differ from box to box); 'library' /
     # 'two_pass': no measurement, every layer the library supports / no layer goes through it (deterministic; ODTK_CONV_ROUTE).
@@ -160,6 +176,9 @@ class _Conv(nn.Module):
                            and dtype in (torch.bfloat16, torch.float16) and w.shape[1] % 8 == 0)
         self.strided_ok = (self.pointwise and tuple(conv.stride) != (1, 1) and dtype in (torch.bfloat16, torch.float16)
                            and w.shape[1] % 8 == 0)
+        # what `odtk_tower_conv3x3` takes (include/odtk_hip.h)
+        self.tower_ok = (tuple(w.shape) == (256, 256, 3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+                         and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and dtype in (torch.bfloat16, torch.float16))
         self.zero_bias = None
         self.learned = {}                                               # kind ('act' | 'only') -> the last measured decision: unplanned geometries follow it
         self.route = {}                                                 # input shape -> (use the library, us library, us miopen + epilogue)
@@ -168,17 +187,33 @@ class _Conv(nn.Module):
         """The convolution without its epilogue (the caller owns the bias: the heads' last convolutions, whose bias the
         post-processing kernels add).  Routed like `forward`: the library's instance list is a second find space for the same
         contraction (a zero bias, no clamp), taken where the plan pass measured it faster than MIOpen's pick."""
+        library = False
         if (self.library_ok and _Conv.use_conv_library and x.is_cuda and x.is_contiguous(memory_format=torch.channels_last)
                 and _C.conv_available()):
             key = ('only',) + tuple(x.shape)
             if self.zero_bias is None:
                 self.zero_bias = torch.zeros_like(self.bias_lp)
-            if self._routed(key, 'only', x, self._miopen_only, self._library_only):
-                try:
-                    return self._library_only(x)
-                except RuntimeError:
-                    self.route[key] = (False, float('inf'), 0.0)
+            library = self._routed(key, 'only', x, self._miopen_only, self._library_only)      # (a plan pass measures here)
+        if library and self._tower_takes(x):
+            try:
+                return _C.tower_conv3x3(x, self.weight, self.zero_bias, False)
+            except RuntimeError:
+                pass
+        if library:
+            try:
+                return self._library_only(x)
+            except RuntimeError:
+                self.route[key] = (False, float('inf'), 0.0)
         return self._miopen_only(x)
+
+    def _tower_takes(self, x, residual=None):
+        """Does this input go through the own 3x3 kernel (class docstring)?  Asked only where the layer is routed to the library's
+        fused epilogue, whose drop-in the kernel is (the same two roundings, the bias in the activation dtype): a layer on the
+        two-pass route -- every layer of an engine no plan pass has routed -- keeps MIOpen's bits.  `on_view` rectangles never do:
+        they are not contiguous."""
+        return (self.tower_ok and self.tower_conv and residual is None and x.is_cuda and x.dim() == 4 and x.dtype == self.weight.dtype
+                and x.is_contiguous(memory_format=torch.channels_last)
+                and x.shape[0] * x.shape[2] * x.shape[3] >= self.tower_min_pixels)
 
     def on_view(self, x, only=False):
         """`forward` (or `conv_only`) on a spatial window of a larger channels_last tensor -- a level's rectangle of the pyramid
@@ -264,13 +299,21 @@ class _Conv(nn.Module):
                             self.route[tuple(x.shape)] = (False, float('inf'), 0.0)
                 return self._copy_then_gemm(x, residual)
             return _C.gemm_bias_act(x, self.weight, self.bias, residual, self.relu)
+        library = False
         if (residual is None and self.library_ok and _Conv.use_conv_library and x.is_cuda
                 and x.is_contiguous(memory_format=torch.channels_last) and _C.conv_available()):
-            if self._routed(tuple(x.shape), 'act', x, self._two_pass, self._one_pass):
-                try:
-                    return self._one_pass(x)
-                except RuntimeError:                                    # an unplanned geometry no instance takes: remember, fall through
-                    self.route[tuple(x.shape)] = (False, float('inf'), 0.0)
+            # (a plan pass measures and records the two vendor routes here whether or not the own kernel then runs the layer)
+            library = self._routed(tuple(x.shape), 'act', x, self._two_pass, self._one_pass)
+        if library and self._tower_takes(x, residual):
+            try:
+                return _C.tower_conv3x3(x, self.weight, self.bias_lp, self.relu)
+            except RuntimeError:                                        # refused: today's routes
+                pass
+        if library:
+            try:
+                return self._one_pass(x)
+            except RuntimeError:                                        # an unplanned geometry no instance takes: remember, fall through
+                self.route[tuple(x.shape)] = (False, float('inf'), 0.0)
         return self._two_pass(x, residual)
 
     def _routed(self, key, kind, x, two, one):
@@ -378,6 +421,7 @@ class FusedRetinaNet(nn.Module):
         blocks = [b for layer in self.layers for b in layer]
         self._seams = {a: b for a, b in zip(blocks, blocks[1:]) if a.seam_to(b, dtype)}
         self.seam_fusion = os.environ.get('ODTK_SEAM_FUSION', '1') != '0'
+        self._tower_conv = _Conv.tower_conv
         self.outputs = list(net.outputs)
         self.lateral = nn.ModuleList([_Conv(fpn.lateral3, None, False, dtype), _Conv(fpn.lateral4, None, False, dtype),
                                       _Conv(fpn.lateral5, None, False, dtype)])
@@ -406,6 +450,19 @@ class FusedRetinaNet(nn.Module):
         self._graphs = {}                                               # input geometry + bias state -> (hipGraph, static input, outputs, tables kept alive)
         self._thresholds = {}                                           # score threshold -> the prefilter's table for cls_head[-1].bias
         self.max_graphs = 8
+
+    @property
+    def tower_conv(self):
+        """The own kernel for the 3x3 256 -> 256 convolutions (`_Conv`, fourth route); ODTK_TOWER_CONV=0 / False: the parent's graph
+        (A/B).  Part of the key of `replay`."""
+        return self._tower_conv
+
+    @tower_conv.setter
+    def tower_conv(self, on):
+        self._tower_conv = bool(on)
+        for mod in self.modules():
+            if isinstance(mod, _Conv):
+                mod.tower_conv = self._tower_conv
 
     def _stem_direct(self, x):
         x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
@@ -605,7 +662,7 @@ class FusedRetinaNet(nn.Module):
         m = self.model[0]                                                # (post-processing parameters are baked into the launches)
         bias = self.cls_head[-1].bias                                    # its state is baked in too: the prefilter's threshold table
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
-               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, self.seam_fusion, bias.data_ptr(), bias._version,
+               m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, self.seam_fusion, self.tower_conv, bias.data_ptr(), bias._version,
                tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None,     # (the suppression rule is baked in as well,
                getattr(m, 'box_voting', None))                                                               #  and so is box voting)
         if getattr(m, 'tta', None) is not None:
