@@ -223,6 +223,44 @@ int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *output
                   uint32_t flags, void *workspace, size_t workspace_size, void *stream);
 
 /*
+ * odtk_matrix_nms -- class-aware Matrix NMS (Wang et al., SOLOv2, 2020; mmdetection's mask_matrix_nms, PaddleDetection's
+ * matrix_nms) on axis-aligned boxes; no reference equivalent.  Inputs, outputs and the optional 4th int32 output as for
+ * odtk_nms_ex / odtk_soft_nms.  Every candidate's score is multiplied by one factor that comes from pairwise IoUs alone: nothing
+ * is serial, and count may be anything in 1..ODTK_MAX_NMS_COUNT_SCRATCH.  Per image, in float32, no FMA contraction:
+ *   participants  the candidates with score > 0 (NaN is not), ranked by score descending, ties by lowest input position; only
+ *                 the first n = min(pre_top, #positive) take part, the rest are dropped.
+ *   iou(a, b)     the IoU of odtk_soft_nms, operation for operation: +1 pixel, torch max / min / clamp NaN rules,
+ *                 inter / ((area_a + area_b) - inter).  Bitwise symmetric.
+ *   cmax_i        max(+0, iou(k, i)) over the participants k of i's class ranked before i, evaluated as
+ *                 `acc = iou > acc ? iou : acc` from acc = 0: a NaN IoU is skipped, whatever the order.
+ *   decay_j       min(1, d(i, j)) over the participants i of j's class ranked before j, evaluated as `acc = d < acc ? d : acc`
+ *                 from acc = 1: a NaN or +inf d (a division by 1 - cmax_i = 0) decides nothing.
+ *                   ODTK_MATRIX_NMS_LINEAR    d = (1 - iou(i, j)) / (1 - cmax_i)        two subtractions, one IEEE division
+ *                   ODTK_MATRIX_NMS_GAUSSIAN  d = exp(((cmax_i * cmax_i) - (iou * iou)) / sigma)   four float32 operations and
+ *                                             one correctly rounded exp; dividing by sigma as odtk_soft_nms does: sigma = 0.5
+ *                                             is mmdetection's sigma = 2.0
+ *                 The first participant of a class has decay 1.  mmdetection takes the minimum of the whole column of its decay
+ *                 matrix instead; row 0 of that matrix (cmax = 0) holds 1 - iou or exp(-iou^2 / sigma), never above 1, so the
+ *                 two agree.
+ *   output        s'_j = score_j * decay_j, one multiplication; j is alive iff s'_j >= min_score.  The alive participants are
+ *                 emitted in order of s' descending, ties by lowest input position, at most detections_per_im of them, each
+ *                 with s', its unchanged box, its class and (4th output) its input position.  Unused slots are zero (index -1).
+ * There is no nms_thresh.  max and min do not depend on the order of evaluation: the same bits on every run.
+ * ODTK_ERR_INVALID: a null pointer, batch_size < 1, count outside 1..ODTK_MAX_NMS_COUNT_SCRATCH, detections_per_im outside
+ * 1..ODTK_MAX_NMS_DETECTIONS, pre_top outside 1..ODTK_MAX_MATRIX_NMS_PRE, a method that is neither of the two, sigma or min_score
+ * not finite or not > 0, any undefined flag bit.  ODTK_FLAG_ROTATED is ODTK_ERR_UNSUPPORTED.  Everything is checked on the host
+ * before anything touches HIP.  Workspace: two-phase query as everywhere (the positive candidates' keys, 8 bytes per candidate,
+ * and 36 bytes per participant).  Four launches (csrc/matrix_nms.hpp: rank, cmax, decay, emit), no host synchronisation, timed
+ * under ODTK_KERNEL_NMS.
+ */
+#define ODTK_MATRIX_NMS_LINEAR   1
+#define ODTK_MATRIX_NMS_GAUSSIAN 2
+#define ODTK_MAX_MATRIX_NMS_PRE  4096
+int odtk_matrix_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                    int detections_per_im, int pre_top, int method, float sigma, float min_score, uint32_t flags,
+                    void *workspace, size_t workspace_size, void *stream);
+
+/*
  * odtk_box_vote -- box voting behind a suppression (Gidaris & Komodakis 2015; Detectron's bbox_vote) on axis-aligned boxes; no
  * reference equivalent.  Per image the inputs are the SUPPRESSION'S INPUT LIST -- inputs[0..2] = scores [batch, count], boxes
  * [batch, count, 4], classes [batch, count], float32, as odtk_nms takes them -- and kept, int32 [batch, detections_per_im]: the

@@ -1,4 +1,4 @@
-// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS, box voting, candidate concatenation, the merge of tiled inference and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
+// nms.hip -- NMS (axis-aligned, rotated staged), Soft-NMS, Matrix NMS, box voting, candidate concatenation, the merge of tiled inference and odtk_iou; nms_impl is what odtk_detect calls (internal.hpp).
 #include <cmath>
 #include <cstring>
 
@@ -6,6 +6,7 @@
 #include "iou.hpp"
 #include "nms.hpp"
 #include "soft_nms.hpp"
+#include "matrix_nms.hpp"
 #include "box_vote.hpp"
 #include "tile.hpp"
 
@@ -223,6 +224,68 @@ int odtk_soft_nms(int batch_size, const void *const *inputs, void *const *output
   sa.min_score = min_score;
   return method == ODTK_SOFT_NMS_GAUSSIAN ? soft_nms_launch<true>(sa, batch_size, static_cast<hipStream_t>(stream))
                                           : soft_nms_launch<false>(sa, batch_size, static_cast<hipStream_t>(stream));
+}
+
+// everything is validated here, on the host, before anything touches the device
+int odtk_matrix_nms(int batch_size, const void *const *inputs, void *const *outputs, int n_outputs, size_t count,
+                    int detections_per_im, int pre_top, int method, float sigma, float min_score, uint32_t flags,
+                    void *workspace, size_t workspace_size, void *stream) {
+  if (batch_size <= 0 || count == 0 || count > ODTK_MAX_NMS_COUNT_SCRATCH || detections_per_im <= 0 ||
+      detections_per_im > ODTK_MAX_NMS_DETECTIONS || pre_top <= 0 || pre_top > ODTK_MAX_MATRIX_NMS_PRE)
+    return ODTK_ERR_INVALID;
+  if (method != ODTK_MATRIX_NMS_LINEAR && method != ODTK_MATRIX_NMS_GAUSSIAN) return ODTK_ERR_INVALID;
+  if (!std::isfinite(sigma) || !(sigma > 0.0f) || !std::isfinite(min_score) || !(min_score > 0.0f)) return ODTK_ERR_INVALID;
+  if (flags & ~(ODTK_FLAG_ROTATED | ODTK_FLAG_LOGITS | ODTK_FLAG_ROTATED_NMS_FIXED_ANGLE)) return ODTK_ERR_INVALID;
+  if (flags & ODTK_FLAG_ROTATED) return ODTK_ERR_UNSUPPORTED;
+  // workspace: [keys of the positive candidates | the participants in rank order: boxes, classes, scores, positions, cmax, decay | n]
+  const size_t batch = static_cast<size_t>(batch_size);
+  const size_t stride = (static_cast<size_t>(pre_top) + odtk::kMatCols - 1) / odtk::kMatCols * odtk::kMatCols;
+  const size_t off_box = align_up(sizeof(uint64_t) * batch * count);
+  const size_t off_cls = off_box + align_up(sizeof(float) * 4 * batch * stride);
+  const size_t per = align_up(sizeof(float) * batch * stride);
+  const size_t off_n = off_cls + 5 * per;
+  const size_t need = off_n + align_up(sizeof(uint32_t) * batch);
+  if (need > 0x7fffffffull) return ODTK_ERR_INVALID;
+  if (!workspace || !workspace_size) return static_cast<int>(need);
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (!inputs || !outputs || n_outputs < 3) return ODTK_ERR_INVALID;
+  for (int i = 0; i < 3; ++i)
+    if (!inputs[i] || !outputs[i]) return ODTK_ERR_INVALID;
+  odtk::MatrixNmsArgs ma;
+  std::memset(&ma, 0, sizeof ma);
+  ma.scores = static_cast<const float *>(inputs[0]);
+  ma.boxes = static_cast<const float *>(inputs[1]);
+  ma.classes = static_cast<const float *>(inputs[2]);
+  ma.out_scores = static_cast<float *>(outputs[0]);
+  ma.out_boxes = static_cast<float *>(outputs[1]);
+  ma.out_classes = static_cast<float *>(outputs[2]);
+  ma.out_indices = n_outputs > 3 ? static_cast<int32_t *>(outputs[3]) : nullptr;
+  char *ws = static_cast<char *>(workspace);
+  ma.keys = reinterpret_cast<unsigned long long *>(ws);
+  ma.r_box = reinterpret_cast<float *>(ws + off_box);
+  ma.r_cls = reinterpret_cast<float *>(ws + off_cls);
+  ma.r_score = reinterpret_cast<float *>(ws + off_cls + per);
+  ma.r_pos = reinterpret_cast<uint32_t *>(ws + off_cls + 2 * per);
+  ma.r_cmax = reinterpret_cast<uint32_t *>(ws + off_cls + 3 * per);
+  ma.r_decay = reinterpret_cast<uint32_t *>(ws + off_cls + 4 * per);
+  ma.r_n = reinterpret_cast<uint32_t *>(ws + off_n);
+  ma.count = static_cast<uint32_t>(count);
+  ma.stride = static_cast<uint32_t>(stride);
+  ma.pre_top = static_cast<uint32_t>(pre_top);
+  ma.ndet = detections_per_im;
+  ma.sigma = sigma;
+  ma.min_score = min_score;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // pair tiles: 64 columns x 256 rows; the ones above the diagonal or beyond an image's participants leave at once
+  const unsigned tiles = static_cast<unsigned>((stride / odtk::kMatCols) * ((stride + odtk::kMatRows - 1) / odtk::kMatRows));
+  const dim3 pair_grid(static_cast<unsigned>(batch_size), tiles), pair_block(odtk::kMatPairThreads);
+  timed_launch(ODTK_KERNEL_NMS, odtk::matrix_nms_rank_kernel, dim3(batch_size), dim3(odtk::kMatThreads), 0, s, ma);
+  timed_launch(ODTK_KERNEL_NMS, odtk::matrix_nms_pairs_kernel<0>, pair_grid, pair_block, 0, s, ma);
+  if (method == ODTK_MATRIX_NMS_GAUSSIAN) timed_launch(ODTK_KERNEL_NMS, odtk::matrix_nms_pairs_kernel<2>, pair_grid, pair_block, 0, s, ma);
+  else timed_launch(ODTK_KERNEL_NMS, odtk::matrix_nms_pairs_kernel<1>, pair_grid, pair_block, 0, s, ma);
+  timed_launch(ODTK_KERNEL_NMS, odtk::matrix_nms_emit_kernel, dim3(batch_size), dim3(odtk::kMatThreads), 0, s, ma);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
 }
 
 // everything is validated here, on the host, before anything touches the device

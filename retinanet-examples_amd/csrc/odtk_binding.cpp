@@ -6,7 +6,7 @@
 //     iou(boxes, anchors)                                                           -> [Tensor[num_anchors, num_boxes]]
 //     Engine                                                                        -> placeholder (TensorRT dropped)
 //
-// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `box_vote`, `concat_candidates`, `tile_images`, `merge_tile_candidates`, `tal_assign_levels` and `rotated_box_loss_levels_forward` / `_backward`.  It is what
+// with the reference's positional signatures, plus `detect` (all pyramid levels + NMS in one enqueue), `soft_nms`, `matrix_nms`, `box_vote`, `concat_candidates`, `tile_images`, `merge_tile_candidates`, `tal_assign_levels` and `rotated_box_loss_levels_forward` / `_backward`.  It is what
 // INTEGRATION.md section 2 tells a maintainer of the reference to write: no kernel lives here -- every function
 // checks its tensors like the reference does (CUDA + contiguous -> RuntimeError), allocates outputs and scratch with
 // torch, and makes the two-phase C ABI call on torch's current HIP stream with the GIL released.  Built by
@@ -138,6 +138,34 @@ std::vector<torch::Tensor> soft_nms(torch::Tensor scores, torch::Tensor boxes, t
     with_scratch(scores, "soft_nms", [&](void *ws, size_t size) {
       return odtk_soft_nms(static_cast<int>(batch), ws ? in : nullptr, ws ? out : nullptr, n_out, static_cast<size_t>(count),
                            detections_per_im, nms_thresh, method, sigma, min_score, 0u, ws, size, ws ? stream : nullptr);
+    });
+  }
+  return result;
+}
+
+// Matrix NMS (odtk_matrix_nms: no reference equivalent), the signature of odtk/_C.py:matrix_nms
+std::vector<torch::Tensor> matrix_nms(torch::Tensor scores, torch::Tensor boxes, torch::Tensor classes, int detections_per_im,
+                                      int pre_top, int method, float sigma, float min_score, bool return_indices) {
+  require_gpu_contiguous(scores, "scores");
+  require_gpu_contiguous(boxes, "boxes");
+  require_gpu_contiguous(classes, "classes");
+  TORCH_CHECK(scores.dim() == 2 && boxes.dim() == 3 && boxes.size(2) == 4 && boxes.size(0) == scores.size(0) &&
+              boxes.size(1) == scores.size(1) && classes.sizes() == scores.sizes(), "matrix_nms: inconsistent shapes");
+  const int64_t batch = scores.size(0), count = scores.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+  auto opt = scores.options();
+  std::vector<torch::Tensor> result = {torch::empty({batch, detections_per_im}, opt), torch::empty({batch, detections_per_im, 4}, opt),
+                                       torch::empty({batch, detections_per_im}, opt)};
+  if (return_indices) result.push_back(torch::empty({batch, detections_per_im}, opt.dtype(torch::kInt32)));
+  const void *in[3] = {scores.data_ptr(), boxes.data_ptr(), classes.data_ptr()};
+  void *out[4] = {result[0].data_ptr(), result[1].data_ptr(), result[2].data_ptr(), return_indices ? result[3].data_ptr() : nullptr};
+  const int n_out = return_indices ? 4 : 3;
+  void *stream = current_stream(scores);
+  {
+    pybind11::gil_scoped_release nogil;
+    with_scratch(scores, "matrix_nms", [&](void *ws, size_t size) {
+      return odtk_matrix_nms(static_cast<int>(batch), ws ? in : nullptr, ws ? out : nullptr, n_out, static_cast<size_t>(count),
+                             detections_per_im, pre_top, method, sigma, min_score, 0u, ws, size, ws ? stream : nullptr);
     });
   }
   return result;
@@ -503,6 +531,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rotated") = false);
   m.def("soft_nms", &soft_nms, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("nms_thresh"),
         py::arg("detections_per_im"), py::arg("method"), py::arg("sigma"), py::arg("min_score"), py::arg("return_indices") = false);
+  m.def("matrix_nms", &matrix_nms, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("ndetections"), py::arg("pre_top"),
+        py::arg("method"), py::arg("sigma"), py::arg("min_score"), py::arg("return_indices") = false);
   m.def("box_vote", &box_vote, py::arg("scores"), py::arg("boxes"), py::arg("classes"), py::arg("kept"), py::arg("vote_thresh"));
   m.def("concat_candidates", &concat_candidates, py::arg("parts"), py::arg("mirror_widths"));
   m.def("tile_images", &tile_images, py::arg("x"), py::arg("tiles"), py::arg("size"));

@@ -10,7 +10,7 @@ conventions, so `from ._C import decode, nms, iou` in a box.py keeps working:
     Engine                                                                        -> placeholder (TensorRT dropped)
 
 plus the MI355X-first batched forms (`decode_levels`, `detect`) that cover all pyramid levels of
-the whole batch in one enqueue, `soft_nms` (linear / Gaussian Soft-NMS), `box_vote` (box voting behind a suppression) and
+the whole batch in one enqueue, `soft_nms` (linear / Gaussian Soft-NMS), `matrix_nms` (linear / Gaussian Matrix NMS), `box_vote` (box voting behind a suppression) and
 `concat_candidates` (the merge of flip test-time augmentation), `tile_images` and `merge_tile_candidates` (tiled inference of
 large images): no reference equivalents.
 
@@ -34,6 +34,8 @@ MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32
 MAX_CONCAT_PARTS = 8
 MAX_TILES = 64
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
+MATRIX_NMS_LINEAR, MATRIX_NMS_GAUSSIAN = 1, 2
+MAX_MATRIX_NMS_PRE = 4096
 ATSS_MAX_TOPK = 16
 BOX_LOSS_IOU, BOX_LOSS_GIOU, BOX_LOSS_DIOU = 1, 2, 3
 BOX_LOSS_KINDS = {'iou': BOX_LOSS_IOU, 'giou': BOX_LOSS_GIOU, 'diou': BOX_LOSS_DIOU}
@@ -186,6 +188,8 @@ _SIGNATURES = {
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_soft_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _vp, _sz, _vp]),
+    'odtk_matrix_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_box_vote': (ctypes.c_int, [ctypes.c_int, _vpp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, _vp]),
     'odtk_concat_candidates': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Candidates), _vpp, ctypes.c_uint32, _vp]),
     'odtk_tile_images': (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 7 + [ctypes.POINTER(Tile), ctypes.c_int, ctypes.c_int, _vp]),
@@ -398,6 +402,22 @@ def soft_nms(scores, boxes, classes, nms_thresh, detections_per_im, method, sigm
     out = _detections(batch, detections_per_im, 4, scores.device, return_indices)
     _enqueue(lib.odtk_soft_nms, 'soft_nms', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
              int(detections_per_im), float(nms_thresh), int(method), float(sigma), float(min_score), 0)
+    return out
+
+
+def matrix_nms(scores, boxes, classes, ndetections, pre_top, method, sigma, min_score, return_indices=False):
+    """Class-aware Matrix NMS on axis-aligned boxes (include/odtk_hip.h: odtk_matrix_nms; no reference equivalent): four launches,
+    any list length.  method: MATRIX_NMS_LINEAR / MATRIX_NMS_GAUSSIAN; emitted scores are the decayed ones."""
+    _check_input(scores, 'scores')
+    _check_input(boxes, 'boxes')
+    _check_input(classes, 'classes')
+    lib = library()
+    batch, count = scores.shape
+    if boxes.shape != (batch, count, 4) or classes.shape != (batch, count):
+        raise RuntimeError('matrix_nms: inconsistent shapes')
+    out = _detections(batch, ndetections, 4, scores.device, return_indices)
+    _enqueue(lib.odtk_matrix_nms, 'matrix_nms', scores.device, batch, _ptrs([scores, boxes, classes]), _ptrs(out), len(out), count,
+             int(ndetections), int(pre_top), int(method), float(sigma), float(min_score), 0)
     return out
 
 

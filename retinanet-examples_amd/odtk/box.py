@@ -669,6 +669,53 @@ def _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, 
     return scores_out, boxes_out, classes_out, index_out
 
 
+def _matrix_nms_cpu(all_scores, all_boxes, all_classes, ndetections, method, sigma, min_score, pre_top):
+    """CPU branch of `matrix_nms`: Matrix NMS (Wang et al., SOLOv2, 2020), class-aware, float32 with `_soft_nms_cpu`'s +1 pixel
+    IoU in its operation order.  Per image the candidates with score > 0 are ranked (score descending, ties by position) and the
+    first `pre_top` take part.  With iou[i, j] over the participants and pair(i, j) = i ranks before j and both have one class:
+      cmax[j]  = max(0, iou[i, j] over pair(i, j))                 (a NaN IoU is skipped)
+      d[i, j]  = (1 - iou[i, j]) / (1 - cmax[i])                   linear
+               = exp((cmax[i] * cmax[i] - iou[i, j] * iou[i, j]) / sigma)   gaussian (the double exp rounded once)
+      decay[j] = min(1, d[i, j] over pair(i, j))                   (a NaN or +inf d is skipped)
+    and participant j comes out with score * decay[j] where that is >= min_score, ordered by it (ties by position)."""
+    all_scores, all_boxes, all_classes = all_scores.float(), all_boxes.float(), all_classes.float()
+    batch = all_scores.shape[0]
+    scores_out = all_scores.new_zeros((batch, ndetections))
+    boxes_out = all_scores.new_zeros((batch, ndetections, 4))
+    classes_out = all_scores.new_zeros((batch, ndetections))
+    index_out = torch.full((batch, ndetections), -1, dtype=torch.int32)
+    sigma = torch.tensor(sigma, dtype=torch.float32)
+    for image in range(batch):
+        order = torch.sort(all_scores[image], descending=True, stable=True)[1]
+        order = order[all_scores[image][order] > 0][:pre_top]                    # (a NaN is not > 0)
+        n = int(order.numel())
+        if n == 0:
+            continue
+        scores, boxes, classes = all_scores[image][order], all_boxes[image][order], all_classes[image][order]
+        area = (boxes[:, 2] - boxes[:, 0] + 1) * (boxes[:, 3] - boxes[:, 1] + 1)
+        lo = torch.max(boxes[:, None, :2], boxes[None, :, :2])
+        hi = torch.min(boxes[:, None, 2:], boxes[None, :, 2:])
+        wh = (hi - lo + 1).clamp(0)
+        inter = wh[..., 0] * wh[..., 1]
+        iou = inter / ((area[None, :] + area[:, None]) - inter)
+        rank = torch.arange(n)
+        pair = (rank[:, None] < rank[None, :]) & (classes[:, None] == classes[None, :])
+        cmax = torch.where(pair & (iou > 0), iou, torch.zeros_like(iou)).amax(0)
+        if method == 'gaussian':
+            d = torch.exp((((cmax * cmax)[:, None] - iou * iou) / sigma).double()).float()
+        else:
+            d = (1 - iou) / (1 - cmax)[:, None]
+        decay = torch.where(pair & (d < 1), d, torch.ones_like(d)).amin(0)
+        decayed = scores * decay
+        alive = torch.nonzero(decayed >= min_score).view(-1)
+        alive = alive[torch.sort(order[alive], stable=True)[1]]                  # by position, then (stable) by decayed score
+        alive = alive[torch.sort(decayed[alive], descending=True, stable=True)[1]][:ndetections]
+        kept = int(alive.numel())
+        scores_out[image, :kept], boxes_out[image, :kept], classes_out[image, :kept] = decayed[alive], boxes[alive], classes[alive]
+        index_out[image, :kept] = order[alive].to(torch.int32)
+    return scores_out, boxes_out, classes_out, index_out
+
+
 def decode(all_cls_head, all_box_head, stride=1, threshold=0.05, top_n=1000, anchors=None, rotated=False):
     """Box decoding and filtering for one pyramid level (reference box.py:255-309).
 
@@ -713,6 +760,41 @@ def soft_nms(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, metho
         return _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score)[:3]
     return _C.soft_nms(all_scores.float().contiguous(), all_boxes.float().contiguous(), all_classes.float().contiguous(),
                        nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score)
+
+
+MATRIX_NMS_METHODS = {'linear': _C.MATRIX_NMS_LINEAR, 'gaussian': _C.MATRIX_NMS_GAUSSIAN}
+MAX_MATRIX_NMS_PRE = _C.MAX_MATRIX_NMS_PRE         # participants per image odtk_matrix_nms ranks
+
+
+def _matrix_nms_options(method, sigma, min_score, pre_top):
+    if method not in MATRIX_NMS_METHODS:
+        raise ValueError("matrix_nms: method must be 'linear' or 'gaussian', not %r" % (method,))
+    sigma, min_score = float(sigma), float(min_score)
+    if not (math.isfinite(sigma) and sigma > 0 and math.isfinite(min_score) and min_score > 0):
+        raise ValueError('matrix_nms: sigma and min_score must be finite and > 0')
+    if isinstance(pre_top, bool) or int(pre_top) != pre_top or not 1 <= pre_top <= MAX_MATRIX_NMS_PRE:
+        raise ValueError('matrix_nms: pre_top must be a whole number in 1..%d, not %r' % (MAX_MATRIX_NMS_PRE, pre_top))
+    return method, sigma, min_score, int(pre_top)
+
+
+def _matrix_nms_dict(matrix_nms, threshold):
+    """The options of a `matrix_nms` dict, validated: (method, sigma, min_score, pre_top)."""
+    unknown = set(matrix_nms) - {'method', 'sigma', 'min_score', 'pre_top'}
+    if unknown:
+        raise ValueError('matrix_nms: unknown option(s) %s' % ', '.join(sorted(unknown)))
+    return _matrix_nms_options(matrix_nms.get('method', 'gaussian'), matrix_nms.get('sigma', 0.5),
+                               matrix_nms.get('min_score', threshold), matrix_nms.get('pre_top', 2000))
+
+
+def matrix_nms(all_scores, all_boxes, all_classes, ndetections=100, method='gaussian', sigma=0.5, min_score=0.001, pre_top=2000):
+    """Batched class-aware Matrix NMS on axis-aligned boxes (no reference equivalent; definition at `_matrix_nms_cpu`): every
+    score is decayed by one factor that comes from the pairwise IoUs of the `pre_top` best candidates; the returned scores are the
+    decayed ones, non-increasing.  There is no IoU threshold, and no limit on the length of the candidate list."""
+    method, sigma, min_score, pre_top = _matrix_nms_options(method, sigma, min_score, pre_top)
+    if not all_scores.is_cuda:
+        return _matrix_nms_cpu(all_scores, all_boxes, all_classes, ndetections, method, sigma, min_score, pre_top)[:3]
+    return _C.matrix_nms(all_scores.float().contiguous(), all_boxes.float().contiguous(), all_classes.float().contiguous(),
+                         ndetections, pre_top, MATRIX_NMS_METHODS[method], sigma, min_score)
 
 
 def _vote_option(vote):
@@ -905,10 +987,14 @@ def merge_tile_candidates(parts, tiles, batch, slots, size, extent, border=0.0, 
     return out
 
 
-def suppress(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, soft_nms=None, vote=None, threshold=0.05):
+def suppress(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, soft_nms=None, vote=None, threshold=0.05, matrix_nms=None):
     """The tail of the post-processing on ONE candidate list of axis-aligned boxes: hard NMS, or Soft-NMS when `soft_nms` is a dict
-    (`method`, `sigma`, `min_score`: default `threshold`), then box voting at IoU `vote` when that is not None.
-    -> (scores [B, D], boxes [B, D, 4], classes [B, D]).  GPU tensors: one launch for the suppression and one for the vote."""
+    (`method`, `sigma`, `min_score`: default `threshold`), or Matrix NMS when `matrix_nms` is a dict (`method`, `sigma`,
+    `min_score`: default `threshold`, `pre_top`: default 2000), then box voting at IoU `vote` when that is not None.
+    -> (scores [B, D], boxes [B, D, 4], classes [B, D]).  GPU tensors: one launch for the suppression (Matrix NMS: four) and one
+    for the vote."""
+    if matrix_nms is not None and soft_nms is not None:
+        raise ValueError('suppress: Soft-NMS and Matrix NMS exclude each other')
     want = vote is not None
     if want:
         vote = _vote_option(vote)
@@ -922,6 +1008,12 @@ def suppress(all_scores, all_boxes, all_classes, nms=0.5, ndetections=100, soft_
             out = _C.soft_nms(all_scores, all_boxes, all_classes, nms, ndetections, SOFT_NMS_METHODS[method], sigma, min_score, want)
         else:
             out = _soft_nms_cpu(all_scores, all_boxes, all_classes, nms, ndetections, method, sigma, min_score)
+    elif matrix_nms is not None:
+        method, sigma, min_score, pre_top = _matrix_nms_dict(matrix_nms, threshold)
+        if cuda:
+            out = _C.matrix_nms(all_scores, all_boxes, all_classes, ndetections, pre_top, MATRIX_NMS_METHODS[method], sigma, min_score, want)
+        else:
+            out = _matrix_nms_cpu(all_scores, all_boxes, all_classes, ndetections, method, sigma, min_score, pre_top)
     elif cuda:
         out = _C.nms(all_scores, all_boxes, all_classes, nms, ndetections, False, want)
     else:
@@ -996,26 +1088,33 @@ def candidates(cls_heads, box_heads, strides, anchors_per_stride, threshold=0.05
 
 
 def detect(cls_heads, box_heads, strides, anchors_per_stride, threshold=0.05, top_n=1000, nms=0.5,
-           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None, soft_nms=None, vote=None):
+           ndetections=100, rotated=False, logits=False, cls_bias=None, box_bias=None, cls_thresholds=None, soft_nms=None, vote=None,
+           matrix_nms=None):
     """sigmoid (logits=True) + decode of all levels + nms: the whole inference post-processing of the
     reference (model.py:140-165) in one enqueue of three launches (rotated: five to seven), reading the head tensors in place.
     cls_bias / box_bias: the heads' last-conv biases, added inside the kernels (see _C.decode_levels); cls_thresholds: the
     prefilter's threshold table for that cls_bias, made once by _C.prefilter_thresholds (optional).
     soft_nms: None, or a dict with `method` ('linear' / 'gaussian'), `sigma` and `min_score` -- the suppression is then Soft-NMS
     (`soft_nms` above) on decode_levels' candidates: three launches as well.
+    matrix_nms: None, or a dict with `method`, `sigma`, `min_score` and `pre_top` -- the suppression is then Matrix NMS
+    (`matrix_nms` above) on decode_levels' candidates: six launches.  Not together with `soft_nms`.
     vote: None, or the IoU threshold of box voting (`box_vote` above) behind the suppression, hard or soft: decode_levels, the
     general NMS with its position output, the vote -- four launches."""
     if soft_nms is not None and rotated:
         raise ValueError('detect: Soft-NMS is not available for rotated boxes')
+    if matrix_nms is not None and rotated:
+        raise ValueError('detect: Matrix NMS is not available for rotated boxes')
+    if matrix_nms is not None and soft_nms is not None:
+        raise ValueError('detect: Soft-NMS and Matrix NMS exclude each other')
     if vote is not None and rotated:
         raise ValueError('detect: box voting is not available for rotated boxes')
     anchors = [anchors_per_stride[s][0] if rotated else anchors_per_stride[s] for s in strides]
     for t in cls_heads:
         _require_gpu(t, 'detect')
     pairs = [_pair(c, b) for c, b in zip(cls_heads, box_heads)]
-    if soft_nms is not None or vote is not None:
+    if soft_nms is not None or vote is not None or matrix_nms is not None:
         return suppress(*_decode_groups(pairs, anchors, strides, threshold, top_n, logits, cls_bias, box_bias, cls_thresholds),
-                        nms, ndetections, soft_nms=soft_nms, vote=vote, threshold=threshold)
+                        nms, ndetections, soft_nms=soft_nms, vote=vote, threshold=threshold, matrix_nms=matrix_nms)
     if len(pairs) > _C.MAX_LEVELS:
         # a model with several backbones has 5 levels per backbone (reference model.py:138): the level table of one call
         # holds MAX_LEVELS, so decode in groups and hand the concatenation to nms (its candidate count is not capped)

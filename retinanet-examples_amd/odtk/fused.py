@@ -664,7 +664,8 @@ class FusedRetinaNet(nn.Module):
         key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last),
                m.threshold, m.top_n, m.nms, m.detections, self.level_streams, self.tower_plan, self.pyramid_canvas, self.seam_fusion, self.tower_conv, bias.data_ptr(), bias._version,
                tuple(sorted(m.soft_nms.items())) if getattr(m, 'soft_nms', None) is not None else None,     # (the suppression rule is baked in as well,
-               getattr(m, 'box_voting', None))                                                               #  and so is box voting)
+               getattr(m, 'box_voting', None),                                                               #  and so is box voting)
+               tuple(sorted(m.matrix_nms.items())) if getattr(m, 'matrix_nms', None) is not None else None)
         if getattr(m, 'tta', None) is not None:
             raise RuntimeError('FusedRetinaNet.replay is not available with Model.tta (two passes of the engine)')
         if getattr(m, 'tile', None) is not None:
@@ -843,4 +844,5 @@ class FusedRetinaNet(nn.Module):
                                       box_bias=box_bias, cls_thresholds=table)
         return box_ops.detect(cls_heads, box_heads, strides, m.anchors, m.threshold, m.top_n, m.nms, m.detections,
                               m.rotated_bbox, logits=True, cls_bias=cls_bias, box_bias=box_bias, cls_thresholds=table,
-                              soft_nms=getattr(m, 'soft_nms', None), vote=getattr(m, 'box_voting', None))
+                              soft_nms=getattr(m, 'soft_nms', None), vote=getattr(m, 'box_voting', None),
+                              matrix_nms=getattr(m, 'matrix_nms', None))

@@ -19,6 +19,9 @@ What differs from the reference, and why:
     from the range, bilinear, on its own canvas, and its boxes with it; with `--device-augment` on the GPU, the same pixels.
   * `--soft-nms {linear,gaussian}` (infer; train: its validation passes) with `--soft-nms-sigma` / `--soft-nms-min-score` is new:
     Soft-NMS (odtk/box.py:soft_nms, one HIP launch) instead of the reference's hard suppression.  Never stored in a checkpoint.
+  * `--matrix-nms {linear,gaussian}` (infer; train: its validation passes) with `--matrix-nms-sigma` / `--matrix-nms-min-score` /
+    `--matrix-nms-pre` is new: Matrix NMS (odtk/box.py:matrix_nms, four HIP launches) instead of the hard suppression; unlike
+    Soft-NMS it takes the merged candidate lists of `--tta flip` and `--tile` at any length.  Never stored in a checkpoint.
   * `--assigner {iou,atss}` (train) with `--atss-topk` is new: ATSS target assignment (odtk/box.py:atss_assign_levels, two HIP
     launches) instead of the reference's fixed `--anchor-ious` rule; axis-aligned boxes only.  Never stored in a checkpoint: a
     resumed run has to be given the flag again.
@@ -92,6 +95,14 @@ _COMMON = [_flag('--with-apex', bool, text=_DROPPED), _flag('--with-dali', bool,
            _flag('--soft-nms-sigma', float, argparse.SUPPRESS, 'width of the gaussian decay (default 0.5)', metavar='value'),
            _flag('--soft-nms-min-score', float, argparse.SUPPRESS, 'decayed scores below this are dropped (default: the '
                  "model's score threshold)", metavar='value'),
+           _flag('--matrix-nms', str, argparse.SUPPRESS, 'Matrix NMS instead of hard suppression: every score is decayed by one '
+                 'factor from the pairwise IoUs of the best candidates; takes candidate lists of any length (train: in the validation '
+                 'passes; not with --soft-nms or --rotated-bbox)', choices=['linear', 'gaussian']),
+           _flag('--matrix-nms-sigma', float, argparse.SUPPRESS, 'width of the gaussian decay (default 0.5)', metavar='value'),
+           _flag('--matrix-nms-min-score', float, argparse.SUPPRESS, 'decayed scores below this are dropped (default: the '
+                 "model's score threshold)", metavar='value'),
+           _flag('--matrix-nms-pre', int, argparse.SUPPRESS, 'candidates per image that take part, the best by score, in 1..4096 '
+                 '(default 2000)', metavar='count'),
            _flag('--box-voting', float, argparse.SUPPRESS, 'box voting behind the suppression: every kept box becomes the score-weighted '
                  'mean of the candidates of its class that overlap it by at least this IoU, in (0, 1] (0.65 is customary; not with '
                  '--rotated-bbox)', metavar='value'),
@@ -206,6 +217,15 @@ def parse(args):
         parser.error('--soft-nms is not available with --rotated-bbox')
     if soft and 'soft_nms' not in soft:
         parser.error('--soft-nms-sigma / --soft-nms-min-score need --soft-nms {linear,gaussian}')
+    matrix = [f for f in ('matrix_nms', 'matrix_nms_sigma', 'matrix_nms_min_score', 'matrix_nms_pre') if hasattr(parsed, f)]
+    if matrix and getattr(parsed, 'rotated_bbox', False):
+        parser.error('--matrix-nms is not available with --rotated-bbox')
+    if matrix and soft:
+        parser.error('--matrix-nms is not available with --soft-nms')
+    if matrix and 'matrix_nms' not in matrix:
+        parser.error('--matrix-nms-sigma / --matrix-nms-min-score / --matrix-nms-pre need --matrix-nms {linear,gaussian}')
+    if hasattr(parsed, 'matrix_nms_pre') and not 1 <= parsed.matrix_nms_pre <= 4096:
+        parser.error('--matrix-nms-pre must be in 1..4096')
     for flag in ('box_voting', 'tta'):
         if hasattr(parsed, flag) and getattr(parsed, 'rotated_bbox', False):
             parser.error('--%s is not available with --rotated-bbox' % flag.replace('_', '-'))
@@ -261,6 +281,14 @@ def soft_nms_options(args, model):
         return None
     return {'method': args.soft_nms, 'sigma': getattr(args, 'soft_nms_sigma', 0.5),
             'min_score': getattr(args, 'soft_nms_min_score', model.threshold)}
+
+
+def matrix_nms_options(args, model):
+    """What `--matrix-nms*` ask for, as `Model.matrix_nms` takes it (None: the flags were not given)."""
+    if not hasattr(args, 'matrix_nms'):
+        return None
+    return {'method': args.matrix_nms, 'sigma': getattr(args, 'matrix_nms_sigma', 0.5),
+            'min_score': getattr(args, 'matrix_nms_min_score', model.threshold), 'pre_top': getattr(args, 'matrix_nms_pre', 2000)}
 
 
 def tile_options(args):
@@ -329,6 +357,9 @@ def worker(rank, args, world, spawned=False):
         model.soft_nms = soft_nms_options(args, model)
         if model.soft_nms is not None and args.rotated_bbox:
             raise RuntimeError('--soft-nms is not available for a model with rotated boxes')
+        model.matrix_nms = matrix_nms_options(args, model)
+        if model.matrix_nms is not None and args.rotated_bbox:
+            raise RuntimeError('--matrix-nms is not available for a model with rotated boxes')
         model.box_voting, model.tta = getattr(args, 'box_voting', None), getattr(args, 'tta', None)
         for flag, value in (('--box-voting', model.box_voting), ('--tta', model.tta)):
             if value is not None and args.rotated_bbox:

@@ -86,6 +86,10 @@ class Model(nn.Module):
         # Soft-NMS instead of the reference's hard rule (odtk/box.py:soft_nms): None, or a dict with `method` ('linear' /
         # 'gaussian'), `sigma` and `min_score` (default: `threshold`).  A run-time option: never written into checkpoints
         self.soft_nms = None
+        # Matrix NMS instead (odtk/box.py:matrix_nms; not together with `soft_nms`): None, or a dict with `method` ('linear' /
+        # 'gaussian', default 'gaussian'), `sigma`, `min_score` (default: `threshold`) and `pre_top` (default 2000).  It takes a
+        # candidate list of any length.  A run-time option as well: never written into checkpoints
+        self.matrix_nms = None
         # two more run-time options of inference, like `soft_nms` never constructor arguments and never written into checkpoints:
         # box voting behind the suppression (odtk/box.py:box_vote) -- None, or its IoU threshold in (0, 1] -- and test-time
         # augmentation -- None, or 'flip': the network also runs on the mirrored batch and one suppression sees both candidate lists
@@ -292,13 +296,20 @@ class Model(nn.Module):
         return self.postprocess(cls_heads, box_heads, strides)
 
     def check_inference_options(self):
-        """The run-time options `soft_nms`, `box_voting`, `tta` and `tile` against the model (axis-aligned boxes only) and their
+        """The run-time options `soft_nms`, `matrix_nms`, `box_voting`, `tta` and `tile` against the model (axis-aligned boxes only) and their
         domains."""
         if self.tta not in (None, 'flip'):
             raise ValueError("Model.tta must be None or 'flip', not {!r}".format(self.tta))
-        for name, value in (('soft_nms', self.soft_nms), ('box_voting', self.box_voting), ('tta', self.tta), ('tile', self.tile)):
+        for name, value in (('soft_nms', self.soft_nms), ('matrix_nms', self.matrix_nms), ('box_voting', self.box_voting), ('tta', self.tta), ('tile', self.tile)):
             if value is not None and self.rotated_bbox:
                 raise ValueError('Model.{} is not available for rotated boxes'.format(name))
+        if self.matrix_nms is not None:
+            if self.soft_nms is not None:
+                raise ValueError('Model.matrix_nms is not available together with Model.soft_nms')
+            if not isinstance(self.matrix_nms, dict):
+                raise ValueError("Model.matrix_nms must be None or a dict with 'method', 'sigma', 'min_score' and 'pre_top', not "
+                                 '{!r}'.format(self.matrix_nms))
+            box_ops._matrix_nms_dict(self.matrix_nms, self.threshold)
         if self.tile is not None:
             if self.tta is not None:
                 raise ValueError('Model.tile is not available together with Model.tta')
@@ -358,7 +369,7 @@ class Model(nn.Module):
                           found[0].new_empty((batch, len(grid) * count), dtype=torch.float32)]
             box_ops.merge_tile_candidates(found, part, batch, len(grid), size, (height, width), border, out=merged)
         return box_ops.suppress(*merged, self.nms, self.detections, soft_nms=self.soft_nms, vote=self.box_voting,
-                                threshold=self.threshold)
+                                threshold=self.threshold, matrix_nms=self.matrix_nms)
 
     def candidates(self, cls_heads, box_heads, strides):
         """Raw head tensors of axis-aligned boxes -> one candidate list (scores [B, L * top_n], boxes [.., 4], classes)."""
@@ -375,7 +386,7 @@ class Model(nn.Module):
                              'top_n'.format(first[0].shape[1] + second[0].shape[1], box_ops.MAX_SOFT_NMS_COUNT))
         merged = box_ops.concat_candidates([first, second], [0, width])
         return box_ops.suppress(*merged, self.nms, self.detections, soft_nms=self.soft_nms, vote=self.box_voting,
-                                threshold=self.threshold)
+                                threshold=self.threshold, matrix_nms=self.matrix_nms)
 
     def postprocess(self, cls_heads, box_heads, strides):
         """Raw head tensors -> (scores [B, D], boxes [B, D, 4|6], classes [B, D])."""
@@ -384,10 +395,11 @@ class Model(nn.Module):
             # sigmoid + decode x5 + nms on the head tensors as the convolutions wrote them
             return box_ops.detect(cls_heads, box_heads, strides, self.anchors, self.threshold, self.top_n,
                                   self.nms, self.detections, self.rotated_bbox, logits=True, soft_nms=self.soft_nms,
-                                  vote=self.box_voting)
-        if self.box_voting is not None:
+                                  vote=self.box_voting, matrix_nms=self.matrix_nms)
+        if self.box_voting is not None or self.matrix_nms is not None:
             return box_ops.suppress(*self.candidates(cls_heads, box_heads, strides), self.nms, self.detections,
-                                    soft_nms=self.soft_nms, vote=self.box_voting, threshold=self.threshold)
+                                    soft_nms=self.soft_nms, vote=self.box_voting, threshold=self.threshold,
+                                    matrix_nms=self.matrix_nms)
         # the reference's sequence, call for call (model.py:140, :153-165); on CPU tensors this is the
         # pure-torch branch of odtk/box.py
         suppress = box_ops.nms_rotated if self.rotated_bbox else box_ops.nms
