@@ -428,6 +428,25 @@ int odtk_canvas_pack(void *canvas, int batch_size, int height, int width, int ch
 int odtk_stem_pack(const void *x, void *out, int batch_size, int height, int width, int in_dtype, int channels_last, int out_dtype,
                    void *stream);
 
+/* Debug / test: the launch shape of the six streaming kernels above (bias_act fast and scalar, bias_act_maxpool, upsample,
+ * canvas, stem_pack).  Every launcher caps its grid (4096, 8192 or 256 * 16 workgroups) and walks the rest with a grid-stride loop;
+ * the caps are reached only by tensors of 70 .. 130 MB, and the max-pool's 64-bit index form only by 2^32 output vectors.
+ *   grid_cap         0 = each launcher's own cap (default); 1 .. 65536 replaces the cap of EVERY one of those grids (odtk_bias_act's
+ *                    fast form still rounds the capped grid UP to a multiple of its unit, so that the grid stride stays a multiple
+ *                    of the row length)
+ *   pool_wide_index  1 = odtk_bias_act_maxpool runs its 64-bit index form whatever the size; 0 = only at 2^32 output vectors (default)
+ * -1 leaves a field as it is; any other value: ODTK_ERR_INVALID, nothing changes.  The results never depend on either field
+ * (tests/test_gpu_engine_streams.py).  Process-wide, one relaxed atomic load per launch; never touches HIP.
+ * odtk_debug_stream_tuning_get: out[0] = grid_cap, out[1] = pool_wide_index. */
+int odtk_debug_stream_tuning(int grid_cap, int pool_wide_index);
+int odtk_debug_stream_tuning_get(int out[2]);
+/* What odtk_bias_act would launch for [n_pixels, channels] of `dtype` under the current odtk_debug_stream_tuning -- answered by the
+ * host function the launcher itself calls.  out[0] = form (0 scalar kernel, 1 fast 16-byte-vector kernel), out[1] = workgroups (of
+ * 256 lanes), out[2] = grid stride = out[1] * 256, in vectors (fast) or elements (scalar), out[3] = passes of lane 0 of workgroup 0
+ * through the fast form's unrolled loop (4 vectors, one stride apart, per pass; 0 for the scalar form).  ODTK_ERR_INVALID: out
+ * null, n_pixels == 0 or channels < 1; ODTK_ERR_UNSUPPORTED: another dtype.  Never touches HIP. */
+int odtk_debug_bias_act_grid(size_t n_pixels, int channels, int dtype, unsigned out[4]);
+
 /*
  * odtk_preprocess_images -- the network's input from decoded source images, one launch for the whole batch: bilinear resize,
  * optional mirror, zero padding to height x width, normalisation, channels_last.  Replaces, on the device, what the reference's

@@ -11,30 +11,63 @@
 
 namespace {
 
-template <typename T, bool kRes, bool kRelu>
-int bias_act_launch(void *y, const float *bias, const void *res, uint64_t n, uint32_t channels, hipStream_t stream) {
-  constexpr int per = T::kPerLoad;
-  uint64_t done = 0;
+// odtk_debug_stream_tuning: both fields in ONE word (a launch reads it once, relaxed): bits 0..16 = grid_cap (0: each launcher's own
+// cap), bit 20 = pool_wide_index.
+constexpr int kStreamCapMax = 65536, kStreamWideBit = 1 << 20;
+std::atomic<int> g_stream_tuning{0};
+
+inline int stream_tuning() { return g_stream_tuning.load(std::memory_order_relaxed); }
+
+// The grid of a streaming kernel: `blocks` workgroups of work, at most the launcher's `own_cap` -- or the debug cap in its place.
+inline uint64_t stream_grid(uint64_t blocks, uint64_t own_cap, int tuning) {
+  const uint64_t cap = (tuning & (kStreamWideBit - 1)) ? static_cast<uint64_t>(tuning & (kStreamWideBit - 1)) : own_cap;
+  return blocks > cap ? cap : blocks;
+}
+
+// What bias_act_launch does with n elements of rows of `channels`, `per` to a 16-byte vector: the ONE place that decides it (the
+// launcher and odtk_debug_bias_act_grid both ask here).
+struct BiasActPlan {
+  bool fast;         // bias_act_kernel (16-byte vectors), else bias_act_scalar_kernel over all n elements
+  uint32_t blocks;   // workgroups of 256 lanes
+  uint32_t vpr;      // fast: vectors per row
+  uint64_t n_vec;    // fast: vectors in all
+  uint64_t stride;   // blocks * 256: the grid stride, in vectors (fast) or elements (scalar)
+  uint64_t trips;    // fast: passes of lane 0 of workgroup 0 through the unrolled loop (4 vectors, `stride` apart, per pass)
+};
+
+BiasActPlan bias_act_plan(uint64_t n, uint32_t channels, int per_, int tuning) {
+  const uint32_t per = static_cast<uint32_t>(per_);
+  BiasActPlan p{};
   if (channels % per == 0 && n / per >= 256) {
     // fast form: grid stride (blocks * 256 lanes) must be a multiple of the row length in vectors
-    const uint32_t vpr = channels / per;
-    const uint64_t n_vec = n / per;                         // n is a multiple of channels, hence of per
-    uint32_t g = vpr, m = 256;                              // unit = vpr / gcd(vpr, 256) blocks
+    p.fast = true;
+    p.vpr = channels / per;
+    p.n_vec = n / per;                                      // n is a multiple of channels, hence of per: no scalar tail
+    uint32_t g = p.vpr, m = 256;                            // unit = vpr / gcd(vpr, 256) blocks
     while (m) { const uint32_t r_ = g % m; g = m; m = r_; }
-    const uint32_t unit = vpr / g;
-    uint64_t blocks = (n_vec + 256ull * 4 - 1) / (256ull * 4);          // ~4 vectors per lane
-    if (blocks > 256 * 16) blocks = 256 * 16;                            // <= 16 workgroups per CU
-    blocks = (blocks + unit - 1) / unit * unit;
-    timed_launch(ODTK_KERNEL_EPILOGUE, odtk::bias_act_kernel<T, kRes, kRelu>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                 stream, y, bias, res, n_vec, vpr);
-    done = n_vec * per;
+    const uint32_t unit = p.vpr / g;
+    uint64_t blocks = stream_grid((p.n_vec + 256ull * 4 - 1) / (256ull * 4), 256 * 16, tuning);   // ~4 vectors per lane, <= 16 workgroups per CU
+    blocks = (blocks + unit - 1) / unit * unit;             // after the cap: the stride stays a multiple of the row
+    p.blocks = static_cast<uint32_t>(blocks);
+    p.stride = blocks * 256;
+    constexpr uint64_t kUnroll = 4;                          // bias_act_kernel's
+    p.trips = p.n_vec > (kUnroll - 1) * p.stride ? (p.n_vec - (kUnroll - 1) * p.stride + kUnroll * p.stride - 1) / (kUnroll * p.stride) : 0;
+  } else {
+    p.blocks = static_cast<uint32_t>(stream_grid((n + 255) / 256, 4096, tuning));
+    p.stride = static_cast<uint64_t>(p.blocks) * 256;
   }
-  if (done < n) {
-    uint64_t blocks = (n - done + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((odtk::bias_act_scalar_kernel<T, kRes, kRelu>), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                       0, stream, y, bias, res, done, n, channels);
-  }
+  return p;
+}
+
+template <typename T, bool kRes, bool kRelu>
+int bias_act_launch(void *y, const float *bias, const void *res, uint64_t n, uint32_t channels, hipStream_t stream) {
+  const BiasActPlan p = bias_act_plan(n, channels, T::kPerLoad, stream_tuning());
+  if (p.fast)
+    timed_launch(ODTK_KERNEL_EPILOGUE, odtk::bias_act_kernel<T, kRes, kRelu>, dim3(p.blocks), dim3(256), 0, stream, y, bias, res, p.n_vec,
+                 p.vpr);
+  else
+    hipLaunchKernelGGL((odtk::bias_act_scalar_kernel<T, kRes, kRelu>), dim3(p.blocks), dim3(256), 0, stream, y, bias, res,
+                       static_cast<uint64_t>(0), n, channels);
   ODTK_HIP_TRY(hipGetLastError());
   return ODTK_OK;
 }
@@ -53,8 +86,7 @@ int bias_act_dispatch(void *y, const float *bias, const void *res, uint64_t n, u
 template <typename TIn>
 int stem_pack_launch(const void *x, void *out, int batch, int height, int width, int channels_last, int out_dtype, hipStream_t stream) {
   const unsigned long long total = 1ull * batch * (height / 2) * (width / 2);
-  unsigned long long blocks = (total + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
+  const unsigned long long blocks = stream_grid((total + 255) / 256, 256 * 32, stream_tuning());
   const odtk::FastDiv by_wo = odtk::fastdiv_make(static_cast<uint32_t>(width / 2));
   const odtk::FastDiv by_howo = odtk::fastdiv_make(static_cast<uint32_t>(height / 2) * static_cast<uint32_t>(width / 2));
   if (out_dtype == ODTK_BF16)
@@ -124,6 +156,35 @@ int odtk_debug_tower_conv_variant(int variant) {
   return variant < 0 ? g_tower_variant.load() : g_tower_variant.exchange(variant);
 }
 
+int odtk_debug_stream_tuning(int grid_cap, int pool_wide_index) {
+  if (grid_cap < -1 || grid_cap > kStreamCapMax || pool_wide_index < -1 || pool_wide_index > 1) return ODTK_ERR_INVALID;
+  int was = g_stream_tuning.load(std::memory_order_relaxed), now;
+  do {
+    now = (grid_cap < 0 ? was & (kStreamWideBit - 1) : grid_cap) | (pool_wide_index < 0 ? was & kStreamWideBit : pool_wide_index ? kStreamWideBit : 0);
+  } while (!g_stream_tuning.compare_exchange_weak(was, now, std::memory_order_relaxed));
+  return ODTK_OK;
+}
+
+int odtk_debug_stream_tuning_get(int out[2]) {
+  if (!out) return ODTK_ERR_INVALID;
+  const int tuning = stream_tuning();
+  out[0] = tuning & (kStreamWideBit - 1);
+  out[1] = (tuning & kStreamWideBit) != 0;
+  return ODTK_OK;
+}
+
+int odtk_debug_bias_act_grid(size_t n_pixels, int channels, int dtype, unsigned out[4]) {
+  if (!out || n_pixels == 0 || channels <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  const BiasActPlan p = bias_act_plan(static_cast<uint64_t>(n_pixels) * channels, static_cast<uint32_t>(channels),
+                                      dtype == ODTK_F32 ? odtk::F32::kPerLoad : odtk::BF16::kPerLoad, stream_tuning());
+  out[0] = p.fast ? 1u : 0u;
+  out[1] = p.blocks;
+  out[2] = static_cast<unsigned>(p.stride);
+  out[3] = p.trips > 0xffffffffull ? 0xffffffffu : static_cast<unsigned>(p.trips);
+  return ODTK_OK;
+}
+
 int odtk_tower_conv3x3(void *y, const void *x, const void *w, const void *bias, int batch_size, int height, int width, int c_in, int c_out,
                        int dtype, int relu, void *stream) {
   if (!y || !x || !w || !bias || batch_size <= 0 || height <= 0 || width <= 0 || c_in <= 0 || c_out <= 0) return ODTK_ERR_INVALID;
@@ -184,8 +245,8 @@ int odtk_bias_act_maxpool(const void *y, const float *bias, void *out, int batch
   if (1ull * height * width * channels >= (1ull << 32)) return ODTK_ERR_UNSUPPORTED;   // 32-bit offsets inside one image
   const uint32_t ho = (static_cast<uint32_t>(height) + 1) / 2, wo = (static_cast<uint32_t>(width) + 1) / 2;
   const uint64_t work = static_cast<uint64_t>(batch_size) * ho * wo * (channels / 8);
-  uint64_t blocks = (work + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;                              // grid-stride beyond 32 workgroups per CU
+  const int tuning = stream_tuning();
+  const uint64_t blocks = stream_grid((work + 255) / 256, 256 * 32, tuning);   // grid-stride beyond 32 workgroups per CU
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t *in = static_cast<const uint16_t *>(y);
   uint16_t *o = static_cast<uint16_t *>(out);
@@ -193,7 +254,7 @@ int odtk_bias_act_maxpool(const void *y, const float *bias, void *out, int batch
   dv.groups = odtk::fastdiv_make(static_cast<uint32_t>(channels / 8));
   dv.wo = odtk::fastdiv_make(wo);
   dv.ho = odtk::fastdiv_make(ho);
-  const bool small = work < (1ull << 32);
+  const bool small = work < (1ull << 32) && !(tuning & kStreamWideBit);   // else 64-bit index arithmetic (k32 = false)
 #define ODTK_POOL_(T, R, S)                                                                                             \
   timed_launch(ODTK_KERNEL_POOL, odtk::bias_act_maxpool_kernel<T, R, S>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, in, \
                bias, o, static_cast<uint32_t>(batch_size), static_cast<uint32_t>(height),                             \
@@ -217,8 +278,7 @@ int odtk_upsample_nearest2x(const void *x, void *out, int batch_size, int height
   const unsigned long long groups = row_bytes / 16;
   const unsigned long long total = 4ull * batch_size * height * width * groups;
   if (total > 0xf0000000ull) return ODTK_ERR_INVALID;
-  unsigned long long blocks = (total + 256ull * 4 - 1) / (256ull * 4);           // ~4 vectors per lane
-  if (blocks > 256 * 16) blocks = 256 * 16;
+  const unsigned long long blocks = stream_grid((total + 256ull * 4 - 1) / (256ull * 4), 256 * 16, stream_tuning());   // ~4 vectors per lane
   timed_launch(ODTK_KERNEL_UPSAMPLE, odtk::upsample_nearest2x_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
                static_cast<hipStream_t>(stream), static_cast<const odtk::vuint4 *>(x), static_cast<odtk::vuint4 *>(out),
                static_cast<uint32_t>(height), static_cast<uint32_t>(width), static_cast<uint32_t>(groups), static_cast<uint32_t>(total),
@@ -248,8 +308,7 @@ int odtk_canvas_pack(void *canvas, int batch_size, int height, int width, int ch
     a.h[l] = static_cast<uint32_t>(h); a.w[l] = static_cast<uint32_t>(w);
     a.src[l] = sources ? static_cast<const odtk::vuint4 *>(sources[l]) : nullptr;
   }
-  unsigned long long blocks = (total + 256ull * 4 - 1) / (256ull * 4);           // ~4 vectors per lane
-  if (blocks > 256 * 16) blocks = 256 * 16;
+  const unsigned long long blocks = stream_grid((total + 256ull * 4 - 1) / (256ull * 4), 256 * 16, stream_tuning());   // ~4 vectors per lane
   hipLaunchKernelGGL(odtk::canvas_fill_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<odtk::vuint4 *>(canvas), a, static_cast<uint32_t>(groups), static_cast<uint32_t>(total),
                      odtk::fastdiv_make(static_cast<uint32_t>(groups)), odtk::fastdiv_make(static_cast<uint32_t>(width)),

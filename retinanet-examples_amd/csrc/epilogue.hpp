@@ -22,10 +22,23 @@
 
 namespace odtk {
 
+// The rounding of an ARITHMETIC result (a sum is never a signalling NaN: its quiet bit survives the shift).
 template <typename T>
 __device__ __forceinline__ uint32_t float_to_storage(float f) {
   if constexpr (std::is_same_v<T, BF16>) return __float_as_uint(round_to_bf16(f)) >> 16;
   else return static_cast<uint32_t>(__builtin_bit_cast(uint16_t, static_cast<_Float16>(f)));
+}
+
+// The cast of a value NO arithmetic has touched (stem_pack hands input pixels through).  round_to_bf16 returns a NaN unchanged, and
+// one whose payload lies in the low 16 mantissa bits only (0x7f800001, 0xff80ffff) would be shifted down to +-inf: a NaN keeps its
+// sign and gets the quiet bit, as torch's cast does.  Only here: the extra select is visible in the instruction-bound pool kernel.
+template <typename T>
+__device__ __forceinline__ uint32_t cast_to_storage(float f) {
+  if constexpr (std::is_same_v<T, BF16>) {
+    const uint32_t b = __float_as_uint(f);
+    const uint32_t r = b + 0x7fffu + ((b >> 16) & 1u);                     // round_to_bf16's rounding
+    return ((b & 0x7fffffffu) > 0x7f800000u ? b | 0x00400000u : r) >> 16;
+  } else return float_to_storage<T>(f);
 }
 
 template <typename T, bool kResidual, bool kRelu>
@@ -323,9 +336,9 @@ __global__ __launch_bounds__(256) void stem_pack_kernel(const void *x, void *out
     }
     vuint4 o0, o1;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o0[e] = float_to_storage<TOut>(v[2 * e]) | (float_to_storage<TOut>(v[2 * e + 1]) << 16);
-    o1[0] = float_to_storage<TOut>(v[8]) | (float_to_storage<TOut>(v[9]) << 16);
-    o1[1] = float_to_storage<TOut>(v[10]) | (float_to_storage<TOut>(v[11]) << 16);
+    for (int e = 0; e < 4; ++e) o0[e] = cast_to_storage<TOut>(v[2 * e]) | (cast_to_storage<TOut>(v[2 * e + 1]) << 16);
+    o1[0] = cast_to_storage<TOut>(v[8]) | (cast_to_storage<TOut>(v[9]) << 16);
+    o1[1] = cast_to_storage<TOut>(v[10]) | (cast_to_storage<TOut>(v[11]) << 16);
     o1[2] = 0u;
     o1[3] = 0u;
     vuint4 *dst = reinterpret_cast<vuint4 *>(static_cast<uint16_t *>(out) + i * 16);

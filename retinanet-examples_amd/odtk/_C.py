@@ -178,6 +178,9 @@ _SIGNATURES = {
                                         ctypes.c_void_p]),
     'odtk_stem_pack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'odtk_debug_stream_tuning': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    'odtk_debug_stream_tuning_get': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
+    'odtk_debug_bias_act_grid': (ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint)]),
     'odtk_preprocess_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), _vp, _sz, _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, _vp]),
     'odtk_augment_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), ctypes.POINTER(Augment), _vp, _sz, _vp, _sz, _vp, _vp,
@@ -1120,7 +1123,10 @@ def _bias_vector(bias, c):
 
 def bias_act_(y, bias, residual=None, relu=True):
     """In place on a channels_last activation: y = act(y + bias[c] (+ residual)).  `bias` is a float32
-    device vector [C].  Replaces the separate bias / frozen-BN / residual-add / ReLU passes."""
+    device vector [C].  Replaces the separate bias / frozen-BN / residual-add / ReLU passes.
+    The sums are float32, rounded once (to nearest even) to y's dtype.  The ReLU is `o > 0 ? o : (isnan(o) ? o : +0.0)`: a NaN goes
+    through, and a sum of -0.0 becomes +0.0 -- torch.relu keeps the -0.0, so the two differ in that one sign bit
+    (tests/engine_streams_ref.py restates the kernel's rule)."""
     if not y.is_cuda or y.dim() != 4 or y.dtype not in _DTYPES:
         raise RuntimeError('bias_act_: y must be a 4-d CUDA tensor of float32/bfloat16/float16')
     n, c, h, w = y.shape
@@ -1226,6 +1232,31 @@ def stem_pack(x, dtype):
     out = torch.empty((n, 16, h // 2, w // 2), dtype=dtype, device=x.device, memory_format=torch.channels_last)
     _launch(library().odtk_stem_pack, 'stem_pack', x.device, x.data_ptr(), out.data_ptr(), n, h, w, _DTYPES[x.dtype], cl, _DTYPES[dtype])
     return out
+
+
+STREAM_TUNING_FIELDS = ('grid_cap', 'pool_wide_index')
+
+
+def stream_tuning(grid_cap=-1, pool_wide_index=-1):
+    """Debug / test: the launch shape of the engine's streaming kernels (include/odtk_hip.h: odtk_debug_stream_tuning).  grid_cap
+    0 = every launcher's own grid cap, 1 .. 65536 replaces them all; pool_wide_index 1 = bias_act_maxpool with 64-bit index
+    arithmetic; -1 leaves a field alone.  Process-wide; never touches the GPU."""
+    _check(library().odtk_debug_stream_tuning(int(grid_cap), int(pool_wide_index)), 'stream_tuning')
+
+
+def stream_tuning_state():
+    """What stream_tuning holds, as a dict over STREAM_TUNING_FIELDS; stream_tuning(**state) puts it back."""
+    out = (ctypes.c_int * 2)()
+    _check(library().odtk_debug_stream_tuning_get(out), 'stream_tuning_state')
+    return dict(zip(STREAM_TUNING_FIELDS, (int(v) for v in out)))
+
+
+def bias_act_grid(n_pixels, channels, dtype):
+    """What bias_act_ launches for [n_pixels, channels] of the torch `dtype` under the current stream_tuning -> dict(form =
+    'scalar' / 'fast', blocks, stride, trips) (include/odtk_hip.h: odtk_debug_bias_act_grid).  Never touches the GPU."""
+    out = (ctypes.c_uint * 4)()
+    _check(library().odtk_debug_bias_act_grid(int(n_pixels), int(channels), _DTYPES[dtype], out), 'bias_act_grid')
+    return {'form': ('scalar', 'fast')[out[0]], 'blocks': int(out[1]), 'stride': int(out[2]), 'trips': int(out[3])}
 
 
 def _image_args(what, src, images, tables, table, height, width):
