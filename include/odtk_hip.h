@@ -67,8 +67,8 @@ extern "C" {
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
  * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t,
- * 9 odtk_candidates_t, 11 odtk_tile_t; -1 for any other value (4, 8 and 10 stay unassigned: tests/test_abi_host.py,
- * tests/test_free_rotate.py and tests/test_box_vote.py probe them as unknown ids).  A binding compiled (or
+ * 9 odtk_candidates_t, 11 odtk_tile_t, 14 odtk_mosaic_tile_t, 15 odtk_mosaic_t; -1 for any other value (4, 8, 10, 12 and 13 stay
+ * unassigned: tests/test_abi_host.py, tests/test_free_rotate.py, tests/test_box_vote.py and later ones probe them as unknown ids).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -549,6 +549,50 @@ typedef struct odtk_rotation {
 int odtk_augment_images_ex(int batch_size, const odtk_image_t *images, const odtk_augment_t *augments, const odtk_rotation_t *rotations,
                            const void *src, size_t src_bytes, const int32_t *tables, size_t tables_len, const void *norm_table, void *out,
                            int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * odtk_mosaic_images -- mosaic augmentation: every output image is a canvas on which up to four resized source images are pasted,
+ * each cropped to its rectangle, on a fill colour; then the colour chain, the table and the pad of odtk_augment_images.
+ * Bit-identical to Pillow on the host (`Image.new`, `resize`, `transpose`, `crop`, `paste`; odtk/data.py: mosaic_pixels).  No
+ * reference equivalent.
+ *   images      HOST odtk_image_t[n_images]: the SOURCES, resized as odtk_preprocess_images resizes them; `mirror` is allowed here.
+ *               resized_s = the resized bytes of source s with its mirror applied, out_width x out_height.
+ *   max_pixels  the largest out_width * out_height over `images`, stated by the caller (the workspace query reads no descriptor);
+ *               checked against the descriptors in the real call: no source may have more.
+ *   mosaics     HOST odtk_mosaic_t[batch_size], one per OUTPUT image.  Canvas pixel (x, y), x < canvas_width, y < canvas_height, of
+ *               output image b is resized_s[y - dst_y + src_y][x - dst_x + src_x] for the highest-numbered used tile (source = s >= 0)
+ *               whose destination rectangle [dst_x, dst_x + width) x [dst_y, dst_y + height) holds (x, y), and `fill` where none does.
+ *   augments    HOST odtk_augment_t[batch_size] or NULL (no colours).  Only the colour operations are read: canvas_width and
+ *               canvas_height must equal the mosaic's and the map must be the identity {65536, 0, 0, 0, 65536, 0}.
+ *   -> the colour chain of odtk_augment_images on the canvas bytes (fill pixels are image pixels: they count in the contrast's grey
+ *      level and go through the table), out[b][y][x][c] = norm_table[c][byte], +0.0 outside the canvas.  Every element is written.
+ * An output image with one tile that covers its canvas from src (0, 0) comes out exactly as odtk_augment_images writes that source
+ * alone (the flip in the map there, in `mirror` here).
+ *   workspace   DEVICE scratch, 16-byte aligned.  Two-phase: workspace == NULL returns the bytes needed, a function of (batch_size,
+ *               n_images, max_pixels, height, width) alone: one 64-bit sum per output image (as many words as there are output images
+ *               or sources, whichever are more: the resize zeroes one word per source), one slot of 3 * max_pixels bytes per
+ *               source, one slot of 3 * height * width bytes per output image for its finished canvas.
+ * A chain of launches on `stream`, no synchronisation: resize of the sources to bytes (64 per launch), the composition (16 output
+ * images per launch), the sum of L (only if some image has contrast on), colours + table + pad through the identity map.
+ * Everything is checked on the host before anything touches HIP: null pointers and non-positive sizes, `source` outside
+ * -1 .. n_images - 1, a used tile without pixels or with a rectangle outside the canvas or with src + size outside its source's
+ * resized image, non-zero pad_, a canvas larger than height x width, everything odtk_preprocess_images checks for the sources, a
+ * workspace that is too small or not 16-byte aligned: ODTK_ERR_INVALID; a bad dtype: ODTK_ERR_UNSUPPORTED.
+ */
+typedef struct odtk_mosaic_tile {
+  int32_t source;                           /* index into images[], -1: tile unused (the other fields are not read) */
+  int32_t dst_x, dst_y, width, height;      /* destination rectangle on the canvas                      */
+  int32_t src_x, src_y;                     /* its top-left corner in the resized source                */
+} odtk_mosaic_tile_t;       /* 28 bytes; odtk_abi_struct_size id 14 */
+typedef struct odtk_mosaic {
+  int32_t canvas_width, canvas_height;      /* <= width, height of the batch                            */
+  odtk_mosaic_tile_t tiles[4];              /* pasted in this order: a later tile covers an earlier one */
+  uint8_t fill[3];                          /* R, G, B where no tile lies                               */
+  uint8_t pad_;                             /* zero                                                     */
+} odtk_mosaic_t;            /* 124 bytes; odtk_abi_struct_size id 15 */
+int odtk_mosaic_images(int batch_size, const odtk_mosaic_t *mosaics, const odtk_augment_t *augments, int n_images,
+                       const odtk_image_t *images, int max_pixels, const void *src, size_t src_bytes, const int32_t *tables,
+                       size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *workspace,
+                       size_t workspace_bytes, void *stream);
 /*
  * odtk_gemm_bias_act -- 1x1 (pointwise) convolution of a channels_last activation as ONE GEMM with
  * the whole epilogue fused:

@@ -1,4 +1,5 @@
-// augment.hpp -- the training augmentations of the input side on the device (odtk_augment_images): quarter turn, flip, brightness,
+// augment.hpp -- the training augmentations of the input side on the device (odtk_augment_images; mosaic.hpp adds pass M, the
+// mosaic composition, as one more producer of the finished canvas that passes B and C read): quarter turn, flip, brightness,
 // contrast, hue and saturation of the RESIZED image, then normalisation by table and zero padding, bit-identical to what the
 // dataset workers do with Pillow on the host (odtk/data.py: __getitem__, restated in numpy there: quarter_turn_map, index_map,
 // blend, contrast_mean, rgb_to_hsv, hsv_to_rgb -- this file follows those line by line).

@@ -43,6 +43,8 @@ int odtk_abi_struct_size(int which) {
     case 7: return static_cast<int>(sizeof(odtk_rotation_t));
     case 9: return static_cast<int>(sizeof(odtk_candidates_t));
     case 11: return static_cast<int>(sizeof(odtk_tile_t));
+    case 14: return static_cast<int>(sizeof(odtk_mosaic_tile_t));
+    case 15: return static_cast<int>(sizeof(odtk_mosaic_t));
     default: return -1;
   }
 }

@@ -1,11 +1,13 @@
-// input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise), odtk_augment_images and
-// odtk_augment_images_ex (the same with a free rotation); odtk_tile_images (the tiler of tiled inference).
+// input.hip -- the input pipeline: odtk_preprocess_images (resize + flip + pad + normalise), odtk_augment_images,
+// odtk_augment_images_ex (the same with a free rotation) and odtk_mosaic_images (four sources composed per canvas, pass M);
+// odtk_tile_images (the tiler of tiled inference).
 #include <cmath>
 #include <cstring>
 
 #include "runtime.hpp"
 #include "preprocess.hpp"
 #include "augment.hpp"
+#include "mosaic.hpp"
 #include "tile.hpp"
 
 extern "C" {
@@ -236,6 +238,167 @@ int odtk_augment_images_ex(int batch_size, const odtk_image_t *images, const odt
                            int height, int width, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
   return augment_images(batch_size, images, augments, rotations, src, src_bytes, tables, tables_len, norm_table, out, height, width, dtype,
                         workspace, workspace_bytes, stream);
+}
+
+// Mosaic: passes A (over the sources), M (mosaic.hpp), B and C (augment.hpp, through the identity map).
+int odtk_mosaic_images(int batch_size, const odtk_mosaic_t *mosaics, const odtk_augment_t *augments, int n_images,
+                       const odtk_image_t *images, int max_pixels, const void *src, size_t src_bytes, const int32_t *tables,
+                       size_t tables_len, const void *norm_table, void *out, int height, int width, int dtype, void *workspace,
+                       size_t workspace_bytes, void *stream) {
+  if (batch_size <= 0 || n_images <= 0 || max_pixels <= 0 || height <= 0 || width <= 0) return ODTK_ERR_INVALID;
+  if (dtype != ODTK_F32 && dtype != ODTK_BF16 && dtype != ODTK_F16) return ODTK_ERR_UNSUPPORTED;
+  if (3ull * height * width >= (1ull << 31) || (height + odtk::kAugRows - 1) / odtk::kAugRows > 65535) return ODTK_ERR_INVALID;
+  if (3ull * max_pixels >= (1ull << 31)) return ODTK_ERR_INVALID;
+  // workspace: one 64-bit word per output image or source, whichever are more (pass A zeroes one per source, pass M the sum of
+  // every output image) | one slot per source for its resized bytes | one slot per output image for its finished canvas bytes
+  const size_t src_slot = align_up(3ull * max_pixels), canvas_slot = align_up(3ull * height * width);
+  const size_t off_bytes = align_up(sizeof(unsigned long long) * (batch_size > n_images ? batch_size : n_images));
+  const unsigned long long need = 1ull * off_bytes + 1ull * src_slot * n_images + 1ull * canvas_slot * batch_size;
+  if (need > 0x7fffffffull) return ODTK_ERR_INVALID;
+  if (!workspace) return static_cast<int>(need);
+  if (!mosaics || !images || !src || !norm_table || !out) return ODTK_ERR_INVALID;
+  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return ODTK_ERR_INVALID;
+  const unsigned es = dtype == ODTK_F32 ? 4u : 2u;
+  if ((reinterpret_cast<uintptr_t>(norm_table) | reinterpret_cast<uintptr_t>(out)) & (es - 1u)) return ODTK_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(tables) & 3u) return ODTK_ERR_INVALID;
+  if (preprocess_images_ok(n_images, images, src_bytes, tables, tables_len, height, width, false) != ODTK_OK) return ODTK_ERR_INVALID;
+  int32_t max_w = 0, max_h = 0;
+  for (int s = 0; s < n_images; ++s) {
+    const odtk_image_t &im = images[s];
+    if (1ull * im.out_width * im.out_height > static_cast<unsigned long long>(max_pixels)) return ODTK_ERR_INVALID;
+    if ((im.out_height + odtk::kPreTileH - 1) / odtk::kPreTileH > 65535) return ODTK_ERR_INVALID;
+    max_w = im.out_width > max_w ? im.out_width : max_w;
+    max_h = im.out_height > max_h ? im.out_height : max_h;
+  }
+  for (int b = 0; b < batch_size; ++b) {
+    const odtk_mosaic_t &mo = mosaics[b];
+    if (mo.canvas_width <= 0 || mo.canvas_height <= 0 || mo.canvas_width > width || mo.canvas_height > height || mo.pad_) return ODTK_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) {
+      const odtk_mosaic_tile_t &t = mo.tiles[k];
+      if (t.source < -1 || t.source >= n_images) return ODTK_ERR_INVALID;
+      if (t.source < 0) continue;
+      if (t.width <= 0 || t.height <= 0 || t.dst_x < 0 || t.dst_y < 0 || t.src_x < 0 || t.src_y < 0) return ODTK_ERR_INVALID;
+      if (1ll * t.dst_x + t.width > mo.canvas_width || 1ll * t.dst_y + t.height > mo.canvas_height) return ODTK_ERR_INVALID;
+      if (1ll * t.src_x + t.width > images[t.source].out_width || 1ll * t.src_y + t.height > images[t.source].out_height) return ODTK_ERR_INVALID;
+    }
+    if (!augments) continue;
+    const odtk_augment_t &au = augments[b];
+    const int32_t identity[6] = {65536, 0, 0, 0, 65536, 0};
+    if (au.canvas_width != mo.canvas_width || au.canvas_height != mo.canvas_height || std::memcmp(au.map, identity, sizeof identity)) return ODTK_ERR_INVALID;
+    if (au.flags & ~(ODTK_AUGMENT_BRIGHTNESS | ODTK_AUGMENT_CONTRAST | ODTK_AUGMENT_HUE | ODTK_AUGMENT_SATURATION)) return ODTK_ERR_INVALID;
+    if (au.pad_[0] | au.pad_[1] | au.pad_[2]) return ODTK_ERR_INVALID;
+    if (((au.flags & ODTK_AUGMENT_BRIGHTNESS) && !std::isfinite(au.brightness)) || ((au.flags & ODTK_AUGMENT_CONTRAST) && !std::isfinite(au.contrast)) ||
+        ((au.flags & ODTK_AUGMENT_SATURATION) && !std::isfinite(au.saturation)))
+      return ODTK_ERR_INVALID;
+  }
+  static_assert(sizeof(odtk::MosArgs) <= 4096, "kernel arguments travel by value");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // A: the sources, 64 per launch
+  odtk::PreArgs pre;
+  pre.src = static_cast<const uint8_t *>(src);
+  pre.tables = tables;
+  pre.norm = nullptr;
+  pre.out = nullptr;
+  pre.height = max_h;
+  pre.width = max_w;
+  pre.vector_rows = 0;
+  pre.bytes = static_cast<uint8_t *>(workspace) + off_bytes;
+  pre.sums = static_cast<unsigned long long *>(workspace);
+  pre.slot = src_slot;
+  for (int first = 0; first < n_images; first += odtk::kPreMaxImages) {
+    const int n = n_images - first < odtk::kPreMaxImages ? n_images - first : odtk::kPreMaxImages;
+    pre.first = first;
+    std::memset(pre.images, 0, sizeof(pre.images));
+    std::memcpy(pre.images, images + first, sizeof(odtk_image_t) * n);
+    const dim3 tiles((max_w + odtk::kPreTileW - 1) / odtk::kPreTileW, (max_h + odtk::kPreTileH - 1) / odtk::kPreTileH, static_cast<unsigned>(n));
+    hipLaunchKernelGGL((odtk::preprocess_images_kernel<4, true>), tiles, dim3(256), 0, s, pre);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  // M: the canvases, 16 per launch
+  odtk::MosArgs mos;
+  mos.bytes = pre.bytes;
+  mos.canvas = pre.bytes + src_slot * n_images;
+  mos.sums = pre.sums;
+  mos.src_slot = src_slot;
+  mos.canvas_slot = canvas_slot;
+  mos.pad_ = 0;
+  for (int first = 0; first < batch_size; first += odtk::kMosMaxImages) {
+    const int n = batch_size - first < odtk::kMosMaxImages ? batch_size - first : odtk::kMosMaxImages;
+    mos.first = first;
+    std::memset(mos.images, 0, sizeof(mos.images));                 // (an all-zero tile is unused: x1 <= x0)
+    unsigned long long pixels = 0;
+    for (int i = 0; i < n; ++i) {
+      const odtk_mosaic_t &mo = mosaics[first + i];
+      odtk::MosImage &d = mos.images[i];
+      d.cw = mo.canvas_width;
+      d.ch = mo.canvas_height;
+      d.fill = static_cast<uint32_t>(mo.fill[0]) | (static_cast<uint32_t>(mo.fill[1]) << 8) | (static_cast<uint32_t>(mo.fill[2]) << 16);
+      for (int k = 0; k < 4; ++k) {
+        const odtk_mosaic_tile_t &t = mo.tiles[k];
+        if (t.source < 0) continue;
+        odtk::MosTile &m = d.tiles[k];
+        m.x0 = t.dst_x;
+        m.y0 = t.dst_y;
+        m.x1 = t.dst_x + t.width;
+        m.y1 = t.dst_y + t.height;
+        m.ox = t.src_x - t.dst_x;
+        m.oy = t.src_y - t.dst_y;
+        m.rw = images[t.source].out_width;
+        m.source = t.source;
+      }
+      const unsigned long long count = 1ull * mo.canvas_width * mo.canvas_height;
+      pixels = count > pixels ? count : pixels;
+    }
+    const unsigned per_group = 256u * odtk::kMosPixels;
+    hipLaunchKernelGGL(odtk::mosaic_compose_kernel, dim3(static_cast<unsigned>((pixels + per_group - 1) / per_group), 1, static_cast<unsigned>(n)),
+                       dim3(256), 0, s, mos);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  // B, C: the finished canvases through the identity map, 64 per launch
+  odtk::AugArgs aug;
+  aug.bytes = mos.canvas;
+  aug.sums = pre.sums;
+  aug.norm = norm_table;
+  aug.out = out;
+  aug.slot = canvas_slot;
+  aug.height = height;
+  aug.width = width;
+  aug.vector_rows = ((3ull * width * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) ? 1 : 0;
+  const unsigned group = 16u * (16u / es);                        // pixels per workgroup row of pass C
+  for (int first = 0; first < batch_size; first += odtk::kPreMaxImages) {
+    const int n = batch_size - first < odtk::kPreMaxImages ? batch_size - first : odtk::kPreMaxImages;
+    aug.first = first;
+    std::memset(aug.images, 0, sizeof(aug.images));
+    bool contrast = false;
+    for (int i = 0; i < n; ++i) {
+      const odtk_mosaic_t &mo = mosaics[first + i];
+      odtk::AugImage &d = aug.images[i];
+      d.cw = d.rw = mo.canvas_width;
+      d.ch = d.rh = mo.canvas_height;
+      d.map[0] = d.map[4] = 65536;
+      d.brightness = d.contrast = d.saturation = 1.0f;
+      if (augments) {
+        const odtk_augment_t &au = augments[first + i];
+        d.flags = au.flags;
+        d.brightness = au.brightness;
+        d.contrast = au.contrast;
+        d.saturation = au.saturation;
+        d.hue = au.hue;
+        contrast = contrast || (au.flags & ODTK_AUGMENT_CONTRAST);
+      }
+    }
+    if (contrast) {
+      hipLaunchKernelGGL(odtk::augment_luma_sum_kernel, dim3(odtk::kAugSumBlocks, 1, static_cast<unsigned>(n)), dim3(256), 0, s, aug);
+      ODTK_HIP_TRY(hipGetLastError());
+    }
+    const dim3 grid((width + group - 1) / group, (height + odtk::kAugRows - 1) / odtk::kAugRows, static_cast<unsigned>(n));
+    if (es == 4)
+      hipLaunchKernelGGL(odtk::augment_images_kernel<4>, grid, dim3(256), 0, s, aug);
+    else
+      hipLaunchKernelGGL(odtk::augment_images_kernel<2>, grid, dim3(256), 0, s, aug);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
 }
 
 // everything is validated here, on the host, before anything touches the device

@@ -98,6 +98,18 @@ class Rotation(ctypes.Structure):
     _fields_ = [('matrix', ctypes.c_double * 6), ('enabled', ctypes.c_int32), ('flip', ctypes.c_int32)]
 
 
+class MosaicTile(ctypes.Structure):
+    """odtk_mosaic_tile_t"""
+    _fields_ = [('source', ctypes.c_int32), ('dst_x', ctypes.c_int32), ('dst_y', ctypes.c_int32), ('width', ctypes.c_int32),
+                ('height', ctypes.c_int32), ('src_x', ctypes.c_int32), ('src_y', ctypes.c_int32)]
+
+
+class Mosaic(ctypes.Structure):
+    """odtk_mosaic_t"""
+    _fields_ = [('canvas_width', ctypes.c_int32), ('canvas_height', ctypes.c_int32), ('tiles', MosaicTile * 4),
+                ('fill', ctypes.c_uint8 * 3), ('pad_', ctypes.c_uint8)]
+
+
 class Candidates(ctypes.Structure):
     """odtk_candidates_t"""
     _fields_ = [('scores', _vp), ('boxes', _vp), ('classes', _vp), ('count', ctypes.c_uint32), ('mirror_width', ctypes.c_int32)]
@@ -187,6 +199,8 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_augment_images_ex': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Image), ctypes.POINTER(Augment), ctypes.POINTER(Rotation), _vp, _sz,
                                               _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
+    'odtk_mosaic_images': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Mosaic), ctypes.POINTER(Augment), ctypes.c_int, ctypes.POINTER(Image),
+                                          ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp]),
     'odtk_nms_sorted_runs': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_uint32, _vp, _sz, _vp]),
     'odtk_soft_nms': (ctypes.c_int, [ctypes.c_int, _vpp, _vpp, ctypes.c_int, _sz, ctypes.c_int, ctypes.c_float, ctypes.c_int,
@@ -248,7 +262,7 @@ def library():
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
         for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation),
-                              (9, Candidates), (11, Tile)):
+                              (9, Candidates), (11, Tile), (14, MosaicTile), (15, Mosaic)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -1259,9 +1273,10 @@ def bias_act_grid(n_pixels, channels, dtype):
     return {'form': ('scalar', 'fast')[out[0]], 'blocks': int(out[1]), 'stride': int(out[2]), 'trips': int(out[3])}
 
 
-def _image_args(what, src, images, tables, table, height, width):
-    """Shared by preprocess_images / augment_images: checks src, tables and table, coerces `images` to a ctypes array and allocates
-    the output -> (images, out, the arguments both entry points take from src on)."""
+def _image_args(what, src, images, tables, table, height, width, batch=None):
+    """Shared by preprocess_images / augment_images / mosaic_images: checks src, tables and table, coerces `images` to a ctypes array
+    and allocates the output (`batch` images; default: as many as `images`) -> (images, out, the arguments the entry points take
+    from src on)."""
     if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
         raise RuntimeError('%s: src must be a contiguous uint8 CUDA tensor' % what)
     if tables.device != src.device or tables.dtype != torch.int32 or not tables.is_contiguous():
@@ -1270,7 +1285,8 @@ def _image_args(what, src, images, tables, table, height, width):
         raise RuntimeError('%s: table must be a contiguous [3, 256] float32/bfloat16/float16 tensor on the device of src' % what)
     if not isinstance(images, ctypes.Array):
         images = (Image * len(images))(*images)
-    out = torch.empty((len(images), 3, height, width), dtype=table.dtype, device=src.device, memory_format=torch.channels_last)
+    out = torch.empty((len(images) if batch is None else batch, 3, height, width), dtype=table.dtype, device=src.device,
+                      memory_format=torch.channels_last)
     return images, out, (src.data_ptr(), src.numel(), tables.data_ptr() if tables.numel() else None, tables.numel(),
                          table.data_ptr(), out.data_ptr(), height, width, _DTYPES[table.dtype])
 
@@ -1307,6 +1323,27 @@ def augment_images(src, images, augments, tables, table, height, width, rotation
     if len(rotations) != len(images):
         raise RuntimeError('augment_images: %d images but %d rotation descriptors' % (len(images), len(rotations)))
     _enqueue(library().odtk_augment_images_ex, 'augment_images', src.device, len(images), images, augments, rotations, *args)
+    return out
+
+
+def mosaic_images(src, images, mosaics, augments, tables, table, height, width):
+    """Mosaic augmentation on the device (include/odtk_hip.h: odtk_mosaic_images): `images` are the SOURCES (resized as
+    `preprocess_images` resizes them, `mirror` allowed), `mosaics` one `Mosaic` per OUTPUT image that pastes up to four of them, each
+    cropped to its rectangle, on a canvas of the fill colour; then the colour operations of `augments` (one `Augment` per output
+    image with the mosaic's canvas and the identity map, or None: no colours), the table and the pad, Pillow-exact.
+    mosaics, augments: ctypes arrays (or sequences), HOST memory; the rest as `preprocess_images`.
+    -> [len(mosaics), 3, height, width] with channels_last strides."""
+    if not isinstance(mosaics, ctypes.Array):
+        mosaics = (Mosaic * len(mosaics))(*mosaics)
+    images, out, args = _image_args('mosaic_images', src, images, tables, table, height, width, batch=len(mosaics))
+    if augments is not None:
+        if not isinstance(augments, ctypes.Array):
+            augments = (Augment * len(augments))(*augments)
+        if len(augments) != len(mosaics):
+            raise RuntimeError('mosaic_images: %d output images but %d augment descriptors' % (len(mosaics), len(augments)))
+    max_pixels = max((im.out_width * im.out_height for im in images), default=0)
+    _enqueue(library().odtk_mosaic_images, 'mosaic_images', src.device, len(mosaics), mosaics, augments, len(images), images, max_pixels,
+             *args)
     return out
 
 

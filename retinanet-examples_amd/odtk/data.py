@@ -26,11 +26,15 @@ run on the device between the resize and the normalisation (`odtk_augment_images
 `augment_free_rotate=(lo, hi)` adds a rotation by a free angle between the quarter turn and the flip: Pillow's bilinear
 `Image.rotate` on the host, or, with `device_augment`, six doubles per image and one more pass on the device
 (`odtk_augment_images_ex`), the same bytes (`free_rotation_matrix`, `rotate_bilinear`).
+`mosaic=p` composes a training item, with probability p, of four images on one canvas of the primary image's size (`CocoDataset`):
+Pillow's `resize`, `crop` and `paste` on the host, or, with `device_augment`, the four source images and one placement record per
+output image and one more pass on the device (`odtk_mosaic_images`), the same bytes (`mosaic_pixels`).
 
 `CocoIndex` is the part of `pycocotools.coco.COCO` (nvidia/cocoapi master, un-pinned and absent from this
 image) that the reference touches: `dataset`, `imgs`, `getCatIds`, `getAnnIds`, `loadAnns`, `loadImgs`,
 `loadRes`.
 """
+import collections
 import functools
 import json
 import math
@@ -425,6 +429,60 @@ def augment_pixels(pixels, aug, rotation=None):
     return pixels
 
 
+# -- mosaic: four images on one canvas ------------------------------------------------------------------------------------------------
+# Tile k = 0..3 (top-left, top-right, bottom-left, bottom-right) is its image resized once, mirrored or not, touching the centre
+# (cx, cy) with one corner and cropped to its quadrant.  `mosaic_placement` and `mosaic_tile_boxes` are shared by the host path and
+# the device path; `mosaic_pixels` is the CPU implementation the device path (include/odtk_hip.h: odtk_mosaic_images) is pinned to.
+
+MOSAIC_FILL = (114, 114, 114)                                       # the canvas where no tile lies
+MOSAIC_MIN_AREA = 0.2                                               # a box stays only with this share of its scaled area left after the clip
+
+
+def mosaic_placement(k, tile_width, tile_height, cx, cy, width, height):
+    """Where tile `k` of `tile_width` x `tile_height` pixels goes on a `width` x `height` canvas with the centre (cx, cy):
+    -> (dst_x, dst_y, dw, dh, src_x, src_y), the dw x dh pixels of the tile from (src_x, src_y) on pasted at (dst_x, dst_y)."""
+    left, top = k in (0, 2), k in (0, 1)
+    dw = min(tile_width, cx if left else width - cx)
+    dh = min(tile_height, cy if top else height - cy)
+    return (cx - dw if left else cx, cy - dh if top else cy, dw, dh, tile_width - dw if left else 0, tile_height - dh if top else 0)
+
+
+def mosaic_tile_boxes(boxes, scale, tile_width, mirror, placement):
+    """The boxes `[N, 4]` (x, y, w, h in source pixels) of one tile on the canvas, in float64: scaled, flipped within the tile if it
+    is mirrored, shifted by dst - src and clipped to the tile's destination rectangle -> (boxes float64 [N, 4], keep bool [N]): a box
+    stays if at least a pixel of its width and of its height and MOSAIC_MIN_AREA of its scaled area are left."""
+    dx, dy, dw, dh, sx, sy = placement
+    x, y, w, h = (boxes[:, k].double() * scale for k in range(4))
+    if mirror:
+        x = tile_width - x - w
+    x, y = x + (dx - sx), y + (dy - sy)
+    left, right = x.clamp(dx, dx + dw), (x + w).clamp(dx, dx + dw)
+    top, bottom = y.clamp(dy, dy + dh), (y + h).clamp(dy, dy + dh)
+    moved = torch.stack([left, top, right - left, bottom - top], 1)
+    keep = (moved[:, 2] >= 1) & (moved[:, 3] >= 1) & (moved[:, 2] * moved[:, 3] >= MOSAIC_MIN_AREA * (w * h))
+    return moved, keep
+
+
+def mosaic_pixels(tiles, record):
+    """`Image.new('RGB', canvas, fill)` and one `canvas.paste(tile.crop(..), dst)` per used tile of one MOSAIC_DTYPE record, without
+    Pillow: `tiles[s]` is the resized (and mirrored) uint8 `[h, w, 3]` image that a tile names as its `source`; tiles are pasted in
+    their order, so a later one covers an earlier one -> the canvas, uint8 `[canvas_height, canvas_width, 3]`."""
+    canvas = np.empty((int(record['canvas_height']), int(record['canvas_width']), 3), dtype=np.uint8)
+    canvas[:] = record['fill']
+    for tile in record['tiles']:
+        if int(tile['source']) < 0:
+            continue
+        dx, dy, w, h, sx, sy = (int(tile[f]) for f in ('dst_x', 'dst_y', 'width', 'height', 'src_x', 'src_y'))
+        canvas[dy:dy + h, dx:dx + w] = np.asarray(tiles[int(tile['source'])])[sy:sy + h, sx:sx + w]
+    return canvas
+
+
+# The geometry of a mosaic item for `SourceBatch.pack`: the canvas, sources = ((out_width, out_height, mirror) per source image of the
+# item), tiles = ((k, index into sources, dst_x, dst_y, width, height, src_x, src_y) per used tile) and the colour operations.  The
+# item's pixels are the list of its source images.
+MosaicGeometry = collections.namedtuple('MosaicGeometry', 'width height sources tiles flags brightness contrast saturation hue')
+
+
 # -- a batch of source images in one buffer -----------------------------------------------------------------------------------------
 AUGMENT_DTYPE = np.dtype([('canvas_width', '<i4'), ('canvas_height', '<i4'), ('map', '<i4', (6,)), ('flags', '<u4'),
                           ('brightness', '<f4'), ('contrast', '<f4'), ('saturation', '<f4'), ('hue', 'u1'), ('pad_', 'u1', (3,))])
@@ -433,7 +491,11 @@ ROTATION_DTYPE = np.dtype([('matrix', '<f8', (6,)), ('enabled', '<i4'), ('flip',
 IMAGE_DTYPE =np.dtype([('src_offset', '<u8'), ('src_width', '<i4'), ('src_height', '<i4'), ('src_pitch', '<i4'),
                         ('out_width', '<i4'), ('out_height', '<i4'), ('mirror', '<i4'), ('x_table', '<i4'), ('y_table', '<i4'),
                         ('x_taps', '<i4'), ('y_taps', '<i4')])      # odtk_image_t (include/odtk_hip.h)
-_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, augments at byte (0: none), rotations at byte (0: none), 0
+MOSAIC_TILE_DTYPE = np.dtype([('source', '<i4'), ('dst_x', '<i4'), ('dst_y', '<i4'), ('width', '<i4'), ('height', '<i4'),
+                              ('src_x', '<i4'), ('src_y', '<i4')])  # odtk_mosaic_tile_t (include/odtk_hip.h)
+MOSAIC_DTYPE = np.dtype([('canvas_width', '<i4'), ('canvas_height', '<i4'), ('tiles', MOSAIC_TILE_DTYPE, (4,)), ('fill', 'u1', (3,)),
+                         ('pad_', 'u1')])                           # odtk_mosaic_t (include/odtk_hip.h)
+_HEADER_WORDS = 8                                                   # int32: batch, height, width, tables at byte, tables length, augments at byte (0: none), rotations at byte (0: none), mosaics at byte (0: none)
 _up16 = lambda n: (n + 15) // 16 * 16
 
 
@@ -452,18 +514,31 @@ class SourceBatch:
     With `augment_free_rotate` the tuples of the rotated images carry two more entries, the matrix of `free_rotation_matrix` and the
     flip, and the buffer one odtk_rotation_t per image after the augment records (the header's seventh word says where; it is 0,
     and the buffer is what it was, when no image of the batch is rotated).  The map of such an image is the quarter turn alone:
-    the free rotation and then the flip follow it on the turned canvas (`odtk_augment_images_ex`)."""
+    the free rotation and then the flip follow it on the turned canvas (`odtk_augment_images_ex`).
+
+    With `mosaic` an item may bring up to four source images (`MosaicGeometry`).  The image descriptors and the pixels are then those
+    of ALL sources of the batch, in item order, the augment records (identity map, the colours) stay one per OUTPUT image, and
+    behind them come 16 bytes (the number of sources, 0, 0, 0) and one odtk_mosaic_t per output image that says which sources go
+    where on its canvas (the header's eighth word says where; it is 0, and the buffer is what it was, when no item is a mosaic).
+    An item of such a batch that is no mosaic becomes a record of one tile (`odtk_mosaic_images`)."""
 
     @staticmethod
     def pack(sources, geometry, stride):
         """sources: uint8 `[h, w, 3]` tensors; geometry: `(out_width, out_height, mirror)` per image, or (device_augment)
         `(out_width, out_height, 0, canvas_width, canvas_height, map, flags, brightness, contrast, saturation, hue)`, or (free
-        rotation) that with `(matrix, flip)` appended."""
+        rotation) that with `(matrix, flip)` appended; or (mosaic) a `MosaicGeometry`, whose entry of `sources` is the list of
+        the item's source images.  From here on `geometry` describes the OUTPUT images and `resized` the source images: one each,
+        the same, unless the batch has a mosaic."""
         up = lambda d: d + (stride - d % stride) % stride
+        mosaics = None
+        if any(isinstance(g, MosaicGeometry) for g in geometry):
+            sources, geometry, resized, mosaics = SourceBatch._mosaic_records(sources, geometry)
         augmented = any(len(g) > 3 for g in geometry)
         if augmented:                                               # plain images of such a batch get the identity map
             geometry = [g if len(g) > 3 else g[:2] + (0,) + quarter_turn_map(g[0], g[1], 0, flip=g[2]) + (0, 1.0, 1.0, 1.0, 0)
                         for g in geometry]
+        if mosaics is None:
+            resized = [g[:3] for g in geometry]
         height = max(up(g[4] if augmented else g[1]) for g in geometry)
         width = max(up(g[3] if augmented else g[0]) for g in geometry)
         tables, where, length = [], {}, 0
@@ -478,36 +553,43 @@ class SourceBatch:
                 length += bounds.size + weights.size
             return where[(in_size, out_size)]
         images = np.zeros(len(sources), dtype=IMAGE_DTYPE)
-        for im, p, (ow, oh, mirror) in zip(images, sources, (g[:3] for g in geometry)):
+        for im, p, (ow, oh, mirror) in zip(images, sources, resized):
             h, w = p.shape[:2]
             im['src_width'], im['src_height'], im['src_pitch'] = w, h, 3 * w
             im['out_width'], im['out_height'], im['mirror'] = ow, oh, int(bool(mirror))
             im['x_table'], im['x_taps'] = table(w, ow)
             im['y_table'], im['y_taps'] = table(h, oh)
-        augments = np.zeros(len(sources) if augmented else 0, dtype=AUGMENT_DTYPE)
+        augments = np.zeros(len(geometry) if augmented else 0, dtype=AUGMENT_DTYPE)
         for aug, g in zip(augments, geometry):
             aug['canvas_width'], aug['canvas_height'], aug['map'], aug['flags'] = g[3], g[4], g[5], g[6]
             aug['brightness'], aug['contrast'], aug['saturation'], aug['hue'] = g[7], g[8], g[9], g[10]
         rotated = any(len(g) > 11 for g in geometry)
-        rotations = np.zeros(len(sources) if rotated else 0, dtype=ROTATION_DTYPE)
+        rotations = np.zeros(len(geometry) if rotated else 0, dtype=ROTATION_DTYPE)
         for rot, g in zip(rotations, geometry):
             if len(g) > 11:
                 rot['matrix'], rot['enabled'], rot['flip'] = g[11], 1, int(bool(g[12]))
         augments_at = _up16(4 * _HEADER_WORDS + images.nbytes) if augmented else 0
         rotations_at = _up16(augments_at + augments.nbytes) if rotated else 0
         tables_at = _up16(max(augments_at, rotations_at, 4 * _HEADER_WORDS + images.nbytes) + (rotations.nbytes if rotated else augments.nbytes))
+        mosaics_at = 0
+        if mosaics is not None:                                     # 16 bytes (the number of source images, 0, 0, 0), then the records
+            mosaics_at = _up16(augments_at + augments.nbytes)
+            tables_at = _up16(mosaics_at + 16 + mosaics.nbytes)
         at = _up16(tables_at + 4 * length)
         for im in images:
             im['src_offset'] = at
             at = _up16(at + int(im['src_pitch']) * int(im['src_height']))
         buffer = _batch_buffer((at,))
         view = buffer.numpy()
-        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(sources), height, width, tables_at, length, augments_at, rotations_at, 0)
+        view[:4 * _HEADER_WORDS].view(np.int32)[:] = (len(geometry), height, width, tables_at, length, augments_at, rotations_at, mosaics_at)
         view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + images.nbytes] = images.view(np.uint8)
         if augmented:
             view[augments_at:augments_at + augments.nbytes] = augments.view(np.uint8)
         if rotated:
             view[rotations_at:rotations_at + rotations.nbytes] = rotations.view(np.uint8)
+        if mosaics is not None:
+            view[mosaics_at:mosaics_at + 16].view(np.int32)[:] = (len(sources), 0, 0, 0)
+            view[mosaics_at + 16:mosaics_at + 16 + mosaics.nbytes] = mosaics.view(np.uint8)
         if tables:
             view[tables_at:tables_at + 4 * length].view(np.int32)[:] = np.concatenate(tables)
         for im, p in zip(images, sources):
@@ -515,13 +597,47 @@ class SourceBatch:
             view[start:start + p.numel()] = p.numpy().reshape(-1)
         return buffer
 
+    @staticmethod
+    def _mosaic_records(sources, geometry):
+        """A batch with a mosaic item -> (the source images of all items in one list, one plain `device_augment` geometry per output
+        image: its canvas, the identity map and its colours, `(out_width, out_height, mirror)` per source image, one MOSAIC_DTYPE
+        record per output image).  An item that is no mosaic becomes a record of one tile that covers its canvas; its flip, which
+        its map held, becomes the source's mirror."""
+        flat, resized, canvases = [], [], []
+        records = np.zeros(len(geometry), dtype=MOSAIC_DTYPE)
+        records['tiles']['source'] = -1
+        records['fill'] = MOSAIC_FILL
+        for record, pixels, g in zip(records, sources, geometry):
+            if isinstance(g, MosaicGeometry):
+                width, height, colour = g.width, g.height, tuple(g[4:])
+                for k, source, *rectangle in g.tiles:
+                    record['tiles'][k] = (len(flat) + source,) + tuple(rectangle)
+                flat.extend(pixels)
+                resized.extend(g.sources)
+            else:
+                if len(g) > 11 or (len(g) > 3 and (tuple(g[3:5]) != tuple(g[:2]) or g[5][1] or g[5][3])):
+                    raise ValueError('SourceBatch.pack: a batch with a mosaic cannot hold a turned or rotated image')
+                width, height = g[:2]
+                colour = (0, 1.0, 1.0, 1.0, 0) if len(g) == 3 else tuple(g[6:11])
+                record['tiles'][0] = (len(flat), 0, 0, width, height, 0, 0)
+                flat.append(pixels)
+                resized.append((width, height, int(bool(g[2] if len(g) == 3 else g[5][0] < 0))))
+            record['canvas_width'], record['canvas_height'] = width, height
+            canvases.append((width, height, 0) + quarter_turn_map(width, height, 0) + colour)
+        return flat, canvases, resized, records
+
     def __init__(self, buffer):
         """buffer: the packed uint8 tensor, in HOST memory (the descriptors are kernel arguments)."""
         self.buffer = buffer
         self.view = buffer.numpy()
         header = self.view[:4 * _HEADER_WORDS].view(np.int32)
-        self.batch, self.height, self.width, self.tables_at, self.tables_len, augments_at, rotations_at = (int(v) for v in header[:7])
-        self.images = self.view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + self.batch * IMAGE_DTYPE.itemsize].view(IMAGE_DTYPE)
+        self.batch, self.height, self.width, self.tables_at, self.tables_len, augments_at, rotations_at, mosaics_at = (int(v) for v in header[:8])
+        self.mosaics = None                                         # one MOSAIC_DTYPE record per output image when one of them is a mosaic
+        n_images = self.batch                                       # source images: one per output image unless there are mosaics
+        if mosaics_at:
+            n_images = int(self.view[mosaics_at:mosaics_at + 4].view(np.int32)[0])
+            self.mosaics = self.view[mosaics_at + 16:mosaics_at + 16 + self.batch * MOSAIC_DTYPE.itemsize].view(MOSAIC_DTYPE)
+        self.images = self.view[4 * _HEADER_WORDS:4 * _HEADER_WORDS + n_images * IMAGE_DTYPE.itemsize].view(IMAGE_DTYPE)
         self.augments = None                                        # one AUGMENT_DTYPE record per image with `device_augment`
         if augments_at:
             self.augments = self.view[augments_at:augments_at + self.batch * AUGMENT_DTYPE.itemsize].view(AUGMENT_DTYPE)
@@ -541,16 +657,24 @@ class SourceBatch:
 
     def apply_cpu(self, table, dtype=torch.float32):
         """-> `[B, 3, H, W]` `dtype`, channels_last storage: what `odtk_preprocess_images` (with augment descriptors:
-        `odtk_augment_images`, with rotation records `odtk_augment_images_ex`) writes, computed on the host."""
+        `odtk_augment_images`, with rotation records `odtk_augment_images_ex`, with mosaic records `odtk_mosaic_images`) writes,
+        computed on the host."""
         table = table.to(device='cpu', dtype=dtype).reshape(-1)
         out = torch.zeros((self.batch, self.height, self.width, 3), dtype=dtype)
         channel = torch.tensor([0, 256, 512])
+        resized = []
         for k, im in enumerate(self.images):
             pixels = resize_bilinear(self.source(k), (int(im['out_width']), int(im['out_height'])))
             if im['mirror']:
                 pixels = pixels[:, ::-1].copy()
+            if self.mosaics is not None:                            # the sources first, then the canvases below
+                resized.append(pixels)
+                continue
             if self.augments is not None:
                 pixels = augment_pixels(pixels, self.augments[k], None if self.rotations is None else self.rotations[k])
+            out[k, :pixels.shape[0], :pixels.shape[1]] = table[torch.from_numpy(pixels).long() + channel]
+        for k, record in enumerate(self.mosaics if self.mosaics is not None else ()):
+            pixels = augment_pixels(mosaic_pixels(resized, record), self.augments[k])
             out[k, :pixels.shape[0], :pixels.shape[1]] = table[torch.from_numpy(pixels).long() + channel]
         return out.permute(0, 3, 1, 2)
 
@@ -579,6 +703,14 @@ class CocoDataset(data.dataset.Dataset):
     uniformly from the range, between the quarter turn and the flip (`Image.rotate(angle, resample=Image.BILINEAR)`; the corners it
     leaves empty are black image pixels) and its boxes move with it (`_rotate_boxes`).  (0, 0), the default, is off: no draw is taken.
 
+    `mosaic=p`, `mosaic_scale=(lo, hi)`: with probability p (drawn behind the jitter draw; 0, the default, takes no draw) a training
+    item is a mosaic (`_mosaic_plan`): a canvas of the primary image's resized size, grey (114), on which four images -- the primary
+    and three drawn from the whole set -- each resized ONCE by its own ratio times g (g uniform in the scale range) and mirrored
+    or not, touch a centre drawn in the middle half of the canvas with one corner and are cropped to their quadrant.  Boxes are
+    clipped to their tile and stay with a pixel of width and height and MOSAIC_MIN_AREA of their area left; the colours follow on
+    the canvas.  An item that is not a mosaic continues as without the option.  It refuses the quarter turns, the free rotation,
+    rotated boxes and `device_resize` alone.
+
     `device_resize=True`: items are source pixels and the target geometry (`_source_item`); it refuses the quarter turns and the
     colour options and the free rotation.  `device_augment=True`: the same hand-over, and those travel as descriptors
     (`_augment_item`)."""
@@ -587,8 +719,19 @@ class CocoDataset(data.dataset.Dataset):
 
     def __init__(self, path, resize, max_size, stride, annotations=None, training=False, rotate_augment=False,
                  augment_brightness=0.0, augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, device_resize=False,
-                 device_augment=False, augment_free_rotate=(0, 0)):
+                 device_augment=False, augment_free_rotate=(0, 0), mosaic=0.0, mosaic_scale=(0.5, 1.0)):
         super().__init__()
+        mosaic, mosaic_scale = float(mosaic), tuple(float(v) for v in mosaic_scale)
+        if not 0.0 <= mosaic <= 1.0:
+            raise ValueError('mosaic must be a probability in [0, 1], got %r' % (mosaic,))
+        if len(mosaic_scale) != 2 or not 0.0 < mosaic_scale[0] <= mosaic_scale[1] <= 1.0:
+            raise ValueError('mosaic_scale must be a range (lo, hi) with 0 < lo <= hi <= 1, got %r' % (mosaic_scale,))
+        if mosaic:
+            for name, value in (('rotate_augment', rotate_augment), ('augment_free_rotate', any(float(v) for v in augment_free_rotate)),
+                                ('rotated boxes', self.box_fields != 4), ('device_resize without device_augment', device_resize and not device_augment)):
+                if value:
+                    raise ValueError('mosaic cannot be combined with %s' % name)
+        self.mosaic, self.mosaic_scale = mosaic, mosaic_scale                                      # 0: off, no draw
         augment_free_rotate = tuple(float(v) for v in augment_free_rotate)
         if len(augment_free_rotate) != 2 or not all(math.isfinite(v) for v in augment_free_rotate) or augment_free_rotate[0] > augment_free_rotate[1]:
             raise ValueError('augment_free_rotate must be a finite range (lo, hi) in degrees with lo <= hi, got %r' % (augment_free_rotate,))
@@ -724,6 +867,9 @@ class CocoDataset(data.dataset.Dataset):
         `augment_free_rotate` the angle is drawn between the turn and the flip, the map holds the turn alone, and the tuple ends in
         `(free_rotation_matrix of the turned canvas, flip)`."""
         im, ratio, size = self._open(image_id)
+        if self.mosaic and random.random() < self.mosaic:
+            tiles, target = self._mosaic_plan(image_id, im, ratio, size)
+            return self._mosaic_item(tiles, size, target)
         pixels = torch.from_numpy(np.array(im, dtype=np.uint8))
         boxes, categories = self._get_target(image_id)
         boxes[:, :4] *= ratio
@@ -741,6 +887,11 @@ class CocoDataset(data.dataset.Dataset):
             rotation = (free_rotation_matrix(cw, ch, free), mirror)
         if mirror:
             boxes = self._flip_boxes(boxes, cw)
+        geometry = size + (0, cw, ch, coefficients) + self._colour_draws() + rotation
+        return pixels, geometry, torch.cat([boxes, categories], dim=1)
+
+    def _colour_draws(self):
+        """`_colour`'s draws and clamps as descriptors -> (flags, brightness, contrast, saturation, hue)."""
         flags, brightness, contrast, saturation, hue = 0, 1.0, 1.0, 1.0, 0
         if self.augment_brightness:
             flags, brightness = flags | AUGMENT_BRIGHTNESS, max(0, random.normalvariate(1, self.augment_brightness))
@@ -750,8 +901,54 @@ class CocoDataset(data.dataset.Dataset):
             flags, hue = flags | AUGMENT_HUE, hue_shift_byte(min(0.5, max(-0.5, random.normalvariate(0, self.augment_hue))))
         if self.augment_saturation:
             flags, saturation = flags | AUGMENT_SATURATION, max(0, random.normalvariate(1, self.augment_saturation))
-        geometry = size + (0, cw, ch, coefficients, flags, brightness, contrast, saturation, hue) + rotation
-        return pixels, geometry, torch.cat([boxes, categories], dim=1)
+        return flags, brightness, contrast, saturation, hue
+
+    # -- mosaic ---------------------------------------------------------------------------------------------
+    def _mosaic_plan(self, image_id, im, ratio, size):
+        """Every draw of a mosaic item behind its decision, in this order: the scale g, the centre, three more images (from the whole
+        set; each with its own `_open` draw), four mirror draws -> (tiles, target).  tiles: `(k, decoded image, tile width, tile
+        height, mirror, mosaic_placement)` for every tile that has pixels on the canvas `size`; target: the boxes of those tiles in
+        tile order (`mosaic_tile_boxes`), or the "no box" row of `_get_target`."""
+        g = random.uniform(*self.mosaic_scale)
+        cx, cy = int(random.uniform(0.25, 0.75) * size[0]), int(random.uniform(0.25, 0.75) * size[1])
+        opened = [(image_id, im, ratio, size)]
+        for _ in range(3):
+            other = self.ids[random.randrange(len(self.ids))]
+            opened.append((other,) + self._open(other))
+        mirrors = [random.randint(0, 1) for _ in range(4)]
+        tiles, rows = [], []
+        for k, (tile_id, tile_im, tile_ratio, tile_size) in enumerate(opened):
+            tw, th = max(1, int(g * tile_size[0])), max(1, int(g * tile_size[1]))
+            placement = mosaic_placement(k, tw, th, cx, cy, *size)
+            if placement[2] == 0 or placement[3] == 0:
+                continue
+            tiles.append((k, tile_im, tw, th, mirrors[k], placement))
+            boxes, categories = self._get_target(tile_id)
+            real = categories[:, 0] >= 0                                 # (the "no box" row is no box)
+            moved, keep = mosaic_tile_boxes(boxes[real], tile_ratio * g, tw, mirrors[k], placement)
+            rows.append(torch.cat([moved[keep].float(), categories[real][keep]], dim=1))
+        target = torch.cat(rows, dim=0) if rows else torch.zeros((0, self.box_fields + 1))
+        if not target.shape[0]:
+            target = torch.cat([torch.ones([1, self.box_fields]), torch.ones([1, 1]) * -1], dim=1)
+        return tiles, target
+
+    def _mosaic_host(self, tiles, size):
+        """The canvas of `_mosaic_plan`'s tiles with Pillow: one resize per tile straight from its source, the mirror, crop, paste."""
+        canvas = Image.new('RGB', size, MOSAIC_FILL)
+        for _, im, tw, th, mirror, (dx, dy, dw, dh, sx, sy) in tiles:
+            tile = im.resize((tw, th), Image.BILINEAR)
+            if mirror:
+                tile = tile.transpose(Image.FLIP_LEFT_RIGHT)
+            canvas.paste(tile.crop((sx, sy, sx + dw, sy + dh)), (dx, dy))
+        return canvas
+
+    def _mosaic_item(self, tiles, size, target):
+        """The mosaic item of `device_augment=True`: `(the tiles' source pixels, MosaicGeometry, target)`; the colour draws happen
+        here, behind `_mosaic_plan`'s."""
+        pixels = [torch.from_numpy(np.array(t[1], dtype=np.uint8)) for t in tiles]
+        geometry = MosaicGeometry(size[0], size[1], tuple((tw, th, mirror) for _, _, tw, th, mirror, _ in tiles),
+                                  tuple((t[0], n) + t[5] for n, t in enumerate(tiles)), *self._colour_draws())
+        return pixels, geometry, target
 
     def __getitem__(self, index):
         image_id = self.ids[index]
@@ -759,7 +956,15 @@ class CocoDataset(data.dataset.Dataset):
             return self._augment_item(image_id)
         if self.device_resize:
             return self._source_item(image_id)
-        im, ratio = self._open_resized(image_id)
+        if self.training and self.mosaic:                                   # the decision is drawn behind the jitter, before the resize
+            im, ratio, size = self._open(image_id)
+            if random.random() < self.mosaic:
+                tiles, target = self._mosaic_plan(image_id, im, ratio, size)
+                im = self._colour(self._mosaic_host(tiles, size))
+                return torch.from_numpy(np.array(im.convert('RGBA'), dtype=np.uint8)), target
+            im = im.resize(size, Image.BILINEAR)
+        else:
+            im, ratio = self._open_resized(image_id)
         target = None
         if self.training:
             boxes, categories = self._get_target(image_id)
@@ -943,6 +1148,8 @@ class DataIterator:
             lines.append('    augmentations on: {}'.format('the device (odtk_augment_images)' if self.device.type == 'cuda' else 'the host (numpy)'))
         if self.dataset.augment_free_rotate:
             lines.append('    free rotation: {:g} to {:g} degrees'.format(*self.dataset.augment_free_rotate))
+        if self.dataset.mosaic:
+            lines.append('    mosaic: probability {:g}, scale {:g} to {:g}'.format(self.dataset.mosaic, *self.dataset.mosaic_scale))
         return '\n'.join(lines)
 
     def __len__(self):
@@ -956,7 +1163,11 @@ class DataIterator:
             return batch.apply_cpu(self.table, self.dtype)
         from . import _C
         uploaded = packed.to(self.device, non_blocking=True)
-        images = (_C.Image * batch.batch).from_buffer_copy(batch.images.tobytes())
+        images = (_C.Image * len(batch.images)).from_buffer_copy(batch.images.tobytes())
+        if batch.mosaics is not None:                               # resize of the sources to bytes, composition, (sum of L,) colour chain + table + pad
+            mosaics = (_C.Mosaic * batch.batch).from_buffer_copy(batch.mosaics.tobytes())
+            augments = (_C.Augment * batch.batch).from_buffer_copy(batch.augments.tobytes())
+            return _C.mosaic_images(uploaded, images, mosaics, augments, batch.tables(uploaded), self.table, batch.height, batch.width)
         if batch.augments is not None:                              # resize to bytes, (sum of L,) gather + colour chain + table + pad
             augments = (_C.Augment * batch.batch).from_buffer_copy(batch.augments.tobytes())
             rotations = None                                        # (with them: + the free rotation, between the resize and the sum)

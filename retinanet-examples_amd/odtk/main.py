@@ -17,6 +17,9 @@ What differs from the reference, and why:
     colour options) on the GPU, as a short chain of HIP launches per batch, bit-identical to Pillow on the host.
   * `--augment-free-rotate MIN MAX` (train), which the reference parses and ignores, rotates every training image by an angle drawn
     from the range, bilinear, on its own canvas, and its boxes with it; with `--device-augment` on the GPU, the same pixels.
+  * `--mosaic P` (train) with `--mosaic-scale LO HI` is new: with probability P a training item is a mosaic of four images on one
+    canvas (odtk/data.py: CocoDataset); with `--device-augment` the composition is one more HIP pass, the same pixels.  Axis-aligned
+    boxes only, not with the turns or the free rotation.  Never stored in a checkpoint.
   * `--soft-nms {linear,gaussian}` (infer; train: its validation passes) with `--soft-nms-sigma` / `--soft-nms-min-score` is new:
     Soft-NMS (odtk/box.py:soft_nms, one HIP launch) instead of the reference's hard suppression.  Never stored in a checkpoint.
   * `--matrix-nms {linear,gaussian}` (infer; train: its validation passes) with `--matrix-nms-sigma` / `--matrix-nms-min-score` /
@@ -157,6 +160,11 @@ TRAIN_FLAGS = [
     _flag('--assigner', str, argparse.SUPPRESS, 'how ground truth becomes training targets: iou = the fixed --anchor-ious thresholds '
           '(default), atss = adaptive training sample selection, tal = task-aligned assignment by the predicted score and IoU (both '
           'not with --rotated-bbox).  Not stored in the checkpoint: give it again when resuming', choices=['iou', 'atss', 'tal']),
+    _flag('--mosaic', float, argparse.SUPPRESS, 'probability with which a training item is a mosaic of four images on one canvas of '
+          'the image\'s size (default 0: off; on the host, or with --device-augment on the device, the same pixels either way; not with '
+          '--rotated-bbox, --augment-rotate, --augment-free-rotate or --device-resize alone).  Not stored in the checkpoint', metavar='P'),
+    _flag('--mosaic-scale', float, argparse.SUPPRESS, 'range of the factor on the four images of a mosaic, 0 < LO <= HI <= 1 '
+          '(default 0.5 1; needs --mosaic)', nargs=2, metavar=('LO', 'HI')),
     _flag('--atss-topk', int, argparse.SUPPRESS, 'nearest cells per box and pyramid level that ATSS considers, 1..16 (default 9; '
           'needs --assigner atss)', metavar='num'),
     _flag('--tal-topk', int, argparse.SUPPRESS, 'anchors a box takes as positives under task-aligned assignment, 1..16 (default 13; '
@@ -272,6 +280,20 @@ def parse(args):
         parser.error('--box-loss {} is not available with --rotated-bbox'.format(parsed.box_loss))
     if getattr(parsed, 'cls_loss', 'focal') != 'focal' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--cls-loss {} is not available with --rotated-bbox'.format(parsed.cls_loss))
+    if hasattr(parsed, 'mosaic_scale') and not hasattr(parsed, 'mosaic'):
+        parser.error('--mosaic-scale needs --mosaic P')
+    if hasattr(parsed, 'mosaic'):
+        if not 0 <= parsed.mosaic <= 1:                                           # (a NaN fails both comparisons)
+            parser.error('--mosaic must be a probability in [0, 1]')
+        low, high = getattr(parsed, 'mosaic_scale', (0.5, 1.0))
+        if not 0 < low <= high <= 1:
+            parser.error('--mosaic-scale must be a range with 0 < LO <= HI <= 1')
+        for flag, given in (('--rotated-bbox', parsed.rotated_bbox), ('--augment-rotate', parsed.augment_rotate),
+                            ('--augment-free-rotate', any(parsed.augment_free_rotate)),
+                            ('--device-resize without --device-augment', getattr(parsed, 'device_resize', False)
+                             and not getattr(parsed, 'device_augment', False))):
+            if given:
+                parser.error('--mosaic is not available with ' + flag)
     return parsed
 
 
@@ -399,7 +421,8 @@ def worker(rank, args, world, spawned=False):
                                rotated_bbox=args.rotated_bbox, absolute_angle=args.absolute_angle,
                                num_workers=args.workers, device_resize=getattr(args, 'device_resize', False),
                                device_augment=getattr(args, 'device_augment', False),
-                               augment_free_rotate=tuple(args.augment_free_rotate))
+                               augment_free_rotate=tuple(args.augment_free_rotate), mosaic=getattr(args, 'mosaic', 0.0),
+                               mosaic_scale=tuple(getattr(args, 'mosaic_scale', (0.5, 1.0))))
         if args.command == 'infer':
             return infer.infer(model, args.images, args.output, args.resize, args.max_size, args.batch,
                                annotations=args.annotations, mixed_precision=not args.full_precision,

@@ -253,7 +253,8 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
           val_iterations, lr, warmup, milestones, gamma, rank=0, world=1, mixed_precision=True, with_apex=False,
           use_dali=False, verbose=True, metrics_url=None, logdir=None, rotate_augment=False, augment_brightness=0.0,
           augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, regularization_l2=0.0001, rotated_bbox=False,
-          absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False, augment_free_rotate=(0, 0)):
+          absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False, augment_free_rotate=(0, 0),
+          mosaic=0.0, mosaic_scale=(0.5, 1.0)):
     """Train `model` on the images under `path` -- the reference's `train.train` (train.py:18-214), same
     arguments: COCO-style annotations through odtk/data.py (`jitter` = the range of short-side sizes),
     `train_batches` above, periodic validation through `infer.infer`, checkpoints to `state['path']`, scalars
@@ -262,7 +263,9 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
     `rotate_augment` and the colour augmentations (ValueError).  `device_augment`: `device_resize`, and those augmentations run on the
     device as well (odtk_augment_images), bit-identical to the host loader.  `augment_free_rotate` = (lo, hi) in degrees: every
     training image is rotated about its centre by an angle drawn from that range, its boxes with it (odtk/data.py; on the host, or
-    with `device_augment` on the device, the same pixels either way); (0, 0) is off."""
+    with `device_augment` on the device, the same pixels either way); (0, 0) is off.  `mosaic` = the probability with which a
+    training item is a mosaic of four images, `mosaic_scale` = (lo, hi) the range of the factor on them (odtk/data.py: CocoDataset;
+    host or device likewise); 0 is off.  It is not stored in the checkpoint."""
     from . import infer as infer_module
     from .data import DataIterator, RotatedDataIterator
     if use_dali or with_apex:
@@ -272,6 +275,8 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
     if verbose:
         print('Preparing dataset...')
     extra = {'absolute_angle': absolute_angle} if rotated_bbox else {}
+    if mosaic:
+        extra.update(mosaic=mosaic, mosaic_scale=tuple(mosaic_scale))
     data_iterator = (RotatedDataIterator if rotated_bbox else DataIterator)(
         path, jitter, max_size, batch_size, model.stride, world, annotations, training=True,
         rotate_augment=rotate_augment, augment_brightness=augment_brightness, augment_contrast=augment_contrast,

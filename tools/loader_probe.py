@@ -17,7 +17,12 @@ of odtk_augment_images does the rest).
 
   python tools/loader_probe.py --augment --free-rotate
 the same with augment_free_rotate=(-30, 30) on top: the host path rotates the resized image with Pillow (bilinear, in double), the
-descriptor path ships six doubles per image and odtk_augment_images_ex rotates on the device."""
+descriptor path ships six doubles per image and odtk_augment_images_ex rotates on the device.
+
+  python tools/loader_probe.py --mosaic 1
+training items with the four colour augmentations on (no quarter turns: mosaic refuses them) and mosaic=P: on the host path a worker
+decodes four images, resizes each with Pillow and pastes them; with device_augment=True it ships the four source images and one
+placement record, and odtk_mosaic_images composes on the device."""
 import json
 import os
 import sys
@@ -35,12 +40,15 @@ from odtk.data import CocoDataset, DataIterator, normalise_batch
 N = int(os.environ.get('PROBE_IMAGES', 192))
 REPEAT = int(os.environ.get('PROBE_REPEAT', 1))
 WIDTH, HEIGHT = (int(v) for v in os.environ.get('PROBE_SIZE', '1280x800').split('x'))
-AUGMENT = '--augment' in sys.argv[1:]
+MOSAIC = float(sys.argv[sys.argv.index('--mosaic') + 1]) if '--mosaic' in sys.argv[1:] else 0.0
+AUGMENT = '--augment' in sys.argv[1:] or MOSAIC > 0
 FREE_ROTATE = AUGMENT and '--free-rotate' in sys.argv[1:]
 OPTIONS = dict(training=True, rotate_augment=True, augment_brightness=0.002, augment_contrast=0.002, augment_hue=0.0002,
                augment_saturation=0.002) if AUGMENT else {}                # the sigmas are `odtk train`'s defaults
 if FREE_ROTATE:
     OPTIONS['augment_free_rotate'] = (-30, 30)
+if MOSAIC:
+    OPTIONS.update(rotate_augment=False, mosaic=MOSAIC)
 MODES = os.environ.get('PROBE_MODES', 'host,device').split(',')
 scratch = tempfile.mkdtemp(prefix='odtk_probe_')
 yy, xx = np.mgrid[0:HEIGHT, 0:WIDTH]
@@ -61,7 +69,8 @@ for mode in MODES:
     device_resize = mode == 'device'
     switch = {'device_augment' if AUGMENT else 'device_resize': device_resize}
     if AUGMENT:
-        print('--- training items, five augmentations on%s: %s' % (' and free rotation by -30 .. 30 degrees' if FREE_ROTATE else '', ('device_augment=True: workers ship source pixels and descriptors' if device_resize
+        print('--- training items, %s augmentations on%s: %s' % ('four colour' if MOSAIC else 'five', ' and mosaic with probability %g' % MOSAIC if MOSAIC else
+                                                               ' and free rotation by -30 .. 30 degrees' if FREE_ROTATE else '', ('device_augment=True: workers ship source pixels and descriptors' if device_resize
                                                                  else 'host path: workers resize, turn and enhance with Pillow')))
     else:
         print('--- %s' % ('device_resize=True: workers ship source pixels' if device_resize else 'host path: workers resize with Pillow'))
