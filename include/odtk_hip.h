@@ -67,8 +67,8 @@ extern "C" {
 const char *odtk_version(void);
 /* ABI guard.  sizeof() of a struct type of this header AS THE LIBRARY WAS COMPILED: which = 0 odtk_level_t,
  * 1 odtk_snap_level_t, 2 odtk_snap_rot_level_t, 3 odtk_loss_level_t, 5 odtk_image_t, 6 odtk_augment_t, 7 odtk_rotation_t,
- * 9 odtk_candidates_t, 11 odtk_tile_t, 14 odtk_mosaic_tile_t, 15 odtk_mosaic_t; -1 for any other value (4, 8, 10, 12 and 13 stay
- * unassigned: tests/test_abi_host.py, tests/test_free_rotate.py, tests/test_box_vote.py and later ones probe them as unknown ids).  A binding compiled (or
+ * 9 odtk_candidates_t, 11 odtk_tile_t, 14 odtk_mosaic_tile_t, 15 odtk_mosaic_t, 17 odtk_optim_tensor_t; -1 for any other value (4, 8, 10,
+ * 12, 13 and 16 stay unassigned: tests/test_abi_host.py, tests/test_free_rotate.py, tests/test_box_vote.py and later ones probe them as unknown ids).  A binding compiled (or
  * mirrored) against another revision of this header would pass level arrays of the wrong stride: both bindings compare
  * their own sizeof with this at load time and refuse to load on a mismatch (odtk/_C.py, csrc/odtk_binding.cpp). */
 int odtk_abi_struct_size(int which);
@@ -965,6 +965,56 @@ int odtk_quality_loss_levels_forward(int n_levels, const odtk_loss_level_t *leve
 int odtk_quality_loss_levels_backward(int n_levels, const odtk_loss_level_t *levels, const float *const *anchors, int batch_size,
                                       int num_anchors, int num_classes, int dtype, int kind, float alpha, float gamma,
                                       const float *grad_sums, void *stream);
+
+/*
+ * odtk_optim_sgd_step / odtk_optim_grad_norm -- the optimisation step of training as one streaming pass over the parameters
+ * (odtk/optim.py: FusedSGD, ModelEMA; `odtk train --ema / --clip-grad-norm / --fused-step`), and the global L2 norm of the
+ * gradients as one more pass.  No reference equivalent (the reference steps with torch.optim.SGD); the definition -- the contract --
+ * restated in torch in odtk/optim.py (FusedSGD._step_reference), every operation in float32 and rounded on its own:
+ *   skipped -- nothing is written -- when found_inf is given and *found_inf != 0, or norm_state is given and its skip word is set;
+ *   otherwise per element, with p, buf, e the element of param, momentum, ema:
+ *     g = grad;  g = g / *grad_scale (grad_scale given);  g = g * coef (norm_state given);  g = g + weight_decay * p (weight_decay != 0)
+ *     buf = first ? g : (momentum * buf) + g;   p = p - (lr * buf);   e = e + one_minus_decay * (p - e) (the tensor's ema given)
+ * which is torch's SGD (dampening 0, no Nesterov) behind GradScaler's unscale and clip_grad_norm_'s factor, and lerp for the EMA.
+ *   tensors      HOST array of 1..ODTK_MAX_OPTIM_TENSORS descriptors of DEVICE float32 arrays of `numel` contiguous elements each;
+ *                they travel by value in the launch (a model with more tensors takes several calls).  numel == 0 is legal and the
+ *                tensor is skipped; `ema` may be NULL per tensor; `momentum` is not read when first != 0.  A tensor whose four
+ *                pointers are all 16-byte aligned is walked with 16-byte accesses, any other element by element: the same bits.
+ *   grad_scale, found_inf   DEVICE float32 scalars in torch.amp.GradScaler's layout, each may be NULL; never read on the host.
+ *   norm_state   NULL, or the DEVICE state odtk_optim_grad_norm wrote: 16 bytes = float32 norm, float32 coef, uint32 skip, uint32 0.
+ *   one_minus_decay   1 - the EMA's decay, in [0, 1].
+ * odtk_optim_grad_norm: norm = float32(sqrt(sum over every element of double(g') * double(g'))) with g' = g / *grad_scale in float32
+ * (grad_scale given), the value the step will use; the squares are exact in double and added in double in one fixed order (lane,
+ * wave, workgroup, then one slot of the workspace per workgroup; the second launch is ONE workgroup that adds the slots up): the
+ * same bits on every run, no atomics.  It writes norm, coef = min(1, max_norm / (norm + 1e-6f)) in float32 (clip_grad_norm_'s
+ * factor; NaN stays NaN) and skip = (norm is not finite) to `state`.  Only `grad` and `numel` of a descriptor are read.
+ * odtk_optim_grad_norm_chained is the same for a model of more than ODTK_MAX_OPTIM_TENSORS tensors: every call of the chain passes
+ * the SAME workspace and the number of slots the calls before it filled (prior_slots; a call fills one slot per started chunk
+ * of ODTK_OPTIM_CHUNK elements of each of its tensors, behind those), and the call with last != 0 adds all of them up in index
+ * order and writes the state; max_norm and state are looked at in that call only.  odtk_optim_grad_norm is the chain of one.
+ * Workspace (the norm): two-phase query as everywhere, 8 bytes per slot up to this call's last one; too small: ODTK_ERR_WORKSPACE.
+ * Everything is checked on the host before anything touches HIP.  ODTK_ERR_INVALID: n_tensors outside 1..ODTK_MAX_OPTIM_TENSORS, a
+ * NULL tensor list, a negative numel, a NULL param / grad / momentum (the norm: grad) in a tensor with numel > 0, a pointer that
+ * is not aligned to its element, a first other than 0 / 1, an lr, momentum or weight_decay that is not finite, a one_minus_decay
+ * outside [0, 1], a max_norm that is not finite or not > 0, a NULL state, a negative prior_slots, more than 2^31 - 1 chunks.
+ * One launch per call of the step, timed under ODTK_KERNEL_EPILOGUE; the norm's launches are timed under
+ * ODTK_KERNEL_LOSS_REDUCE.  No allocation, no host synchronisation: capturable in a hipGraph.
+ */
+#define ODTK_MAX_OPTIM_TENSORS 64     /* descriptors per call: they travel by value, kernargs stay < 4 KiB */
+#define ODTK_OPTIM_CHUNK 4096         /* elements of one tensor a workgroup owns */
+typedef struct odtk_optim_tensor {
+  float *param;
+  const float *grad;
+  float *momentum;
+  float *ema;                         /* may be NULL */
+  int64_t numel;
+} odtk_optim_tensor_t;      /* 40 bytes; odtk_abi_struct_size id 17 */
+int odtk_optim_grad_norm(int n_tensors, const odtk_optim_tensor_t *tensors, const float *grad_scale, float max_norm, void *state,
+                         void *workspace, size_t workspace_size, void *stream);
+int odtk_optim_grad_norm_chained(int n_tensors, const odtk_optim_tensor_t *tensors, const float *grad_scale, float max_norm, void *state,
+                                 int prior_slots, int last, void *workspace, size_t workspace_size, void *stream);
+int odtk_optim_sgd_step(int n_tensors, const odtk_optim_tensor_t *tensors, float lr, float momentum, float weight_decay, int first,
+                        float one_minus_decay, const float *grad_scale, const float *found_inf, const void *norm_state, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (used by bench.py; off by default, zero cost when off).

@@ -45,6 +45,7 @@ int odtk_abi_struct_size(int which) {
     case 11: return static_cast<int>(sizeof(odtk_tile_t));
     case 14: return static_cast<int>(sizeof(odtk_mosaic_tile_t));
     case 15: return static_cast<int>(sizeof(odtk_mosaic_t));
+    case 17: return static_cast<int>(sizeof(odtk_optim_tensor_t));
     default: return -1;
   }
 }

@@ -515,7 +515,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       odtk_abi_struct_size(1) != static_cast<int>(sizeof(odtk_snap_level_t)) ||
       odtk_abi_struct_size(2) != static_cast<int>(sizeof(odtk_snap_rot_level_t)) ||
       odtk_abi_struct_size(9) != static_cast<int>(sizeof(odtk_candidates_t)) ||
-      odtk_abi_struct_size(11) != static_cast<int>(sizeof(odtk_tile_t)))
+      odtk_abi_struct_size(11) != static_cast<int>(sizeof(odtk_tile_t)) ||
+      odtk_abi_struct_size(17) != static_cast<int>(sizeof(odtk_optim_tensor_t)))
     throw py::import_error("odtk._C_ext was compiled against another revision of include/odtk_hip.h than libodtk_hip.so "
                            "(struct sizes differ): rebuild it -- make -C retinanet-examples_amd/csrc");
   py::class_<Engine>(m, "Engine")
@@ -553,6 +554,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // wrong stride (tests/test_compiled_binding.py compares them with the ctypes mirror on every CPU run)
   m.def("abi_sizes", [] {
     return py::dict(py::arg("level") = sizeof(odtk_level_t), py::arg("snap_level") = sizeof(odtk_snap_level_t),
-                    py::arg("snap_rot_level") = sizeof(odtk_snap_rot_level_t));
+                    py::arg("snap_rot_level") = sizeof(odtk_snap_rot_level_t), py::arg("optim_tensor") = sizeof(odtk_optim_tensor_t));
   });
 }

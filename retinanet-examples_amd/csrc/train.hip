@@ -1,6 +1,7 @@
 // train.hip -- target assignment (odtk_snap_to_anchors*, odtk_atss_assign_levels, odtk_tal_assign_levels) and the focal + smooth-L1 loss: launch shapes,
 // odtk_debug_loss_*, odtk_retina_loss_*; the IoU-family box losses (odtk_box_iou_loss_levels_*); the quality / varifocal
-// classification losses (odtk_quality_loss_levels_*); the Gaussian box losses of rotated boxes (odtk_rotated_box_loss_levels_*).
+// classification losses (odtk_quality_loss_levels_*); the Gaussian box losses of rotated boxes (odtk_rotated_box_loss_levels_*);
+// the optimisation step and the gradient norm (odtk_optim_sgd_step, odtk_optim_grad_norm*).
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -13,6 +14,7 @@
 #include "box_iou_loss.hpp"   // (all three over cell_loss.hpp)
 #include "quality_loss.hpp"
 #include "rotated_box_loss.hpp"
+#include "optim.hpp"
 
 namespace {
 
@@ -336,6 +338,31 @@ int cell_loss_levels_backward(int rc, const float *grad_sums, Walk walk) {
   if (reinterpret_cast<uintptr_t>(grad_sums) & 3u) return ODTK_ERR_INVALID;
   walk();
   ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
+}
+
+// The kernel arguments of odtk_optim_sgd_step / odtk_optim_grad_norm* (csrc/optim.hpp) from the ABI's tensor list: the prefix table of
+// the chunks and the alignment bit of every tensor.  `norm`: only grad and numel of a descriptor count.
+int optim_fill(odtk::OptimArgs &oa, int n_tensors, const odtk_optim_tensor_t *tensors, bool norm, unsigned *total_blocks) {
+  if (n_tensors < 1 || n_tensors > ODTK_MAX_OPTIM_TENSORS || !tensors) return ODTK_ERR_INVALID;
+  std::memset(&oa, 0, sizeof oa);
+  oa.n_tensors = static_cast<uint32_t>(n_tensors);
+  unsigned long long total = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const odtk_optim_tensor_t &t = tensors[i];
+    if (t.numel < 0) return ODTK_ERR_INVALID;
+    const uintptr_t all = reinterpret_cast<uintptr_t>(t.grad) |
+                          (norm ? 0u : reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.momentum) | reinterpret_cast<uintptr_t>(t.ema));
+    if (t.numel > 0 && (!t.grad || (!norm && (!t.param || !t.momentum)))) return ODTK_ERR_INVALID;
+    if (all & 3u) return ODTK_ERR_INVALID;
+    oa.t[i] = t;
+    if (!(all & 15u)) oa.vec_mask |= 1ull << i;
+    oa.block_begin[i] = static_cast<uint32_t>(total);
+    total += (static_cast<unsigned long long>(t.numel) + ODTK_OPTIM_CHUNK - 1) / ODTK_OPTIM_CHUNK;
+    if (total > 0x7fffffffull) return ODTK_ERR_INVALID;
+  }
+  for (int i = n_tensors; i <= ODTK_MAX_OPTIM_TENSORS; ++i) oa.block_begin[i] = static_cast<uint32_t>(total);
+  *total_blocks = static_cast<unsigned>(total);
   return ODTK_OK;
 }
 
@@ -756,6 +783,68 @@ int odtk_rotated_box_loss_levels_backward(int n_levels, const odtk_loss_level_t 
   unsigned total = 0;
   const int rc = box_iou_fill(ba, true, true, n_levels, levels, anchors, batch_size, num_anchors, dtype, kind, grad_sums, &total, 6);
   return cell_loss_levels_backward(rc, grad_sums, [&] { box_loss_dispatch<odtk::RotatedBoxLoss, true>(dtype, ba, total, static_cast<hipStream_t>(stream)); });
+}
+
+int odtk_optim_grad_norm_chained(int n_tensors, const odtk_optim_tensor_t *tensors, const float *grad_scale, float max_norm, void *state,
+                                 int prior_slots, int last, void *workspace, size_t workspace_size, void *stream) {
+  odtk::OptimArgs oa;
+  unsigned total = 0;
+  const int rc = optim_fill(oa, n_tensors, tensors, true, &total);
+  if (rc != ODTK_OK) return rc;
+  if (prior_slots < 0 || (last != 0 && last != 1) || 1ull * prior_slots + total > 0x7fffffffull / sizeof(double)) return ODTK_ERR_INVALID;
+  if (last && (!std::isfinite(max_norm) || !(max_norm > 0.0f))) return ODTK_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(grad_scale) & 3u) return ODTK_ERR_INVALID;
+  const size_t slots = static_cast<size_t>(prior_slots) + total;
+  const size_t need = align_up(slots ? slots * sizeof(double) : 1);
+  if (!workspace) return static_cast<int>(need);                       // two-phase convention of the reference's plugins
+  if (workspace_size < need) return ODTK_ERR_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7u) return ODTK_ERR_INVALID;
+  if (last && (!state || (reinterpret_cast<uintptr_t>(state) & 3u))) return ODTK_ERR_INVALID;
+  oa.grad_scale = grad_scale;
+  oa.slots = static_cast<double *>(workspace) + prior_slots;
+  if (total) {                                                         // (a list of empty tensors fills no slot)
+    timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::optim_grad_norm_kernel, dim3(total), dim3(odtk::kOptimThreads), 0,
+                 static_cast<hipStream_t>(stream), oa);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  if (last) {
+    odtk::OptimFinishArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    fa.slots = static_cast<const double *>(workspace);
+    fa.n_slots = static_cast<uint32_t>(slots);
+    fa.max_norm = max_norm;
+    fa.state = static_cast<odtk::OptimState *>(state);
+    timed_launch(ODTK_KERNEL_LOSS_REDUCE, odtk::optim_grad_norm_finish_kernel, dim3(1), dim3(odtk::kOptimFinishThreads), 0,
+                 static_cast<hipStream_t>(stream), fa);
+    ODTK_HIP_TRY(hipGetLastError());
+  }
+  return ODTK_OK;
+}
+
+int odtk_optim_grad_norm(int n_tensors, const odtk_optim_tensor_t *tensors, const float *grad_scale, float max_norm, void *state,
+                         void *workspace, size_t workspace_size, void *stream) {
+  return odtk_optim_grad_norm_chained(n_tensors, tensors, grad_scale, max_norm, state, 0, 1, workspace, workspace_size, stream);
+}
+
+int odtk_optim_sgd_step(int n_tensors, const odtk_optim_tensor_t *tensors, float lr, float momentum, float weight_decay, int first,
+                        float one_minus_decay, const float *grad_scale, const float *found_inf, const void *norm_state, void *stream) {
+  odtk::OptimArgs oa;
+  unsigned total = 0;
+  const int rc = optim_fill(oa, n_tensors, tensors, false, &total);
+  if (rc != ODTK_OK) return rc;
+  if (!std::isfinite(lr) || !std::isfinite(momentum) || !std::isfinite(weight_decay) || (first != 0 && first != 1)) return ODTK_ERR_INVALID;
+  if (!(one_minus_decay >= 0.0f && one_minus_decay <= 1.0f)) return ODTK_ERR_INVALID;            // (a NaN fails both comparisons)
+  if ((reinterpret_cast<uintptr_t>(grad_scale) | reinterpret_cast<uintptr_t>(found_inf) | reinterpret_cast<uintptr_t>(norm_state)) & 3u)
+    return ODTK_ERR_INVALID;
+  oa.lr = lr; oa.momentum = momentum; oa.wd = weight_decay; oa.one_minus_decay = one_minus_decay;
+  oa.first = first;
+  oa.grad_scale = grad_scale; oa.found_inf = found_inf;
+  oa.norm_state = static_cast<const odtk::OptimState *>(norm_state);
+  if (!total) return ODTK_OK;                                          // nothing but empty tensors
+  timed_launch(ODTK_KERNEL_EPILOGUE, odtk::optim_sgd_step_kernel, dim3(total), dim3(odtk::kOptimThreads), 0,
+               static_cast<hipStream_t>(stream), oa);
+  ODTK_HIP_TRY(hipGetLastError());
+  return ODTK_OK;
 }
 
 }  // extern "C"

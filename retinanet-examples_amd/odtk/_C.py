@@ -33,6 +33,7 @@ FLAG_ROTATED, FLAG_LOGITS, FLAG_ROTATED_NMS_FIXED_ANGLE = 1, 2, 4
 MAX_LEVELS, MAX_ANCHORS, MAX_TOP_N, MAX_NMS_COUNT, MAX_NMS_COUNT_SCRATCH = 6, 32, 16384, 7680, 1 << 22
 MAX_CONCAT_PARTS = 8
 MAX_TILES = 64
+MAX_OPTIM_TENSORS, OPTIM_CHUNK = 64, 4096   # = ODTK_MAX_OPTIM_TENSORS, ODTK_OPTIM_CHUNK of include/odtk_hip.h (tests/test_optim.py compares)
 SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 1, 2
 MATRIX_NMS_LINEAR, MATRIX_NMS_GAUSSIAN = 1, 2
 MAX_MATRIX_NMS_PRE = 4096
@@ -110,6 +111,11 @@ class Mosaic(ctypes.Structure):
                 ('fill', ctypes.c_uint8 * 3), ('pad_', ctypes.c_uint8)]
 
 
+class OptimTensor(ctypes.Structure):
+    """odtk_optim_tensor_t"""
+    _fields_ = [('param', _vp), ('grad', _vp), ('momentum', _vp), ('ema', _vp), ('numel', ctypes.c_int64)]
+
+
 class Candidates(ctypes.Structure):
     """odtk_candidates_t"""
     _fields_ = [('scores', _vp), ('boxes', _vp), ('classes', _vp), ('count', ctypes.c_uint32), ('mirror_width', ctypes.c_int32)]
@@ -169,6 +175,11 @@ _SIGNATURES = {
                                          [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [_vp, _vp, _sz, _vp]),
     'odtk_quality_loss_levels_backward': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LossLevel), ctypes.POINTER(_fp)] +
                                           [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [_vp, _vp]),
+    'odtk_optim_grad_norm': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptimTensor), _vp, ctypes.c_float, _vp, _vp, _sz, _vp]),
+    'odtk_optim_grad_norm_chained': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptimTensor), _vp, ctypes.c_float, _vp, ctypes.c_int,
+                                                    ctypes.c_int, _vp, _sz, _vp]),
+    'odtk_optim_sgd_step': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptimTensor)] + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_float,
+                                           _vp, _vp, _vp, _vp]),
     'odtk_bias_act': (ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     'odtk_profile_enable': (ctypes.c_int, [ctypes.c_int]),
     'odtk_debug_set_trace': (ctypes.c_int, [_vp]),
@@ -262,7 +273,7 @@ def library():
             fn.argtypes = args
         # ABI guard: the ctypes mirrors below must have the layout the library was compiled with (include/odtk_hip.h)
         for which, mirror in ((0, Level), (1, SnapLevel), (2, SnapRotLevel), (3, LossLevel), (5, Image), (6, Augment), (7, Rotation),
-                              (9, Candidates), (11, Tile), (14, MosaicTile), (15, Mosaic)):
+                              (9, Candidates), (11, Tile), (14, MosaicTile), (15, Mosaic), (17, OptimTensor)):
             if lib.odtk_abi_struct_size(which) != ctypes.sizeof(mirror):
                 raise ImportError('odtk._C: %s was built from another revision of include/odtk_hip.h (sizeof struct %d: library %d, '
                                   'binding %d) -- rebuild it (make -C retinanet-examples_amd/csrc)'
@@ -1636,6 +1647,82 @@ def loss_form(form):
     """Debug / A-B: 0 = the symmetric element form everywhere, 1 (default) = vectors of negatives through the negatives-only
     form; 2..4 = timing ablations with wrong sums (include/odtk_hip.h: odtk_debug_loss_form)."""
     _check(library().odtk_debug_loss_form(int(form)), 'loss_form')
+
+
+def _dense(t):
+    """No gaps and no overlap: contiguous in the default or a channels_last order (what parameters and their gradients are)."""
+    return (t.numel() == 0 or t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)) or
+            (t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d)))
+
+
+def optim_tensors(params, grads, momenta, emas=None):
+    """The descriptor groups of odtk_optim_sgd_step / odtk_optim_grad_norm for lists of float32 CUDA tensors (`emas`: None, or a
+    list whose entries may be None): [(OptimTensor array, count)] of at most MAX_OPTIM_TENSORS entries each.  The tensors must be
+    dense (any memory format: the step is elementwise, and the four of a parameter share their strides)."""
+    groups = []
+    for first in range(0, len(params), MAX_OPTIM_TENSORS):
+        count = min(MAX_OPTIM_TENSORS, len(params) - first)
+        table = (OptimTensor * count)()
+        for i in range(count):
+            p, g, m = params[first + i], grads[first + i], momenta[first + i]
+            e = emas[first + i] if emas is not None else None
+            for t, name in ((p, 'param'), (g, 'grad'), (m, 'momentum'), (e, 'ema')):
+                if t is None and name == 'ema':
+                    continue
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == p.device):
+                    raise RuntimeError('optim_tensors: %s must be a float32 CUDA tensor on the parameter\'s device' % name)
+                if t.numel() != p.numel() or t.stride() != p.stride() or not _dense(t):
+                    raise RuntimeError('optim_tensors: %s must be dense and share the parameter\'s shape and strides' % name)
+            table[i] = OptimTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), e.data_ptr() if e is not None else None, p.numel())
+        groups.append((table, count))
+    return groups
+
+
+OPTIM_STATE_FLOATS = 4      # the device state of odtk_optim_grad_norm: float32 norm, float32 coef, uint32 skip, uint32 0
+
+
+def optim_grad_norm(groups, grad_scale, max_norm, state):
+    """Global L2 norm of the (unscaled) gradients of `groups` (optim_tensors) -> `state` (float32 CUDA tensor of OPTIM_STATE_FLOATS
+    elements: norm, coef, the skip word, 0), enqueued: one launch per group + one (include/odtk_hip.h: odtk_optim_grad_norm_chained).
+    `grad_scale`: None or a float32 CUDA scalar."""
+    if not (state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= OPTIM_STATE_FLOATS):
+        raise RuntimeError('optim_grad_norm: state must be a contiguous float32 CUDA tensor of %d elements' % OPTIM_STATE_FLOATS)
+    lib, device = library(), state.device
+    scale = _optim_scalar(grad_scale, device, 'grad_scale')
+    # the slots the calls before group k filled: one per started chunk of each of their tensors
+    prior = [0]
+    for table, _ in groups:
+        prior.append(prior[-1] + sum((int(t.numel) + OPTIM_CHUNK - 1) // OPTIM_CHUNK for t in table))
+    with torch.cuda.device(device):
+        table, count = groups[-1]                                   # the last call's query covers every slot of the chain
+        size = _check(lib.odtk_optim_grad_norm_chained(count, table, scale, float(max_norm), state.data_ptr(), prior[-2], 1, None, 0, None),
+                      'optim_grad_norm (workspace query)')
+        ws, stream = _workspace(device, size)
+        for k, (table, count) in enumerate(groups):
+            _check(lib.odtk_optim_grad_norm_chained(count, table, scale, float(max_norm), state.data_ptr(), prior[k], int(k == len(groups) - 1),
+                                                    ws.data_ptr(), ws.numel(), stream), 'optim_grad_norm')
+
+
+def _optim_scalar(t, device, name):
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.numel() == 1):
+        raise RuntimeError('%s must be a float32 CUDA scalar on the parameters\' device' % name)
+    return t.data_ptr()
+
+
+def optim_sgd_step(groups, lr, momentum, weight_decay, first, one_minus_decay, grad_scale=None, found_inf=None, norm_state=None, device=None):
+    """The fused SGD step over `groups` (optim_tensors), enqueued: one launch per group (include/odtk_hip.h: odtk_optim_sgd_step).
+    `grad_scale`, `found_inf`: None or float32 CUDA scalars (torch.amp.GradScaler's); `norm_state`: None or what optim_grad_norm
+    wrote.  Nothing is read back."""
+    lib = library()
+    args = [_optim_scalar(grad_scale, device, 'grad_scale'), _optim_scalar(found_inf, device, 'found_inf'),
+            norm_state.data_ptr() if norm_state is not None else None]
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for table, count in groups:
+            _check(lib.odtk_optim_sgd_step(count, table, float(lr), float(momentum), float(weight_decay), int(bool(first)), float(one_minus_decay),
+                                           *args, stream), 'optim_sgd_step')
 
 
 TRACE_WORDS = 16384     # odtk_debug_set_trace: >= 128 KiB (include/odtk_hip.h): coarse stamps in the first 8192 words, select_decode's

@@ -57,6 +57,15 @@ What differs from the reference, and why:
     anchors, csrc/rotated_box_loss.hpp) instead of the reference's smooth-L1 on (dx, dy, dw, dh, sin, cos), times
     `--box-loss-weight`.  The loss sees the (sin, cos) pair only through its direction and charges a square box nothing for its
     angle.  Rotated boxes only; `iou`, `giou` and `diou` stay axis-aligned only.  Never stored in a checkpoint.
+  * `--ema DECAY`, `--clip-grad-norm MAX` and `--fused-step` (train) are new: with any of them the optimisation step is
+    odtk/optim.py's `FusedSGD` -- GradScaler's unscale and skip, the clip factor, weight decay, momentum, the update and the
+    average in one HIP pass over the parameters (csrc/optim.hpp), the gradient norm in one more -- instead of torch.optim.SGD; the
+    optimizer state in the checkpoint is the same either way.  `--ema` keeps an exponential moving average of the weights
+    (decay min(DECAY, (1 + t) / (10 + t)) at step t): validation runs on it, the checkpoint carries it as `ema` beside the raw
+    weights (resuming continues both; resuming without `--ema` drops it and says so), and `infer` / `export` load it unless
+    `--no-ema` is given.  `--clip-grad-norm` scales the gradients so that their global L2 norm is at most MAX and skips a step whose
+    norm is not finite; the report line and the scalar log gain `grad_norm`.  The flags themselves are not stored: give them again
+    when resuming.
 """
 import argparse
 import os
@@ -179,6 +188,14 @@ TRAIN_FLAGS = [
           'when resuming', choices=['smooth-l1', 'iou', 'giou', 'diou', 'probiou', 'kld']),
     _flag('--box-loss-weight', float, argparse.SUPPRESS, 'factor on the box loss, finite and > 0 (default 1; needs --box-loss iou, '
           'giou, diou, probiou or kld)', metavar='value'),
+    _flag('--ema', float, argparse.SUPPRESS, 'keep an exponential moving average of the weights with this decay, in (0, 1) (0.9998 is '
+          'customary): it is what gets validated, it is saved beside the raw weights and `infer` loads it.  Give it again when resuming: '
+          'without it a stored average is dropped', metavar='DECAY'),
+    _flag('--clip-grad-norm', float, argparse.SUPPRESS, 'scale the gradients so that their global L2 norm is at most this, finite and '
+          '> 0 (35 is customary); a step whose norm is not finite is skipped.  Not stored in the checkpoint: give it again when resuming',
+          metavar='MAX'),
+    _flag('--fused-step', bool, text='run the optimisation step as one HIP pass over the parameters (implied by --ema and '
+          '--clip-grad-norm; same optimizer state in the checkpoint)', default=argparse.SUPPRESS),
     _flag('--cls-loss', str, argparse.SUPPRESS, 'what the class scores are trained with: focal on the one-hot target (default), or the '
           'quality focal (qfl) / varifocal (vfl) loss on the IoU of the predicted and the assigned box (not with --rotated-bbox).  Not '
           'stored in the checkpoint: give it again when resuming', choices=['focal', 'qfl', 'vfl']),
@@ -190,12 +207,15 @@ INFER_FLAGS = [
     *_SIZES, *_COMMON,
     _flag('--full-precision', bool, text='fp32 instead of mixed precision'),
     _flag('--rotated-bbox', bool, text='the model predicts rotated boxes'),
+    _flag('--no-ema', bool, text='use the raw weights of a checkpoint that also holds averaged ones (--ema of train); the default is '
+          'the average', default=argparse.SUPPRESS),
 ]
 EXPORT_FLAGS = [                                                   # parsed for compatibility; `export` itself is refused
     _flag('--size', int, [1280], nargs='+', metavar='height width'), _flag('--full-precision', bool), _flag('--int8', bool),
     _flag('--calibration-batches', int, 2, metavar='size'), _flag('--calibration-images', str, '', metavar='path'),
     _flag('--calibration-table', str, '', metavar='path'), _flag('--verbose', bool), _flag('--rotated-bbox', bool),
     _flag('--dynamic-batch-opts', int, [1, 8, 16], nargs=3, metavar='value value value'),
+    _flag('--no-ema', bool, default=argparse.SUPPRESS),
 ]
 
 
@@ -280,6 +300,10 @@ def parse(args):
         parser.error('--box-loss {} is not available with --rotated-bbox'.format(parsed.box_loss))
     if getattr(parsed, 'cls_loss', 'focal') != 'focal' and getattr(parsed, 'rotated_bbox', False):
         parser.error('--cls-loss {} is not available with --rotated-bbox'.format(parsed.cls_loss))
+    if hasattr(parsed, 'ema') and not 0 < parsed.ema < 1:                          # (a NaN fails both comparisons)
+        parser.error('--ema must be a decay in (0, 1)')
+    if hasattr(parsed, 'clip_grad_norm') and not 0 < parsed.clip_grad_norm < float('inf'):
+        parser.error('--clip-grad-norm must be finite and > 0')
     if hasattr(parsed, 'mosaic_scale') and not hasattr(parsed, 'mosaic'):
         parser.error('--mosaic-scale needs --mosaic P')
     if hasattr(parsed, 'mosaic'):
@@ -340,6 +364,14 @@ def load_model(args, verbose=False):
         if verbose:
             print('Loading model from {}...'.format(os.path.basename(args.model)))
         model, state = Model.load(filename=args.model, rotated_bbox=args.rotated_bbox)
+        if args.command != 'train' and 'ema' in state:              # the averaged weights are what a trained checkpoint is used with
+            if getattr(args, 'no_ema', False):
+                if verbose:
+                    print('Using the raw weights (--no-ema); the checkpoint also holds averaged ones.')
+            else:
+                model.load_state_dict(state['ema']['state_dict'])
+                if verbose:
+                    print('Using the averaged weights (EMA, {} updates) of the checkpoint.'.format(state['ema']['updates']))
     elif ext in ('.engine', '.plan'):
         raise RuntimeError('TensorRT engines are not supported on MI355X: "{}"'.format(args.model))
     else:
@@ -422,7 +454,8 @@ def worker(rank, args, world, spawned=False):
                                num_workers=args.workers, device_resize=getattr(args, 'device_resize', False),
                                device_augment=getattr(args, 'device_augment', False),
                                augment_free_rotate=tuple(args.augment_free_rotate), mosaic=getattr(args, 'mosaic', 0.0),
-                               mosaic_scale=tuple(getattr(args, 'mosaic_scale', (0.5, 1.0))))
+                               mosaic_scale=tuple(getattr(args, 'mosaic_scale', (0.5, 1.0))), ema_decay=getattr(args, 'ema', None),
+                               clip_grad_norm=getattr(args, 'clip_grad_norm', None), fused_step=getattr(args, 'fused_step', False))
         if args.command == 'infer':
             return infer.infer(model, args.images, args.output, args.resize, args.max_size, args.batch,
                                annotations=args.annotations, mixed_precision=not args.full_precision,

@@ -60,7 +60,7 @@ def _init_prior(conv):
 
 
 class Model(nn.Module):
-    CHECKPOINT_EXTRAS = ('iteration', 'optimizer', 'scheduler')
+    CHECKPOINT_EXTRAS = ('iteration', 'optimizer', 'scheduler', 'ema')   # 'ema': ModelEMA.state_dict() (odtk/optim.py); 'state_dict' stays the raw weights
 
     def __init__(self, backbones='ResNet50FPN', classes=80, ratios=DEFAULT_RATIOS, scales=DEFAULT_SCALES,
                  angles=None, rotated_bbox=False, anchor_ious=[0.4, 0.5], config={}):

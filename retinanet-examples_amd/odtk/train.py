@@ -75,11 +75,15 @@ def lr_schedule(warmup, milestones, gamma):
 
 
 def prepare(model, device, lr=0.01, world=1, rank=0, warmup=1000, milestones=(), gamma=0.1, state=None,
-            bucket_cap_mb=25, weight_decay=0.0001, frozen_bn=True):
+            bucket_cap_mb=25, weight_decay=0.0001, frozen_bn=True, ema_decay=None, clip_grad_norm=None, fused_step=False):
     """Frozen-BN conversion, channels_last, optimizer, DDP wrapper, LR schedule (reference train.py:29-59).
     frozen_bn=False (not a reference option): the batch-norm layers stay live -- what training a backbone from its random
     initialisation needs; the reference never does that (it starts from ImageNet weights, resnet.py:20-22), this image has no
-    weights to start from (tests/test_gpu_trained_ap.py pre-trains its detector this way, then fine-tunes frozen)."""
+    weights to start from (tests/test_gpu_trained_ap.py pre-trains its detector this way, then fine-tunes frozen).
+    `ema_decay`, `clip_grad_norm`, `fused_step` (not reference options either): with any of them the optimizer is odtk/optim.py's
+    `FusedSGD` -- one HIP pass per step that also keeps an exponential moving average of the weights (`optimizer.ema`, a `ModelEMA`
+    with that decay, continued from `state['ema']`) and clips the global gradient norm to `clip_grad_norm` --, otherwise
+    `torch.optim.SGD` exactly as before.  Both read and write the same optimizer state."""
     if frozen_bn:
         model = convert_fixedbn_model(model)
     model = model.to(device)
@@ -88,7 +92,12 @@ def prepare(model, device, lr=0.01, world=1, rank=0, warmup=1000, milestones=(),
     model.freeze_unused_params()
     # every parameter, frozen ones included, exactly like the reference (train.py:34): the param-group layout is
     # part of the checkpoint format (optimizer.load_state_dict), and SGD skips parameters without a gradient
-    optimizer = SGD(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=0.9)
+    fused = ema_decay is not None or clip_grad_norm is not None or fused_step
+    if fused:
+        from .optim import FusedSGD
+        optimizer = FusedSGD(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=0.9, max_norm=clip_grad_norm)
+    else:
+        optimizer = SGD(model.parameters(), lr=lr, weight_decay=weight_decay, momentum=0.9)
     net = model
     if world > 1:
         net = DistributedDataParallel(model, device_ids=[device.index] if device.type == 'cuda' else None,
@@ -97,9 +106,23 @@ def prepare(model, device, lr=0.01, world=1, rank=0, warmup=1000, milestones=(),
     model.train()
     if state and 'optimizer' in state:
         optimizer.load_state_dict(state['optimizer'])
+    if ema_decay is not None:
+        from .optim import ModelEMA
+        ema = ModelEMA(model, ema_decay)                              # starts at the current weights with updates = 0 ...
+        if state and 'ema' in state:
+            ema.load_state_dict(state['ema'])                         # ... unless the checkpoint continues one
+        optimizer.bind_ema(ema)
+    elif state and 'ema' in state and rank == 0:
+        print('The checkpoint holds averaged weights (EMA) but --ema was not given: they are dropped.')
     scheduler = LambdaLR(optimizer, lr_schedule(warmup, list(milestones), gamma))
     if state and 'scheduler' in state:
         scheduler.load_state_dict(state['scheduler'])
+        if fused:
+            # LambdaLR's constructor has just put the schedule's FIRST rate into the optimizer, and loading its state does not put
+            # the stored one back: the first step after a resume would run at the warm-up's starting rate.  The reference path
+            # keeps that behaviour (its bits are the reference's); the fused path resumes exactly.
+            for group, rate in zip(optimizer.param_groups, scheduler.get_last_lr()):
+                group['lr'] = rate
     return model, net, optimizer, scheduler
 
 
@@ -137,12 +160,16 @@ def reduce_losses(cls_loss, box_loss, world, extra=None):
 
 def train_batches(model, state, batches, iterations, device, lr=0.01, warmup=1000, milestones=(), gamma=0.1, world=1,
                   rank=0, mixed_precision=True, log_every=60.0, save_path=None, verbose=True, log_interval=None,
-                  weight_decay=0.0001, validate=None, val_iterations=None, on_report=None, frozen_bn=True):
+                  weight_decay=0.0001, validate=None, val_iterations=None, on_report=None, frozen_bn=True, ema_decay=None,
+                  clip_grad_norm=None, fused_step=False):
     """The training loop of reference train.py:18-214 over any source of (images, targets) batches.
 
     `validate(net, iteration)` is called on EVERY rank (it gathers detections) after iteration `iterations` and after every
     `val_iterations`-th one (reference train.py:185); `on_report(iteration, focal, box, seconds_per_step, lr)` on
-    rank 0 at each logging step (metrics / scalar logs).
+    rank 0 at each logging step (metrics / scalar logs).  `ema_decay`, `clip_grad_norm`, `fused_step`: see `prepare`.  With an EMA
+    the validation runs on the averaged weights (`ModelEMA.swapped`) and the checkpoint carries them as 'ema' beside the raw weights,
+    so a resumed run continues weights, momentum and average alike; with clipping the report line shows the last step's gradient
+    norm, read at the report's own host synchronisation, and `on_report` gets it as the keyword `grad_norm`.
 
     Logging / checkpoint cadence.  The reference all-reduces both losses and tests them on the host EVERY
     step (train.py:126-138: two collectives + one host sync per iteration).  Here the losses are summed on
@@ -153,7 +180,9 @@ def train_batches(model, state, batches, iterations, device, lr=0.01, warmup=100
     RANK 0's measured step time (target: one report per `log_every` seconds) and handed to every rank
     inside the loss all-reduce itself."""
     model, net, optimizer, scheduler = prepare(model, device, lr, world, rank, warmup, milestones, gamma, state,
-                                              weight_decay=weight_decay, frozen_bn=frozen_bn)
+                                              weight_decay=weight_decay, frozen_bn=frozen_bn, ema_decay=ema_decay,
+                                              clip_grad_norm=clip_grad_norm, fused_step=fused_step)
+    ema = getattr(optimizer, 'ema', None)
     amp_dtype = torch.float16 if (mixed_precision and device.type == 'cuda') else None
     scaler = torch.amp.GradScaler('cuda', enabled=amp_dtype is not None) if amp_dtype is not None else None
     iteration = state.get('iteration', 0) if state else 0
@@ -173,16 +202,21 @@ def train_batches(model, state, batches, iterations, device, lr=0.01, warmup=100
         cls_mean, box_mean, agreed = (float(v) for v in both)       # the only host sync of the interval
         if not math.isfinite(cls_mean + box_mean):
             raise RuntimeError('Loss is diverging!\nTry lowering the learning rate.')
+        clipped = {}
+        if clip_grad_norm is not None and optimizer.last_grad_norm is not None:
+            clipped['grad_norm'] = float(optimizer.last_grad_norm)   # (the device is idle: `both` was just read)
         if rank == 0 and verbose:
-            print('[{:{w}}/{}] focal loss: {:.3f}, box loss: {:.3f}, {:.3f}s/{}-batch, {:.1f} im/s, lr: {:.2g}'.format(
+            print('[{:{w}}/{}] focal loss: {:.3f}, box loss: {:.3f}, {:.3f}s/{}-batch, {:.1f} im/s, lr: {:.2g}{}'.format(
                 iteration, iterations, cls_mean, box_mean, per_step, int(round(seen / max(n_mark, 1))), seen / max(now - t_mark, 1e-9),
-                scheduler.get_last_lr()[0], w=len(str(iterations))), flush=True)
+                scheduler.get_last_lr()[0], ', grad norm: {:.3g}'.format(clipped['grad_norm']) if clipped else '',
+                w=len(str(iterations))), flush=True)
         if rank == 0 and on_report is not None:
-            on_report(iteration, cls_mean, box_mean, per_step, scheduler.get_last_lr()[0])
+            on_report(iteration, cls_mean, box_mean, per_step, scheduler.get_last_lr()[0], **clipped)
         if rank == 0 and save_path:
             with ignore_sigint():
+                extras = {'ema': ema.state_dict()} if ema is not None else {}
                 model.save({'path': save_path, 'iteration': iteration, 'optimizer': optimizer.state_dict(),
-                            'scheduler': scheduler.state_dict()})
+                            'scheduler': scheduler.state_dict(), **extras})
         interval = max(1, int(round(agreed)))
         next_log = iteration + interval
         t_mark, n_mark, cls_sum, box_sum = time.time(), 0, None, None
@@ -206,7 +240,11 @@ def train_batches(model, state, batches, iterations, device, lr=0.01, warmup=100
                 report()
                 seen = 0
             if validate is not None and (iteration == iterations or (val_iterations and iteration % val_iterations == 0)):
-                validate(net, iteration)
+                if ema is not None:
+                    with ema.swapped(model):
+                        validate(net, iteration)
+                else:
+                    validate(net, iteration)
                 net.train()
                 t_mark = time.time() if n_mark == 0 else t_mark     # validation time is not step time
         if not progressed:                                           # empty data source: nothing will ever change
@@ -254,7 +292,7 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
           use_dali=False, verbose=True, metrics_url=None, logdir=None, rotate_augment=False, augment_brightness=0.0,
           augment_contrast=0.0, augment_hue=0.0, augment_saturation=0.0, regularization_l2=0.0001, rotated_bbox=False,
           absolute_angle=False, num_workers=2, device=None, device_resize=False, device_augment=False, augment_free_rotate=(0, 0),
-          mosaic=0.0, mosaic_scale=(0.5, 1.0)):
+          mosaic=0.0, mosaic_scale=(0.5, 1.0), ema_decay=None, clip_grad_norm=None, fused_step=False):
     """Train `model` on the images under `path` -- the reference's `train.train` (train.py:18-214), same
     arguments: COCO-style annotations through odtk/data.py (`jitter` = the range of short-side sizes),
     `train_batches` above, periodic validation through `infer.infer`, checkpoints to `state['path']`, scalars
@@ -265,7 +303,9 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
     training image is rotated about its centre by an angle drawn from that range, its boxes with it (odtk/data.py; on the host, or
     with `device_augment` on the device, the same pixels either way); (0, 0) is off.  `mosaic` = the probability with which a
     training item is a mosaic of four images, `mosaic_scale` = (lo, hi) the range of the factor on them (odtk/data.py: CocoDataset;
-    host or device likewise); 0 is off.  It is not stored in the checkpoint."""
+    host or device likewise); 0 is off.  It is not stored in the checkpoint.  `ema_decay`, `clip_grad_norm`, `fused_step`: the fused
+    optimisation step with an average of the weights and gradient clipping (`prepare`, odtk/optim.py); all off, the optimizer is the
+    reference's torch.optim.SGD.  With clipping the scalar `grad_norm` is logged."""
     from . import infer as infer_module
     from .data import DataIterator, RotatedDataIterator
     if use_dali or with_apex:
@@ -292,8 +332,10 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
     log = ScalarLog(logdir) if (is_master and logdir is not None) else None
     if log is not None and verbose:
         print('Writing logs to: {}'.format(logdir))
-    def on_report(iteration, focal, box, per_step, learning_rate):
+    def on_report(iteration, focal, box, per_step, learning_rate, grad_norm=None):
         if log is not None:
+            if grad_norm is not None:
+                log.add_scalar('grad_norm', grad_norm, iteration)
             log.add_scalar('focal_loss', focal, iteration)
             log.add_scalar('box_loss', box, iteration)
             log.add_scalar('learning_rate', learning_rate, iteration)
@@ -317,7 +359,7 @@ def train(model, state, path, annotations, val_path, val_annotations, resize, ma
                              milestones=milestones, gamma=gamma, world=world, rank=rank, mixed_precision=mixed_precision,
                              save_path=(state or {}).get('path'), verbose=verbose, weight_decay=regularization_l2,
                              validate=validate if val_annotations else None, val_iterations=val_iterations,
-                             on_report=on_report)
+                             on_report=on_report, ema_decay=ema_decay, clip_grad_norm=clip_grad_norm, fused_step=fused_step)
     finally:
         if log is not None:
             log.close()
