@@ -118,14 +118,22 @@ int oracle_decode(const float *cls, const float *box, int B, int A, int C, int H
 typedef struct { float x, y; } pt_t;
 #define POLY_MAX 8
 
-/* clip polygon P (4 vertices on entry) by the 4 directed edges of quad R; |shoelace|/2 */
-static float clip_area(const pt_t *R, pt_t *P) {
-  int count = 4;
+/* clip polygon P (4 vertices on entry) by the 4 directed edges of quad R; |shoelace|/2.
+ * st (may be null; bookkeeping only, no arithmetic depends on it): st[0] = the largest number of vertices one clip
+ * edge emitted, before the cap; st[3] = 1 if an edge AFTER one that emitted more than POLY_MAX still finds vertices of
+ * the (capped) polygon strictly on both of its sides, i.e. the dropped vertices changed what a later edge clips. */
+static float clip_area_stats(const pt_t *R, pt_t *P, int *st) {
+  int count = 4, overflowed = 0;
   for (int e = 0; e < 4; ++e) {
     const pt_t r1 = R[e], r2 = R[(e + 1) & 3];
     const float la = r2.y - r1.y, lb = r1.x - r2.x, lc = r2.x * r1.y - r2.y * r1.x;   /* nms_iou.cu:86 */
     float lv[POLY_MAX];
     for (int j = 0; j < count; ++j) lv[j] = la * P[j].x + lb * P[j].y + lc;             /* :90 */
+    if (st && overflowed) {
+      int in = 0, out = 0;
+      for (int j = 0; j < count; ++j) { in |= lv[j] < 0.0f; out |= lv[j] > 0.0f; }
+      if (in && out) st[3] = 1;
+    }
     pt_t Q[POLY_MAX];
     int nq = 0;
     for (int j = 0; j < count; ++j) {
@@ -142,6 +150,10 @@ static float clip_area(const pt_t *R, pt_t *P) {
         ++nq;
       }
     }
+    if (st) {
+      if (nq > st[0]) st[0] = nq;
+      if (nq > POLY_MAX) overflowed = 1;
+    }
     count = nq < POLY_MAX ? nq : POLY_MAX;
     for (int j = 0; j < count; ++j) P[j] = Q[j];
   }
@@ -153,6 +165,8 @@ static float clip_area(const pt_t *R, pt_t *P) {
     }
   return fabsf(area / 2.0f);
 }
+
+static float clip_area(const pt_t *R, pt_t *P) { return clip_area_stats(R, P, 0); }
 
 static float quad_shoelace(const pt_t *R) {
   float s = 0.0f;
@@ -170,18 +184,21 @@ static void rotated_corners(const float *b, float s, float c, pt_t *out) {      
   }
 }
 
-static float overlap_from(const pt_t *I, const pt_t *M) {                                /* :233-247 */
+static float overlap_from_stats(const pt_t *I, const pt_t *M, int *st) {                /* :233-247 */
   pt_t P[POLY_MAX];
   for (int k = 0; k < 4; ++k) {
     P[k].x = I[k].x + (I[k].x == M[k].x ? 0.001f : 0.0f);
     P[k].y = I[k].y + (I[k].y == M[k].y ? 0.001f : 0.0f);
   }
-  const float inter = clip_area(M, P);
+  const float inter = st ? clip_area_stats(M, P, st) : clip_area(M, P);
   const float uni = (fabsf(quad_shoelace(I)) + fabsf(quad_shoelace(M))) / 2.0f;
+  if (st) { st[1] = inter != inter; st[2] = uni != uni; }
   if (inter != inter && uni != uni) return 1.0f;
   if (inter != inter) return 0.0f;
   return inter / (uni - inter);
 }
+
+static float overlap_from(const pt_t *I, const pt_t *M) { return overlap_from_stats(I, M, 0); }
 
 /* boxes [N, 8] corner quads, anchors [M, 8]; out [M, N]  (anchor = subject, box = clipper) */
 void oracle_iou_pairs(const float *boxes, const float *anchors, int N, int M, float *out) {
@@ -203,6 +220,18 @@ float oracle_rotated_overlap(const float *m, const float *j, int own_angle) {
   rotated_corners(j, j[4], j[5], I);
   rotated_corners(m, own_angle ? m[4] : j[4], own_angle ? m[5] : j[5], Mq);
   return overlap_from(I, Mq);
+}
+
+/* the same overlap, plus what the clip went through -- so that tests can PROVE that their inputs reach the degenerate
+ * paths: stats[0] = the largest number of vertices any of the four clip edges emitted, before the cap at POLY_MAX;
+ * stats[1] = `inter` was NaN; stats[2] = `uni` was NaN; stats[3] = after an edge emitted more than POLY_MAX vertices a
+ * later edge still crossed the capped polygon (clip_area_stats). */
+float oracle_rotated_overlap_stats(const float *m, const float *j, int own_angle, int *stats) {
+  pt_t I[4], Mq[4];
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  rotated_corners(j, j[4], j[5], I);
+  rotated_corners(m, own_angle ? m[4] : j[4], own_angle ? m[5] : j[5], Mq);
+  return overlap_from_stats(I, Mq, stats);
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -35,6 +35,8 @@ def library():
         lib.oracle_iou_pairs.argtypes = [_f, _f, ctypes.c_int, ctypes.c_int, _f]
         lib.oracle_rotated_overlap.restype = ctypes.c_float
         lib.oracle_rotated_overlap.argtypes = [_f, _f, ctypes.c_int]
+        lib.oracle_rotated_overlap_stats.restype = ctypes.c_float
+        lib.oracle_rotated_overlap_stats.argtypes = [_f, _f, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         _lib = lib
     return _lib
 
@@ -91,6 +93,16 @@ def iou_pairs(boxes, anchors):
 def rotated_overlap(m, j, own_angle=False):
     m, j = _c(m), _c(j)
     return float(library().oracle_rotated_overlap(_p(m), _p(j), 1 if own_angle else 0))
+
+
+def rotated_overlap_stats(m, j, own_angle=False):
+    """-> (overlap, most vertices one clip edge emitted before the cap, inter was NaN, uni was NaN, a later edge still
+    crossed the polygon after the cap dropped vertices).  The overlap is rotated_overlap's; the rest lets a test prove
+    that its inputs reach the degenerate paths of the clip."""
+    m, j = _c(m), _c(j)
+    st = (ctypes.c_int * 4)()
+    ov = float(library().oracle_rotated_overlap_stats(_p(m), _p(j), 1 if own_angle else 0, st))
+    return ov, int(st[0]), bool(st[1]), bool(st[2]), bool(st[3])
 
 
 # ---------------------------------------------------------------------------------------------
